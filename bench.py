@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the tracking hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU over RCCL.  Under a launcher (RANK / WORLD_SIZE in the environment, e.g.
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`) this process is one rank; invoked
@@ -55,6 +55,10 @@ def parse():
     ap.add_argument("--running", action="store_true", help="headline = the free-running filter instead of the replayed frame")
     ap.add_argument("--repeats", type=int, default=7, help="the timed loop of exactly --steps steps is run this many times; "
                                                            "ms_per_step is the median repetition")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy "
+                         "(float32; rank 0's objects): result.npy (objects, 8) = getResult(), particles.npy "
+                         "(objects, P, 8) = getParticles(), columns x y z w roll pitch yaw weight")
     return ap.parse_args()
 
 
@@ -281,6 +285,32 @@ def reference_operating_point(model, cloud, trans, dev, with_cpu):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261015
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs: `outs` = [(getResult(), getParticles())] per object, as the last timed step left them.  Above
+    DUMP_LIMIT_BYTES the particles are a fixed seeded sample of rows, the same for every object; the row numbers go to
+    particles_index.npy."""
+    import numpy as np
+
+    from pcl_tracking_amd.scene import PARTICLE_DTYPE
+
+    result = np.stack([np.array([r], dtype=PARTICLE_DTYPE).view(np.float32) for r, _ in outs])
+    particles = np.stack([np.ascontiguousarray(p, PARTICLE_DTYPE).view(np.float32).reshape(-1, 8) for _, p in outs])
+    arrays = {"result": result, "particles": particles}
+    n_obj, n_part = particles.shape[:2]
+    if result.nbytes + particles.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - result.nbytes) // (particles.itemsize * 8 * n_obj + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_part, size=keep, replace=False))
+        arrays["particles"] = np.ascontiguousarray(particles[:, idx])
+        arrays["particles_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     spawn_ranks_if_needed()  # --gpus N > 1 without a launcher: becomes the parent of N ranks and never returns
 
@@ -376,6 +406,9 @@ def main():
             for t in ts:
                 t.debugStateSave()
 
+        def outputs():
+            return [(t.getResult(), t.getParticles()) for t in ts]
+
         trk = ts[0] if ts else None
     else:
         from pcl_tracking_amd.dist import HipPhases, ShardedFilter
@@ -394,6 +427,9 @@ def main():
 
         def save_state():
             ph.t.debugStateSave()
+
+        def outputs():
+            return [(sf.getResult(), sf.getParticles())]
 
         trk = ph.t
 
@@ -432,6 +468,8 @@ def main():
     reps = sorted(timed(replay) for _ in range(max(1, ARGS.repeats)))
     dt = reps[len(reps) // 2]
     ms_per_step = dt / ARGS.steps * 1e3
+    if ARGS.dump_outputs and rank == 0:  # the state the last timed step left, before anything below runs a frame
+        dump_outputs(ARGS.dump_outputs, outputs())
     dt_other = sorted(timed(not replay) for _ in range(3))[1]  # the other mode, reported beside the headline
 
     # ranks that actually took part (never a constant: a launch that lost ranks must not report them)

@@ -43,3 +43,38 @@ def test_gpu_count_does_not_load_torch_and_honours_visible_devices(monkeypatch):
         env["HIP_VISIBLE_DEVICES"] = ""
         r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True, env=env)
         assert r.stdout.split()[0] == "0"
+
+
+def test_dump_outputs_writes_float32_and_samples_above_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+
+    from pcl_tracking_amd.scene import PARTICLE_DTYPE
+
+    b = _bench()
+    rng = np.random.default_rng(3)
+
+    def outs(n_obj, n):
+        o = []
+        for _ in range(n_obj):
+            p = rng.standard_normal((n, 8)).astype(np.float32).view(PARTICLE_DTYPE).reshape(-1)
+            o.append((p[0].copy(), p))
+        return o
+
+    small = outs(2, 100)
+    b.dump_outputs(str(tmp_path / "a"), small)
+    res, part = np.load(tmp_path / "a" / "result.npy"), np.load(tmp_path / "a" / "particles.npy")
+    assert res.dtype == np.float32 and res.shape == (2, 8) and part.dtype == np.float32 and part.shape == (2, 100, 8)
+    assert np.array_equal(part[1], small[1][1].view(np.float32).reshape(-1, 8))
+    assert np.array_equal(res[0], part[0, 0]) and not (tmp_path / "a" / "particles_index.npy").exists()
+
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4096)
+    big = outs(2, 1000)
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), big)
+    total = sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b"))  # less the .npy headers
+    assert total <= 4096
+    idx = np.load(tmp_path / "b" / "particles_index.npy")
+    part = np.load(tmp_path / "b" / "particles.npy")
+    assert idx.dtype == np.float64 and len(idx) > 0 and np.all(np.diff(idx) > 0) and part.shape == (2, len(idx), 8)
+    assert np.array_equal(part[0], big[0][1].view(np.float32).reshape(-1, 8)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "particles_index.npy"))  # the sample is fixed
