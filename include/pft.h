@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define PFT_ABI_VERSION 4
+#define PFT_ABI_VERSION 5
 
 /* pcl::PointXYZRGBA (32 B, 16-aligned): x,y,z,1.0f | rgba (bytes b,g,r,a) | 12 B pad */
 typedef struct pft_point_xyzrgba {
@@ -90,7 +90,15 @@ typedef struct pft_config {
   /* NearestPairPointCloudCoherence (true nearest neighbour) instead of ApproxNearestPair...: the alternative the
    * reference keeps commented out at auto_tracking.cpp:237-238, :249 */
   int32_t exact_nearest;
+  /* order of the two population sums (normalizeWeight's weight sum, update()'s weighted mean):
+   *   PFT_SUM_TREE  adjacent-pair trees in double: independent of how the population is split, fast at any size
+   *   PFT_SUM_PCL   PCL's own order: index order, weights in double, pose components in float (one workgroup runs
+   *                 the dependent chains; the poses then follow PCL's tracker bit for bit where the trig agrees) */
+  int32_t sum_order;
 } pft_config;
+
+#define PFT_SUM_TREE 0
+#define PFT_SUM_PCL 1
 
 typedef struct pft_tracker pft_tracker;
 

@@ -7,7 +7,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PFT_LIB_PATH: another build of the same HIP library (A/B timing of compile-time variants, tools/build_variant.py)
 LIB_PATH = os.environ.get("PFT_LIB_PATH") or os.path.join(_HERE, "_build", "libpft_hip.so")
 
-PFT_ABI_VERSION = 4
+PFT_ABI_VERSION = 5
+PFT_SUM_TREE, PFT_SUM_PCL = 0, 1  # pft_config::sum_order
 K_RESAMPLE, K_AABB, K_CROP, K_OCTREE, K_LIKELIHOOD, K_POPULATION, K_PACK, K_COUNT = range(8)
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no input cloud", 3: "no reference cloud", 4: "no usable HIP device",
@@ -35,7 +36,7 @@ class Config(C.Structure):
         ("max_reference_points", C.c_uint32), ("max_input_points", C.c_uint32),
         ("kld_adaptive", C.c_int32), ("maximum_particle_num", C.c_int32), ("kld_delta", C.c_double),
         ("kld_epsilon", C.c_double), ("kld_bin_size", C.c_double * 6), ("motion_ratio", C.c_double),
-        ("exact_nearest", C.c_int32),
+        ("exact_nearest", C.c_int32), ("sum_order", C.c_int32),
     ]
 
 

@@ -184,6 +184,7 @@ extern "C" void pft_config_default(pft_config* c) {
   for (int k = 0; k < 6; k++) c->kld_bin_size[k] = 0.1;  // :212-219
   c->motion_ratio = 0.25;
   c->exact_nearest = 0;  // ApproxNearestPairPointCloudCoherence, as the reference runs (:235-236)
+  c->sum_order = PFT_SUM_TREE;
 }
 
 // KLDAdaptiveParticleFilterTracker::normalQuantile (kld_adaptive_particle_filter.h): despite its name the polynomial
@@ -454,7 +455,8 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   *out = nullptr;
   if (cfg->abi_version != PFT_ABI_VERSION || cfg->particle_num <= 0 || cfg->iteration_num <= 0 ||
       cfg->world_size <= 0 || cfg->rank < 0 || cfg->rank >= cfg->world_size || cfg->use_normal != 0 ||
-      cfg->particle_num % cfg->world_size != 0 || !(cfg->octree_resolution > 0))
+      cfg->particle_num % cfg->world_size != 0 || !(cfg->octree_resolution > 0) ||
+      (cfg->sum_order != PFT_SUM_TREE && cfg->sum_order != PFT_SUM_PCL))
     return PFT_ERR_INVALID_ARG;
   if (cfg->particle_num > PFT_MAX_PARTICLES) return PFT_ERR_CAPACITY;
   if (cfg->kld_adaptive) {
@@ -519,6 +521,7 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   p.kld_eps = cfg->kld_epsilon;
   for (int k = 0; k < 6; k++) p.kld_bin[k] = (float)cfg->kld_bin_size[k];
   p.motion_ratio = cfg->motion_ratio;
+  p.sum_order = cfg->sum_order;
   // capacity in particles: the KLD variant grows / shrinks between particle_num and maximum_particle_num
   t->Pcap = p.kld && p.kld_max > p.P_total ? p.kld_max : p.P_total;
 

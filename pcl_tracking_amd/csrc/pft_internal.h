@@ -75,6 +75,7 @@ struct PftParams {  // immutable per handle, passed by value to kernels
   double kld_eps;        // epsilon_
   float kld_bin[6];      // bin_size_ (a ParticleXYZRPY upstream: floats)
   double motion_ratio;   // motion_ratio_
+  int32_t sum_order;     // pft_config::sum_order: PFT_SUM_TREE (k_population) or PFT_SUM_PCL (k_population_seq)
 };
 
 struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (and by the host for debug)
@@ -242,7 +243,7 @@ void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
 // shard (nullable): sharded handles -- the particles with their raw weights also go into the all-gather's send buffer
 void pftk_finalize_raw(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles,
                        float* raw_out /*nullable*/, pft_particle* shard /*nullable*/);
-// normalise + update + alias prefix form over part_all[0..n) in one launch; from_partials != 0: the raw weights are
+// normalise + update + alias prefix form over part_all[0..n) in one launch, in the handle's summation order; from_partials != 0: the raw weights are
 // first formed from the likelihood partial sums (single-GPU path: fuses k_finalize_raw)
 void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n, int from_partials,
                      int do_normalize, int do_mean, int do_alias);

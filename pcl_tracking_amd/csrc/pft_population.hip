@@ -121,6 +121,29 @@ __device__ __forceinline__ bool grid_barrier(PftHeader* hdr, int k, uint32_t G, 
   return *sh_flag == 0u;
 }
 
+// w = -(float) val, val = sum of particle i's per-chunk likelihood partial sums, in chunk order (both summation orders)
+// (the loads go out eight at a time: one load, wait, add per chunk -- what the plain loop compiles to -- is a chain of
+// nchunk cache latencies, 11 at the headline size and 35 with the 64-point items of a 400-particle filter; the additions
+// stay in chunk order, so the value is the same)
+__device__ __forceinline__ float pop_raw_weight(const PftParams& prm, const PftDev& d, uint32_t i) {
+  double v = 0.0;
+  const double* row = d.partial + (size_t)i * prm.nchunk;
+  for (uint32_t c0 = 0; c0 < prm.nchunk; c0 += 8u) {
+    double tv[8];
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) tv[k] = row[min(c0 + k, prm.nchunk - 1u)];
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++)
+      if (c0 + k < prm.nchunk) v += tv[k];
+  }
+  return -(float)v;
+}
+
+// normalizeWeight's exponential of a non-zero raw weight (both summation orders)
+__device__ __forceinline__ float pop_exp_weight(const PftParams& prm, float w, double wmin, double wmax) {
+  return (float)exp(1.0 - prm.alpha * ((double)w - wmin) / (wmax - wmin));
+}
+
 template <int K>
 __device__ __forceinline__ void population_body(const PftParams& prm, const PftDev& d, uint32_t n, int from_partials,
                                                 int do_norm, int do_mean, int do_alias, PopcSh& S) {
@@ -140,21 +163,8 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
     const uint32_t i = i0 + j;
     wr[j] = 0.0f;
     if (i < n) {
-      if (from_partials) {  // w = -(float) val, val = sum of the per-chunk likelihood partial sums, in chunk order
-        // (the loads go out eight at a time: one load, wait, add per chunk -- what the plain loop compiles to -- is a chain
-        // of nchunk cache latencies, 11 at the headline size and 35 with the 64-point items of a 400-particle filter; the
-        // additions stay in chunk order, so the value is the same)
-        double v = 0.0;
-        const double* row = d.partial + (size_t)i * prm.nchunk;
-        for (uint32_t c0 = 0; c0 < prm.nchunk; c0 += 8u) {
-          double tv[8];
-#pragma unroll
-          for (uint32_t k = 0; k < 8u; k++) tv[k] = row[min(c0 + k, prm.nchunk - 1u)];
-#pragma unroll
-          for (uint32_t k = 0; k < 8u; k++)
-            if (c0 + k < prm.nchunk) v += tv[k];
-        }
-        wr[j] = -(float)v;
+      if (from_partials) {
+        wr[j] = pop_raw_weight(prm, d, i);
         if (!do_norm) P[i].weight = wr[j];
         if (d.raw_w) d.raw_w[i] = wr[j];
       } else {
@@ -210,7 +220,7 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
       sv[j] = 0.0;
       if (i0 + j < n) {
         if (wmax != wmin) {
-          if (wr[j] != 0.0f) wr[j] = (float)exp(1.0 - prm.alpha * ((double)wr[j] - wmin) / (wmax - wmin));
+          if (wr[j] != 0.0f) wr[j] = pop_exp_weight(prm, wr[j], wmin, wmax);
         } else {
           wr[j] = 1.0f / (float)n;
         }
@@ -398,6 +408,243 @@ __global__ __launch_bounds__(PFT_POPC_THREADS) void k_population(PftParams prm, 
   population_body<K>(prm, d, n, from_partials, do_norm, do_mean, do_alias, S);
 }
 
+// ---- PCL summation order (pft_config::sum_order = PFT_SUM_PCL) ----
+// The same stages as k_population with PCL's sums: normalizeWeight adds the weights one after the other in index order in
+// double, update() adds (float)(x * (double)w) one after the other in float, per component.  Those are dependent chains
+// over the whole population, so the kernel is ONE 1024-thread workgroup (no device-scope barrier): the other threads form
+// the chain's terms chunk by chunk in LDS (raw weights, exponentials, products), one lane runs the double chain, six lanes
+// of one wave run the six float chains side by side.  min / max, the exponential, the division and the alias prefix
+// form are those of the tree order (the alias running sums may differ in the last bits of q, as the tree's do).
+#define PFT_SEQ_THREADS 1024
+#define PFT_SEQ_CHUNK 2048  // chain terms staged in LDS per round (a multiple of PFT_SEQ_THREADS and of 4)
+#define PFT_SEQ_WAVES (PFT_SEQ_THREADS / WAVE)
+
+struct SeqSh {
+  float buf[6][PFT_SEQ_CHUNK + 4];  // [0]: weights of the round; [0..5]: the six products of the round (rows 16 B apart
+                                    // in the banks: the six chain lanes read theirs in the same ds_read_b128)
+  double da[PFT_SEQ_WAVES], db[PFT_SEQ_WAVES];
+  uint32_t u[PFT_SEQ_WAVES];
+  double oa[PFT_SEQ_WAVES + 1], ob[PFT_SEQ_WAVES + 1];
+  uint32_t ou[PFT_SEQ_WAVES + 1];
+  double sum;
+  float rep[6];
+};
+
+// s += (double) b[0], .. b[4 * m4 - 1], one after the other (the LDS loads of an unrolled group go out together)
+__device__ __forceinline__ double seq_chain_f64(const float* b, uint32_t m4, double s) {
+  const float4* v = reinterpret_cast<const float4*>(b);
+#pragma unroll 4
+  for (uint32_t k = 0; k < m4; k++) {
+    const float4 x = v[k];
+    s += (double)x.x;
+    s += (double)x.y;
+    s += (double)x.z;
+    s += (double)x.w;
+  }
+  return s;
+}
+
+// r = r + b[0], .. b[4 * m4 - 1] in float, one after the other
+__device__ __forceinline__ float seq_chain_f32(const float* b, uint32_t m4, float r) {
+  const float4* v = reinterpret_cast<const float4*>(b);
+#pragma unroll 4
+  for (uint32_t k = 0; k < m4; k++) {
+    const float4 x = v[k];
+    r = r + x.x;
+    r = r + x.y;
+    r = r + x.z;
+    r = r + x.w;
+  }
+  return r;
+}
+
+// Thread t owns particles t, t + 1024, ..: every global read of P[i].weight in the chain phases is of a value the same
+// thread wrote, and the rounds' padding terms are +0.0 (the chains start at +0.0 and stay off -0.0, so adding +0.0 is
+// exact).  n = particles (KLD variant: the live count is read from d.p_active).
+__global__ __launch_bounds__(PFT_SEQ_THREADS) void k_population_seq(PftParams prm, PftDev d, uint32_t n,
+                                                                    int from_partials, int do_norm, int do_mean,
+                                                                    int do_alias) {
+  __shared__ SeqSh S;
+  if (d.p_active) n = *d.p_active;
+  pft_particle* P = d.part_all;
+  PftHeader* hdr = d.hdr;
+  const uint32_t tid = threadIdx.x;
+  const int lane = lane_id(), w = wave_id();
+
+  // ---- raw (or given) weights, min / max(!= 0) ----
+  double wmin = DBL_MAX, wmax = -DBL_MAX;
+  if (from_partials || do_norm) {
+    for (uint32_t i = tid; i < n; i += PFT_SEQ_THREADS) {
+      float x;
+      if (from_partials) {
+        x = pop_raw_weight(prm, d, i);
+        P[i].weight = x;
+        if (d.raw_w) d.raw_w[i] = x;
+      } else {
+        x = P[i].weight;
+      }
+      const double xd = (double)x;
+      if (wmin > xd) wmin = xd;
+      if (xd != 0.0 && wmax < xd) wmax = xd;
+    }
+  }
+  if (do_norm) {
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+      wmin = fmin(wmin, __shfl_xor(wmin, o));
+      wmax = fmax(wmax, __shfl_xor(wmax, o));
+    }
+    if (lane == 0) {
+      S.da[w] = wmin;
+      S.db[w] = wmax;
+    }
+    __syncthreads();
+    for (int k = 0; k < PFT_SEQ_WAVES; k++) {
+      wmin = fmin(wmin, S.da[k]);
+      wmax = fmax(wmax, S.db[k]);
+    }
+    if (tid == 0) hdr->fit_ratio = wmin;
+    // ---- the exponential; sum += (double) w[i] in index order ----
+    double sum = 0.0;
+    for (uint32_t base = 0; base < n; base += PFT_SEQ_CHUNK) {
+      for (uint32_t j = tid; j < PFT_SEQ_CHUNK; j += PFT_SEQ_THREADS) {
+        const uint32_t i = base + j;
+        float x = 0.0f;
+        if (i < n) {
+          if (wmax != wmin) {
+            x = P[i].weight;
+            if (x != 0.0f) x = pop_exp_weight(prm, x, wmin, wmax);
+          } else {
+            x = 1.0f / (float)n;
+          }
+          P[i].weight = x;
+        }
+        S.buf[0][j] = x;
+      }
+      __syncthreads();
+      if (tid == 0) sum = seq_chain_f64(S.buf[0], (min(n - base, (uint32_t)PFT_SEQ_CHUNK) + 3u) >> 2, sum);
+      __syncthreads();
+    }
+    if (tid == 0) S.sum = sum;
+    __syncthreads();
+    sum = S.sum;
+    const float fs = (float)sum;
+    for (uint32_t i = tid; i < n; i += PFT_SEQ_THREADS) P[i].weight = (sum != 0.0) ? P[i].weight / fs : 1.0f / (float)n;
+  }
+
+  // ---- update(): r = r + (float)(c[i] * (double)w[i]) per component, in index order ----
+  if (do_mean) {
+    constexpr int comp[6] = {0, 1, 2, 4, 5, 6};  // x, y, z, roll, pitch, yaw inside the 8-float particle
+    float r = 0.0f;  // lane k < 6 of wave 0: component k
+    for (uint32_t base = 0; base < n; base += PFT_SEQ_CHUNK) {
+      for (uint32_t j = tid; j < PFT_SEQ_CHUNK; j += PFT_SEQ_THREADS) {
+        const uint32_t i = base + j;
+        if (i < n) {
+          const float* f = reinterpret_cast<const float*>(P + i);
+          const double wd = (double)f[7];
+#pragma unroll
+          for (int k = 0; k < 6; k++) S.buf[k][j] = (float)((double)f[comp[k]] * wd);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 6; k++) S.buf[k][j] = 0.0f;
+        }
+      }
+      __syncthreads();
+      if (w == 0 && lane < 6) r = seq_chain_f32(S.buf[lane], (min(n - base, (uint32_t)PFT_SEQ_CHUNK) + 3u) >> 2, r);
+      __syncthreads();
+    }
+    if (w == 0 && lane < 6) S.rep[lane] = r;
+    __syncthreads();
+    if (tid == 0) {
+      pft_particle orig = hdr->rep, rp;
+      rp.x = S.rep[0]; rp.y = S.rep[1]; rp.z = S.rep[2]; rp.w = 1.0f;
+      rp.roll = S.rep[3]; rp.pitch = S.rep[4]; rp.yaw = S.rep[5];
+      rp.weight = 1.0f / (float)n;
+      pft_particle m;
+      m.x = rp.x - orig.x; m.y = rp.y - orig.y; m.z = rp.z - orig.z; m.w = 1.0f;
+      m.roll = rp.roll - orig.roll; m.pitch = rp.pitch - orig.pitch; m.yaw = rp.yaw - orig.yaw;
+      m.weight = 0.0f;
+      hdr->rep = rp;
+      hdr->motion = m;
+    }
+  }
+
+  // ---- alias prefix form (as k_population's): rounds of 1024 particles from the highest index down, thread t taking
+  //      the particle with t higher-indexed ones in the round; inclusive scans across the workgroup plus the carries ----
+  if (do_alias) {
+    __syncthreads();  // the normalised weights of other threads' particles
+    int32_t* Llist = d.alias_list;
+    int32_t* Hlist = d.alias_list + n;
+    double* Dp = d.alias_pref;      // inclusive running deficit over the L list
+    double* Ep = d.alias_pref + n;  // inclusive running excess over the H list
+    uint32_t cL = 0;                // carries: L particles, deficit, excess of the rounds before
+    double cD = 0.0, cE = 0.0;
+    for (uint32_t base = 0; base < n; base += PFT_SEQ_THREADS) {
+      const uint32_t above = base + tid;  // particles with a higher index than mine
+      const bool act = above < n;
+      const uint32_t i = act ? n - 1u - above : 0u;
+      const double q = act ? (double)(P[i].weight * (float)n) : 1.0;  // float product widened, as genAliasTable does
+      const bool small = act && q < 1.0;
+      uint32_t iu = small ? 1u : 0u;
+      double ia = small ? 1.0 - q : 0.0, ib = (act && !small) ? q - 1.0 : 0.0;
+#pragma unroll
+      for (int o = 1; o < WAVE; o <<= 1) {
+        const uint32_t nu = __shfl_up(iu, o);
+        const double na = __shfl_up(ia, o), nb = __shfl_up(ib, o);
+        if (lane >= o) {
+          iu += nu;
+          ia += na;
+          ib += nb;
+        }
+      }
+      if (lane == WAVE - 1) {
+        S.u[w] = iu;
+        S.da[w] = ia;
+        S.db[w] = ib;
+      }
+      __syncthreads();
+      if (tid == 0) {  // the waves' offsets (exclusive running sums after the carries); [PFT_SEQ_WAVES]: the next carries
+        uint32_t tL = cL;
+        double tD = cD, tE = cE;
+        for (int k = 0; k <= PFT_SEQ_WAVES; k++) {
+          S.ou[k] = tL;
+          S.oa[k] = tD;
+          S.ob[k] = tE;
+          if (k < PFT_SEQ_WAVES) {
+            tL += S.u[k];
+            tD += S.da[k];
+            tE += S.db[k];
+          }
+        }
+      }
+      __syncthreads();
+      const uint32_t oL = S.ou[w];
+      const double oD = S.oa[w], oE = S.ob[w];
+      if (act) {
+        if (small) {
+          const uint32_t off = oL + iu - 1u;
+          Llist[off] = (int32_t)i;
+          Dp[off] = oD + ia;
+          d.alias_pos[i] = off;
+        } else {
+          const uint32_t off = above - (oL + iu);
+          Hlist[off] = (int32_t)i;
+          Ep[off] = oE + ib;
+          d.alias_pos[i] = off | 0x80000000u;
+        }
+      }
+      cL = S.ou[PFT_SEQ_WAVES];
+      cD = S.oa[PFT_SEQ_WAVES];
+      cE = S.ob[PFT_SEQ_WAVES];
+      __syncthreads();  // (the scratch is rewritten by the next round)
+    }
+    if (tid == 0) {
+      hdr->alias_m = cL;
+      hdr->alias_nh = n - cL;
+    }
+  }
+}
+
 // debug / test hook: the explicit (a, q) table of genAliasTable from the prefix-sum form
 __global__ void k_alias_materialize(const pft_particle* __restrict__ P, AliasView v, const PftHeader* __restrict__ hdr,
                                     int32_t* __restrict__ a, double* __restrict__ q) {
@@ -421,6 +668,11 @@ __global__ void k_alias_materialize(const pft_particle* __restrict__ P, AliasVie
 void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n, int from_partials,
                      int do_normalize, int do_mean, int do_alias) {
   if (!n) return;
+  if (p.sum_order == PFT_SUM_PCL) {
+    hipLaunchKernelGGL(k_population_seq, dim3(1), dim3(PFT_SEQ_THREADS), 0, s, p, d, n, from_partials, do_normalize,
+                       do_mean, do_alias);
+    return;
+  }
   // one particle per thread over G workgroups until G would exceed PFT_POP_WGS (the sums are the same adjacent-pair trees for
   // any K and G).  One workgroup with K particles per thread and no device-scope barrier was tried for the reference's
   // own 400-500 particles: slower (the two workgroups' barriers cost less than a second particle per thread).

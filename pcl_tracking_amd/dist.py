@@ -27,7 +27,7 @@ from .tracker import make_reference_tracker
 class HipPhases:
     """per-rank stages of include/pft.h's pft_dist_* API, enqueued on torch's current HIP stream"""
 
-    def __init__(self, particle_num_total, rank, world_size, device, seed=1, iteration_num=2):
+    def __init__(self, particle_num_total, rank, world_size, device, seed=1, iteration_num=2, sum_order="tree"):
         assert particle_num_total % world_size == 0
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -35,7 +35,7 @@ class HipPhases:
         self.P_local = particle_num_total // world_size
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self.t = make_reference_tracker(particle_num=particle_num_total, seed=seed, device_id=self.device.index or 0,
-                                        stream=stream, rank=rank, world_size=world_size)
+                                        stream=stream, rank=rank, world_size=world_size, sum_order=sum_order)
         self.t.setIterationNum(iteration_num)
         self.iteration_num = iteration_num
         # exchange buffers are torch tensors so the collectives see ordinary device memory

@@ -13,7 +13,7 @@
 // all enqueued on ONE HIP stream per rank, no host synchronisation inside a frame.  The app-level steps (model
 // preparation, result consumer) are tracking_app.hpp's, as in auto_tracking_amd.cpp.
 //
-//   dist_tracking_amd <model> <frame0> [frame1 ...] [--particles N_TOTAL] [--seed S] [--model-leaf L] [--id-file PATH]
+//   dist_tracking_amd <model> <frame0> [frame1 ...] [--particles N_TOTAL] [--seed S] [--model-leaf L] [--id-file PATH] [--pcl-sums]
 //
 // Launch: one process per GPU with RANK / WORLD_SIZE / LOCAL_RANK in the environment (as torch.distributed.run or mpirun
 // -x would set them; unset = a single rank).  The ncclUniqueId travels through a file: --id-file PATH, or
@@ -119,10 +119,11 @@ int main(int argc, char** argv) {
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--seed") && i + 1 < argc) opt.seed = std::strtoull(argv[++i], nullptr, 10);
     else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) id_file = argv[++i];
+    else if (!std::strcmp(argv[i], "--pcl-sums")) opt.pcl_sums = true;
     else files.push_back(argv[i]);
   }
   if (files.size() < 2) {
-    std::fprintf(stderr, "usage: %s <model> <frame>... [--particles N_TOTAL] [--seed S] [--model-leaf L] [--id-file PATH]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <model> <frame>... [--particles N_TOTAL] [--seed S] [--model-leaf L] [--id-file PATH] [--pcl-sums]\n", argv[0]);
     return 2;
   }
   const int rank = env_int("RANK", 0), world = env_int("WORLD_SIZE", 1), local_rank = env_int("LOCAL_RANK", rank);

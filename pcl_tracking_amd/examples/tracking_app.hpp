@@ -38,6 +38,7 @@ struct Options {
   bool use_fixed = true;                // the reference's main() passes false (:821): the KLD-adaptive tracker
   double downsampling_grid_size = 0.01; // :824; 0 = the model is used as given
   unsigned threads = 16;                // :845, meaningless on the GPU
+  bool pcl_sums = false;                // PCL's summation order for normalizeWeight / update (pft_config::sum_order)
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -118,6 +119,7 @@ class TrackingApp {
       tr->setResampleLikelihoodThr(0.00);
       tr->setUseNormal(false);
       tr->setSeed(opt_.seed + (uint64_t)obj_id);
+      tr->setSumOrder(opt_.pcl_sums ? PFT_SUM_PCL : PFT_SUM_TREE);
       ApproxNearestPairPointCloudCoherence<RefPointType>::Ptr coherence(new ApproxNearestPairPointCloudCoherence<RefPointType>());
       coherence->addPointCoherence(std::make_shared<DistanceCoherence<RefPointType>>());
       auto color = std::make_shared<HSVColorCoherence<RefPointType>>();

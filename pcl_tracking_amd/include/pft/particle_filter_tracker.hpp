@@ -202,6 +202,8 @@ class ParticleFilterTracker {
   void setAlpha(double a) { guard(); cfg_.alpha = a; }
   void setMinIndices(int) {}  // read only when use_normal_ is true
   void setSeed(uint64_t s) { guard(); cfg_.seed = s; }      // PCL's engines are time(0)-seeded
+  // PFT_SUM_TREE (default) or PFT_SUM_PCL: the order of normalizeWeight's and update()'s population sums (pft.h)
+  void setSumOrder(int order) { guard(); cfg_.sum_order = order; }
   void setDevice(int id) { guard(); cfg_.device_id = id; }
   // enqueue on the caller's HIP stream (hipStream_t; nullptr = the default stream) instead of a stream of the handle's own
   void setStream(void* hip_stream) { guard(); cfg_.stream = hip_stream; cfg_.stream_is_external = 1; }

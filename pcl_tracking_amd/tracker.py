@@ -8,6 +8,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Config, PftError
+
+SUM_ORDERS = {"tree": _lib.PFT_SUM_TREE, "pcl": _lib.PFT_SUM_PCL}
 from .scene import PARTICLE_DTYPE, POINT_DTYPE
 
 
@@ -80,7 +82,9 @@ class NearestPairPointCloudCoherence(ApproxNearestPairPointCloudCoherence):
 class ParticleFilterTracker:
     """pcl::tracking::ParticleFilterOMPTracker<PointXYZRGBA, ParticleXYZRPY>, fixed particle number."""
 
-    def __init__(self, threads=16, device_id=0, stream=None, seed=1, rank=0, world_size=1):
+    def __init__(self, threads=16, device_id=0, stream=None, seed=1, rank=0, world_size=1, sum_order="tree"):
+        """sum_order: "tree" (the default: adjacent-pair trees, independent of how the population is split) or "pcl"
+        (PCL's own order for normalizeWeight's weight sum and update()'s weighted mean; one workgroup runs the chains)"""
         self._L = _lib.load()
         self._cfg = Config()
         self._L.pft_config_default(C.byref(self._cfg))
@@ -91,6 +95,7 @@ class ParticleFilterTracker:
         self._cfg.rank = rank
         self._cfg.world_size = world_size
         self._h = None
+        self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
         self._ref = None
         self._keep = None
@@ -100,6 +105,15 @@ class ParticleFilterTracker:
     def _cfg_guard(self):
         if self._h is not None:
             raise PftError(7, "configuration is fixed once the handle exists")
+
+    def setSumOrder(self, order):
+        """"tree" or "pcl", or a PFT_SUM_* value (pft_create validates it); fixed once the handle exists"""
+        self._cfg_guard()
+        if isinstance(order, str):
+            if order not in SUM_ORDERS:
+                raise PftError(1, "sum_order must be one of %s" % sorted(SUM_ORDERS))
+            order = SUM_ORDERS[order]
+        self._cfg.sum_order = int(order)
 
     def setTrans(self, m):
         self._trans = np.ascontiguousarray(m, np.float32).reshape(4, 4)
