@@ -140,6 +140,28 @@ void pft_to_state(const float m[16], pft_particle* out);
 int pft_get_fit_ratio(pft_tracker* t, double* out);
 int pft_synchronize(pft_tracker* t);
 
+/* ---- change detection (ParticleFilterTracker::setUseChangeDetector, setIntervalOfChangeDetection,
+ *      setMinPointsOfChangeDetection, setResolutionOfChangeDetection; PCL defaults 0, 10, 10, 0.01) ----
+ * Callable at any time.  An iteration whose counter has run out tests the cropped cloud against the one tested last
+ * (OctreePointCloudChangeDetector, double-buffered); a test that finds no new voxel with at least min_points points skips
+ * the octree build, the likelihood, update() and the next resample, and only renormalises the weights it holds.  The
+ * skip is decided on the device: pft_compute stays asynchronous.  The resolution is latched at the first pft_compute, as
+ * PCL creates its detector there.  Single-GPU handles with the approximate coherence only: a sharded handle or the
+ * exact-NN mode returns PFT_ERR_INVALID_ARG for use != 0. */
+int pft_set_change_detector(pft_tracker* t, int use, int interval, int min_points, double resolution);
+int pft_get_change_detector(pft_tracker* t, int* use, int* interval, int* min_points, double* resolution);
+#define PFT_CD_RING 32
+/* detector state (synchronises).  which = 0: the tracker's detector, 1: the instance of pft_debug_change_detect.
+ * gate = changed_, box = {min xyz, max xyz} in double; ring receives up to PFT_CD_RING decisions, oldest first, 5 words each
+ * {tested, changed, new voxels, new points, counter after}; *n_calls = decisions made in all (0 before the first) */
+int pft_debug_change_state(pft_tracker* t, int which, uint32_t* gate, uint32_t* counter, double box[6], int32_t* depth,
+                           uint32_t* ring, uint32_t* n_calls);
+/* one test on an explicit cloud with a detector of its own (never the tracker's); reset != 0 starts that detector afresh
+ * at `resolution` (otherwise the resolution of its last reset holds).  new_idx receives up to cap indices of the points
+ * that lie in new voxels of at least min_points points, ascending; *n_new their number */
+int pft_debug_change_detect(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, int min_points, double resolution,
+                            int reset, uint32_t* new_idx, size_t cap, size_t* n_new);
+
 /* ---- multi-GPU phase API (one handle per rank; the collectives between the phases are issued by
  *      the host layer on the same stream, see pcl_tracking_amd/dist.py and DESIGN.md) ----
  * The host layer owns three device buffers and binds them once:
@@ -170,7 +192,9 @@ int pft_debug_get_scan_stats(pft_tracker* t, uint64_t* queries, uint64_t* scanne
 int pft_debug_set_limits(pft_tracker* t, uint32_t max_words, int sorted_npass);
 /* checkpoint of the filter state between two frames (population with weights, alias table, representative state,
  * motion, KLD particle count, resample epoch); restore is one kernel on the handle's stream.  bench.py replays the
- * same frame with it (stationary workload); tests use it to compare two schedules from the same state. */
+ * same frame with it (stationary workload); tests use it to compare two schedules from the same state.  The change
+ * detector's state is part of the checkpoint; restore returns PFT_ERR_STATE (and changes nothing) if the detector was
+ * first enabled, or its buffers grew with the input, after the save. */
 int pft_debug_state_save(pft_tracker* t);
 int pft_debug_state_restore(pft_tracker* t);
 /* OR `bits` into the device-side error flags right after the next crop launch (what a failing stage leaves behind) */

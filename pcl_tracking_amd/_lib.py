@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("PFT_LIB_PATH") or os.path.join(_HERE, "_build", "libp
 
 PFT_ABI_VERSION = 5
 PFT_SUM_TREE, PFT_SUM_PCL = 0, 1  # pft_config::sum_order
+PFT_CD_RING = 32  # decisions kept by the change detector (pft_debug_change_state)
 K_RESAMPLE, K_AABB, K_CROP, K_OCTREE, K_LIKELIHOOD, K_POPULATION, K_PACK, K_COUNT = range(8)
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no input cloud", 3: "no reference cloud", 4: "no usable HIP device",
@@ -102,6 +103,10 @@ SYMBOLS = [
     ("pft_debug_resample", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _u32, _u32, _sz, _vp]),
     ("pft_debug_pose_to_matrix", C.c_int, [_vp, _vp, _sz, _vp]),
     ("pft_debug_kld_resample", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _u32, _vp, _vp, _P(_u32), _P(_u32)]),
+    ("pft_set_change_detector", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f64]),
+    ("pft_get_change_detector", C.c_int, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_int), _P(_f64)]),
+    ("pft_debug_change_state", C.c_int, [_vp, C.c_int, _P(_u32), _P(_u32), _vp, _P(_i32), _vp, _P(_u32)]),
+    ("pft_debug_change_detect", C.c_int, [_vp, _vp, _sz, C.c_int, _f64, C.c_int, _vp, _sz, _P(_sz)]),
     ("pft_kld_normal_quantile", _f64, [_f64]),
     ("pft_kld_bound", _f64, [C.c_int, _f64, _f64]),
     ("pft_profile_enable", C.c_int, [_vp, C.c_int]),

@@ -27,6 +27,12 @@ struct EvPair {
   hipEvent_t a, b;
 };
 
+// one change-detector instance: the device state and its buffers (pft_change.hip)
+struct CdInst {
+  PftChangeBufs b = {};
+  float4* pts = nullptr;  // pft_debug_change_detect: the explicit cloud
+};
+
 struct pft_tracker {
   pft_config cfg;
   PftParams prm;
@@ -109,6 +115,23 @@ struct pft_tracker {
   int sv_cur = 0;
   uint32_t sv_epoch = 0;
   bool sv_changed = false, sv_valid = false;
+
+  // change detection (pft_set_change_detector): PCL's settings, read on every call except the resolution, which the first
+  // pft_compute latches.  Until the detector is first enabled no detector launch exists and the host keeps
+  // change_counter_ (every iteration evaluates then); from then on the counter and changed_ live on the device
+  int cd_use = 0;
+  uint32_t cd_interval = 10, cd_min_points = 10;
+  double cd_res = 0.01, cd_res_latched = 0.01;
+  bool cd_latched = false, cd_ever = false, gate_on = false;
+  uint32_t cd_counter = 0;
+  CdInst cd, cd_dbg;
+  double cd_dbg_res = 0.01;  // resolution of pft_debug_change_detect's instance since its last reset
+  PftChangeState* sv_cd = nullptr;
+  unsigned long long* sv_cd_key[2] = {nullptr, nullptr};
+  uint32_t* sv_cd_cnt[2] = {nullptr, nullptr};
+  uint32_t sv_cd_cap = 0;
+  bool sv_cd_valid = false;
+  uint32_t sv_cd_counter = 0;
 
   // state
   bool has_ref = false, has_input = false, initialized = false, changed = false;
@@ -378,6 +401,7 @@ static void sync_dev(pft_tracker* t) {
   d.hdr = t->d_hdr;
   d.nn_idx = t->d_nn_idx;
   d.nn_d2 = t->d_nn_d2;
+  d.gate = t->gate_on ? &t->cd.b.st->gate : nullptr;
 }
 
 // Device-side failures (PftHeader::error: octree capacity, depth / growth overflow, the one-pass crop's bounded wait)
@@ -398,7 +422,11 @@ static int check_device_error(pft_tracker* t) {
     m += " [bit4] a device-scope barrier of the population kernel timed out (its workgroups did not become co-resident "
          "within the spin limit): that iteration's normalisation, weighted mean and alias table were NOT written -- the "
          "weights, the result pose and the resampling table are those of the last completed iteration;";
-  if (e & ~23u) m += " [other] " + std::to_string(e & ~23u) + ";";
+  if (e & 32u)
+    m += " [bit5] the change detector's octree outgrew 21-bit keys or its growth steps per test (PFT_MAX_GROW 40): that "
+         "iteration evaluated as if the scene had changed, and the detector forgot its previous crop (its box is never reset: "
+         "once deeper than 21 levels, every later test does the same);";
+  if (e & ~55u) m += " [other] " + std::to_string(e & ~55u) + ";";
   if (e & 7u) m += " the iteration(s) with bit0-2 ran without a target cloud (all likelihoods zero)";
   if (e & 16u) {  // the barrier counters of an interrupted launch are cleared before the next one (the launch resets them itself
                   // when all its workgroups get through; this covers a launch that did not)
@@ -447,6 +475,47 @@ static int ensure_input_capacity(pft_tracker* t, uint32_t n) {
   HIPCHK(t, dalloc(&t->sort.tile_cnt, (size_t)t->sort.ntiles * (PFT_MAX_DEPTH + 2)));
   HIPCHK(t, dalloc(&t->sort.tile_box, (size_t)t->sort.ntiles * 6));
   t->in_cap = cap;
+  return PFT_OK;
+}
+
+static void cd_free(CdInst& c) {
+  dfree(c.b.st); dfree(c.b.set_key[0]); dfree(c.b.set_key[1]); dfree(c.b.set_cnt[0]); dfree(c.b.set_cnt[1]);
+  dfree(c.b.tab_key); dfree(c.b.tab_cnt); dfree(c.b.pt_key); dfree(c.b.mark); dfree(c.pts);
+  c.b.cap = c.b.tab_cap = 0;
+}
+// room for crops of `cap` points; the state and both voxel sets survive a growth (the stream is synchronised by the caller)
+static int cd_reserve(pft_tracker* t, CdInst& c, uint32_t cap, bool debug) {
+  if (cap < 1024u) cap = 1024u;
+  if (c.b.st && cap <= c.b.cap) return PFT_OK;
+  CdInst n;
+  uint32_t tab = 64u;
+  while (tab < 4u * cap) tab <<= 1;
+  HIPCHK(t, dalloc(&n.b.st, 1));
+  for (int k = 0; k < 2; k++) {
+    HIPCHK(t, dalloc(&n.b.set_key[k], cap));
+    HIPCHK(t, dalloc(&n.b.set_cnt[k], cap));
+  }
+  HIPCHK(t, dalloc(&n.b.tab_key, tab));
+  HIPCHK(t, dalloc(&n.b.tab_cnt, tab));
+  HIPCHK(t, dalloc(&n.b.pt_key, cap));
+  if (debug) {
+    HIPCHK(t, dalloc(&n.b.mark, cap));
+    HIPCHK(t, dalloc(&n.pts, cap));
+  }
+  n.b.cap = cap;
+  n.b.tab_cap = tab;
+  if (c.b.st) {
+    HIPCHK(t, hipMemcpyAsync(n.b.st, c.b.st, sizeof(PftChangeState), hipMemcpyDeviceToDevice, t->stream));
+    for (int k = 0; k < 2; k++) {
+      HIPCHK(t, hipMemcpyAsync(n.b.set_key[k], c.b.set_key[k], (size_t)c.b.cap * 8u, hipMemcpyDeviceToDevice, t->stream));
+      HIPCHK(t, hipMemcpyAsync(n.b.set_cnt[k], c.b.set_cnt[k], (size_t)c.b.cap * 4u, hipMemcpyDeviceToDevice, t->stream));
+    }
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+  } else {
+    HIPCHK(t, hipMemsetAsync(n.b.st, 0, sizeof(PftChangeState), t->stream));
+  }
+  cd_free(c);
+  c = n;
   return PFT_OK;
 }
 
@@ -610,6 +679,8 @@ extern "C" void pft_destroy(pft_tracker* t) {
   dfree(t->d_alias_pref); dfree(t->d_pop_part); dfree(t->d_kld_table); dfree(t->d_kld_bins); dfree(t->d_eg_start); dfree(t->d_eg_cnt); dfree(t->d_eg_tile); dfree(t->d_ec_slot); dfree(t->d_ec_cells); dfree(t->d_ec_count); dfree(t->d_ec_base); dfree(t->d_ec_list); dfree(t->d_eq_cellq); dfree(t->d_eq_nq); dfree(t->d_eq_qbase); dfree(t->d_eq_bbase); dfree(t->d_eq_fill); dfree(t->d_eq_blk); dfree(t->d_eq_tiles); dfree(t->d_eq_sorted); dfree(t->d_eq_out); dfree(t->d_hdr); dfree(t->d_nn_idx); dfree(t->d_nn_d2); dfree(t->d_dbg_part);
   dfree(t->d_dbg_hdr); dfree(t->d_dbg_f);
   dfree(t->sv_part); dfree(t->sv_alias_list); dfree(t->sv_alias_pref); dfree(t->sv_alias_pos); dfree(t->sv_hdr);
+  cd_free(t->cd); cd_free(t->cd_dbg);
+  dfree(t->sv_cd); dfree(t->sv_cd_key[0]); dfree(t->sv_cd_key[1]); dfree(t->sv_cd_cnt[0]); dfree(t->sv_cd_cnt[1]);
   if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
   delete t;
 }
@@ -738,6 +809,10 @@ static int set_input_common(pft_tracker* t, const void* src, size_t n, bool devi
   hipSetDevice(t->cfg.device_id);
   int r = ensure_input_capacity(t, (uint32_t)n);
   if (r != PFT_OK) return r;
+  if (t->cd_ever && t->cd.b.cap < t->in_cap) {  // the detector's sets follow the input capacity (crops are at most N points)
+    r = cd_reserve(t, t->cd, t->in_cap, false);
+    if (r != PFT_OK) return r;
+  }
   t->N = (uint32_t)n;
   if (n) {
     const pft_point_xyzrgba* dsrc = static_cast<const pft_point_xyzrgba*>(src);
@@ -836,6 +911,15 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
                                    // population launch: pft_compute raises it there)
       hipLaunchKernelGGL(k_inject_error, dim3(1), dim3(1), 0, t->stream, t->d_hdr, t->inject_error & ~16u);
       t->inject_error &= 16u;
+    }
+    if (t->gate_on) {  // weight()'s change-detector test on this crop: writes the gate the launches below read
+      PftChangeArgs a;
+      a.res = t->cd_res_latched;
+      a.use = t->cd_use ? 1u : 0u;
+      a.interval = t->cd_interval;
+      a.min_points = t->cd_min_points;
+      a.force = 0u;
+      pftk_change_detect(t->stream, t->cd.b, t->d_crop_pts, &t->d_hdr->n_crop, 0u, a, t->h_stat);
     }
   }
   if (t->cfg.exact_nearest) {  // NearestPairPointCloudCoherence: uniform grid + true nearest neighbour, no octree
@@ -962,6 +1046,12 @@ extern "C" int pft_compute(pft_tracker* t) {
     return PFT_ERR_STATE;
   }
   if (!t->initialized) stage_init_particles(t);
+  if (!t->cd_latched) {  // initCompute() creates the change detector at the resolution in force now
+    t->cd_res_latched = t->cd_res;
+    t->cd_latched = true;
+  }
+  t->gate_on = t->cd_ever;
+  sync_dev(t);
   // Steady-state frames as ONE graph launch (opt-in): every launch below is recorded instead of issued, and the recorded
   // graph updates the instantiated one in place (kernel arguments such as the epochs and the particle-buffer parity
   // change from frame to frame, the node sequence only when the builder choice does: then it is instantiated anew).
@@ -986,7 +1076,8 @@ extern "C" int pft_compute(pft_tracker* t) {
         // => changed_ = true => update(); the alias prefix form feeds the next resample: one launch
         pftk_population(t->stream, t->prm, t->dev, t->prm.kld ? t->Pcap : t->prm.P_total, 1, 1, 1, 1);
       }
-      t->changed = true;
+      t->changed = true;  // (the launches of the next iteration; with a detector the device gate decides what they do)
+      if (!t->cd_ever) t->cd_counter = t->cd_counter == 0u ? t->cd_interval : t->cd_counter - 1u;
     }
   };
   const bool graphed = t->use_graph && !t->cfg.exact_nearest && t->changed && !t->prof && t->graph_frames++ >= 2u;
@@ -996,6 +1087,7 @@ extern "C" int pft_compute(pft_tracker* t) {
     const int cur0 = t->cur;
     const uint32_t epoch0 = t->resample_epoch, crop0 = t->crop_epoch, grid0 = t->dev.bbox_grid;
     const pft_point_xyzrgba* raw0 = t->raw_pending;
+    const uint32_t cdc0 = t->cd_counter;
     hipError_t ge = hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal);
     hipGraph_t g = nullptr;
     if (ge == hipSuccess) {
@@ -1036,10 +1128,13 @@ extern "C" int pft_compute(pft_tracker* t) {
       t->crop_epoch = crop0;
       t->dev.bbox_grid = grid0;
       t->raw_pending = raw0;
+      t->cd_counter = cdc0;
       sync_dev(t);
       run_iterations();
     }
   }
+  t->gate_on = false;  // (no other entry point reads the gate: pft_eval_weights and the debug hooks evaluate)
+  sync_dev(t);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     t->err = std::string("kernel launch: ") + hipGetErrorString(e);
@@ -1217,10 +1312,31 @@ extern "C" int pft_debug_state_save(pft_tracker* t) {
   CopySegs cs;
   state_segments(t, true, &cs);
   hipLaunchKernelGGL(k_copy_segments, dim3(64, 5), dim3(256), 0, t->stream, cs);
+  t->sv_cd_valid = false;
+  if (t->cd_ever) {  // the change detector's state and both voxel sets
+    const uint32_t cap = t->cd.b.cap;
+    if (t->sv_cd_cap != cap) {
+      dfree(t->sv_cd); dfree(t->sv_cd_key[0]); dfree(t->sv_cd_key[1]); dfree(t->sv_cd_cnt[0]); dfree(t->sv_cd_cnt[1]);
+      t->sv_cd_cap = 0;
+      HIPCHK(t, dalloc(&t->sv_cd, 1));
+      for (int k = 0; k < 2; k++) {
+        HIPCHK(t, dalloc(&t->sv_cd_key[k], cap));
+        HIPCHK(t, dalloc(&t->sv_cd_cnt[k], cap));
+      }
+      t->sv_cd_cap = cap;
+    }
+    HIPCHK(t, hipMemcpyAsync(t->sv_cd, t->cd.b.st, sizeof(PftChangeState), hipMemcpyDeviceToDevice, t->stream));
+    for (int k = 0; k < 2; k++) {
+      HIPCHK(t, hipMemcpyAsync(t->sv_cd_key[k], t->cd.b.set_key[k], (size_t)cap * 8u, hipMemcpyDeviceToDevice, t->stream));
+      HIPCHK(t, hipMemcpyAsync(t->sv_cd_cnt[k], t->cd.b.set_cnt[k], (size_t)cap * 4u, hipMemcpyDeviceToDevice, t->stream));
+    }
+    t->sv_cd_valid = true;
+  }
   HIPCHK(t, hipStreamSynchronize(t->stream));
   t->sv_cur = t->cur;
   t->sv_epoch = t->resample_epoch;
   t->sv_changed = t->changed;
+  t->sv_cd_counter = t->cd_counter;
   t->sv_valid = true;
   return check_device_error(t);
 }
@@ -1231,14 +1347,29 @@ extern "C" int pft_debug_state_restore(pft_tracker* t) {
     t->err = "pft_debug_state_restore without a saved state";
     return PFT_ERR_STATE;
   }
+  if (t->sv_cd_valid != t->cd_ever || (t->sv_cd_valid && t->cd.b.cap != t->sv_cd_cap)) {
+    // the detector was first enabled, or its sets were re-allocated for a larger input, after the save: the checkpoint
+    // cannot put it back.  Checked before anything is copied, so the handle is left as it was
+    t->err = "pft_debug_state_restore: the change detector was enabled or its buffers grew after pft_debug_state_save";
+    return PFT_ERR_STATE;
+  }
   hipSetDevice(t->cfg.device_id);
   t->cur = t->sv_cur;
   t->resample_epoch = t->sv_epoch;
   t->changed = t->sv_changed;
+  t->cd_counter = t->sv_cd_counter;
   sync_dev(t);
   CopySegs cs;
   state_segments(t, false, &cs);
   hipLaunchKernelGGL(k_copy_segments, dim3(64, 5), dim3(256), 0, t->stream, cs);
+  if (t->sv_cd_valid) {
+    const uint32_t cap = t->sv_cd_cap;
+    HIPCHK(t, hipMemcpyAsync(t->cd.b.st, t->sv_cd, sizeof(PftChangeState), hipMemcpyDeviceToDevice, t->stream));
+    for (int k = 0; k < 2; k++) {
+      HIPCHK(t, hipMemcpyAsync(t->cd.b.set_key[k], t->sv_cd_key[k], (size_t)cap * 8u, hipMemcpyDeviceToDevice, t->stream));
+      HIPCHK(t, hipMemcpyAsync(t->cd.b.set_cnt[k], t->sv_cd_cnt[k], (size_t)cap * 4u, hipMemcpyDeviceToDevice, t->stream));
+    }
+  }
   return PFT_OK;
 }
 
@@ -1605,4 +1736,112 @@ extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, s
   delete h;
   HIPCHK(t, e);
   return PFT_OK;
+}
+
+// ---- change detection ----
+extern "C" int pft_set_change_detector(pft_tracker* t, int use, int interval, int min_points, double resolution) {
+  if (!t || interval < 0 || min_points < 0 || !(resolution > 0)) return PFT_ERR_INVALID_ARG;
+  if (use && t->cfg.world_size != 1) {
+    t->err = "change detection is not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (use && t->cfg.exact_nearest) {
+    t->err = "change detection is not supported with the exact nearest-neighbour coherence (exact_nearest)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  hipSetDevice(t->cfg.device_id);
+  if (use && !t->cd_ever) {
+    // the device takes over change_counter_ and changed_ from the host: every iteration so far evaluated
+    int r = cd_reserve(t, t->cd, t->in_cap, false);
+    if (r != PFT_OK) return r;
+    PftChangeState st;
+    memset(&st, 0, sizeof(st));
+    st.counter = t->cd_counter;
+    st.gate = t->changed ? 1u : 0u;
+    HIPCHK(t, hipMemcpyAsync(t->cd.b.st, &st, sizeof(st), hipMemcpyHostToDevice, t->stream));
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+    t->cd_ever = true;
+  }
+  t->cd_use = use ? 1 : 0;
+  t->cd_interval = (uint32_t)interval;
+  t->cd_min_points = (uint32_t)min_points;
+  t->cd_res = resolution;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_change_detector(pft_tracker* t, int* use, int* interval, int* min_points, double* resolution) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (use) *use = t->cd_use;
+  if (interval) *interval = (int)t->cd_interval;
+  if (min_points) *min_points = (int)t->cd_min_points;
+  if (resolution) *resolution = t->cd_res;
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_change_state(pft_tracker* t, int which, uint32_t* gate, uint32_t* counter, double box[6],
+                                      int32_t* depth, uint32_t* ring, uint32_t* n_calls) {
+  if (!t || (which != 0 && which != 1)) return PFT_ERR_INVALID_ARG;
+  PftChangeState st;
+  memset(&st, 0, sizeof(st));
+  const CdInst& c = which ? t->cd_dbg : t->cd;
+  if (c.b.st) {
+    HIPCHK(t, hipMemcpyAsync(&st, c.b.st, sizeof(st), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+  } else if (which == 0) {  // not enabled yet: the host's bookkeeping
+    st.counter = t->cd_counter;
+    st.gate = t->changed ? 1u : 0u;
+  }
+  if (gate) *gate = st.gate;
+  if (counter) *counter = st.counter;
+  if (box)
+    for (int k = 0; k < 3; k++) {
+      box[k] = st.mn[k];
+      box[3 + k] = st.mx[k];
+    }
+  if (depth) *depth = st.depth;
+  if (n_calls) *n_calls = st.n_calls;
+  if (ring) {
+    const uint32_t m = st.n_calls < PFT_CD_RING ? st.n_calls : PFT_CD_RING;
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t* r = st.ring[(st.n_calls - m + i) % PFT_CD_RING];
+      for (int k = 0; k < 5; k++) ring[5 * i + k] = r[k];
+    }
+  }
+  return check_device_error(t);
+}
+
+extern "C" int pft_debug_change_detect(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, int min_points,
+                                       double resolution, int reset, uint32_t* new_idx, size_t cap, size_t* n_new) {
+  if (!t || (!pts && n) || min_points < 0 || !(resolution > 0)) return PFT_ERR_INVALID_ARG;
+  if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
+  hipSetDevice(t->cfg.device_id);
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  if (reset || !t->cd_dbg.b.st) {
+    cd_free(t->cd_dbg);
+    t->cd_dbg_res = resolution;
+  }
+  int r = cd_reserve(t, t->cd_dbg, (uint32_t)n, true);
+  if (r != PFT_OK) return r;
+  std::vector<float4> xyz(n);
+  for (size_t i = 0; i < n; i++) xyz[i] = make_float4(pts[i].x, pts[i].y, pts[i].z, 0.0f);
+  if (n) HIPCHK(t, hipMemcpyAsync(t->cd_dbg.pts, xyz.data(), n * sizeof(float4), hipMemcpyHostToDevice, t->stream));
+  PftChangeArgs a;
+  a.res = t->cd_dbg_res;
+  a.use = 1u;
+  a.interval = 0u;
+  a.min_points = (uint32_t)min_points;
+  a.force = 1u;
+  pftk_change_detect(t->stream, t->cd_dbg.b, t->cd_dbg.pts, nullptr, (uint32_t)n, a, t->h_stat);
+  std::vector<uint32_t> mark(n);
+  if (n) HIPCHK(t, hipMemcpyAsync(mark.data(), t->cd_dbg.b.mark, n * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  HIPCHK(t, hipGetLastError());
+  size_t k = 0;
+  for (size_t i = 0; i < n; i++)
+    if (mark[i]) {
+      if (new_idx && k < cap) new_idx[k] = (uint32_t)i;
+      k++;
+    }
+  if (n_new) *n_new = k;
+  return check_device_error(t);
 }

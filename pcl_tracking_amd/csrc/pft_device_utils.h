@@ -11,6 +11,9 @@
 // (K x float4 in flight overflows the 128-VGPR budget of a 1024-thread workgroup and spills to scratch)
 #define UNROLL_FENCE(j, every) do { if (((j) % (every)) == (every) - 1) __builtin_amdgcn_sched_barrier(0); } while (0)
 
+// change detection: the gate word (PftDev::gate) says this iteration's test found no change (changed_ == false)
+__device__ __forceinline__ bool pft_unchanged(const uint32_t* gate) { return gate && *gate == 0u; }
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 

@@ -83,7 +83,10 @@ struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (
   uint32_t n_crop;
   uint32_t error;   // per iteration (cleared by the crop kernel): bit0 octree capacity exceeded, bit1 depth / growth steps
                     // exceeded, bit2 one-pass crop gave up waiting, bit3 (internal, transient) sorted builder's radix passes
-                    // too few -> the rescue launch rebuilds, bit4 a device-scope barrier of the population kernel timed out
+                    // too few -> the rescue launch rebuilds, bit4 a device-scope barrier of the population kernel timed out,
+                    // bit5 the change detector's depth (21) or growth steps exceeded -- raised in the pinned status block
+                    // only (host_stat[2..3]): every stage reads a non-zero word here as "no target", and that iteration
+                    // evaluates
   double omin[3], omax[3];
   int32_t depth;
   int32_t use_table;
@@ -194,7 +197,44 @@ struct PftDev {  // device pointers (host-side struct, passed by value)
                         // accumulated since the host last looked (checked and cleared at the host's sync points)
   int32_t* nn_idx;      // debug only
   float* nn_d2;
+  // change detection (pft_change.hip): &PftChangeState::gate while pft_compute drives a handle whose detector has ever been
+  // enabled, else null.  Gate 0 (changed_ == false): the builders and the likelihood return at once, the population
+  // launch only renormalises the stored weights, the resample launches copy the population through
+  const uint32_t* gate;
 };
+
+// per-handle state of the change detector (OctreePointCloudChangeDetector of ParticleFilterTracker), in HBM; apart from
+// PftHeader, whose per-iteration fields the crop kernel clears
+struct PftChangeState {
+  double mn[3], mx[3];  // the detector octree's bounding box: never reset, grows over every crop tested
+  int32_t depth;
+  uint32_t defined;     // bounding_box_defined_
+  uint32_t counter;     // change_counter_
+  uint32_t gate;        // changed_
+  uint32_t n_set[2];    // voxels of the two sets (packed 3 x 21-bit key + point count)
+  uint32_t prev;        // the set of the previous test
+  uint32_t n_calls;     // decisions made; ring[n_calls % PFT_CD_RING] is the next
+  uint32_t ring[PFT_CD_RING][5];  // tested, changed, new voxels, new points, counter after
+};
+struct PftChangeBufs {  // one detector instance (by value into the kernel)
+  PftChangeState* st;
+  unsigned long long* set_key[2];
+  uint32_t* set_cnt[2];
+  unsigned long long* tab_key;  // [tab_cap] open-addressing table of the test (keys)
+  uint32_t* tab_cnt;            // [tab_cap] points of the current crop | bit 31: voxel of the previous set
+  unsigned long long* pt_key;   // [cap] packed key of every point of the crop
+  uint32_t* mark;               // [cap] debug instance: 1 for a point of a counted new voxel (null in the tracker's)
+  uint32_t cap, tab_cap;        // points (and voxels per set); table entries (a power of two >= 4 cap)
+};
+struct PftChangeArgs {
+  double res;           // latched resolution
+  uint32_t use, interval, min_points;
+  uint32_t force;       // debug instance: test regardless of the counter, leave the counter alone
+};
+// the detector launch: counter bookkeeping, and at counter 0 with use != 0 the test of pts[0 .. *n_ptr (or n)) against the
+// previous test.  Writes st->gate; a depth above 21 or too many growth steps raises error bit 5 in host_stat[2..3]
+void pftk_change_detect(hipStream_t s, const PftChangeBufs& b, const float4* pts, const uint32_t* n_ptr, uint32_t n,
+                        const PftChangeArgs& a, uint32_t* host_stat);
 
 // launchers
 void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, int argorder, float4* xyz,

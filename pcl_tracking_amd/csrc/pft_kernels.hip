@@ -56,7 +56,7 @@ template <bool TABLE>
 __global__ void k_resample(PftParams p, const pft_particle* __restrict__ old, AliasView v,
                            const int32_t* __restrict__ ta, const double* __restrict__ tq,
                            const PftHeader* __restrict__ hdr, uint32_t epoch, pft_particle* __restrict__ out,
-                           float* __restrict__ mats) {
+                           float* __restrict__ mats, const uint32_t* gate) {
   uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
   __shared__ double cD[256], cE[256];
   if (!TABLE) {  // coarse levels of the two prefix arrays: 8 of the 13 dependent loads of a search become LDS reads
@@ -76,7 +76,9 @@ __global__ void k_resample(PftParams p, const pft_particle* __restrict__ old, Al
   if (li >= p.P_local) return;
   uint32_t g = p.id_offset + li;
   pft_particle s;
-  if (g == 0) {
+  if (pft_unchanged(gate)) {  // change detection: no resample after an unchanged weight(); the population goes through
+    s = old[g];
+  } else if (g == 0) {
     s = hdr->rep;
   } else {
     uint32_t o[4];
@@ -231,11 +233,12 @@ __global__ __launch_bounds__(1024) void k_aabb(const float4* __restrict__ ref, u
 // (pft_hull.hip: 84 of the 2 048 points of the bench's model), 21 points per lane; the per-point expression, the
 // translation added after the reduction and the NaN-ignoring min / max are those of k_aabb: the same bits.
 #define PFT_BOX_FUSED_MAX 256u  // support points up to which the box is fused into the resample launch
-template <bool BOX>
+template <bool BOX, bool GATED>
 __global__ __launch_bounds__(256) void k_resample4(PftParams p, const pft_particle* __restrict__ old, AliasView v,
                                                    const PftHeader* __restrict__ hdr, uint32_t epoch,
                                                    pft_particle* __restrict__ out, float* __restrict__ mats,
-                                                   const float4* __restrict__ box, float* __restrict__ part) {
+                                                   const float4* __restrict__ box, float* __restrict__ part,
+                                                   const uint32_t* gate) {
   __shared__ double cD[256], cE[256];
   __shared__ float4 lbox[BOX ? PFT_BOX_FUSED_MAX : 1u];
   __shared__ float s_red[6][4];
@@ -258,11 +261,16 @@ __global__ __launch_bounds__(256) void k_resample4(PftParams p, const pft_partic
   const int lane = lane_id(), q0 = lane & ~3;  // first lane of my quad
   const bool live = li < p.P_local;
   const uint32_t g = p.id_offset + li;
+  // change detection: no resample after an unchanged weight() -- the population goes through without noise, and the
+  // matrices and box partials are formed from it as after a draw (the same bits as the last ones)
+  const bool keep = GATED && pft_unchanged(gate), draw = g != 0 && !keep;
   pft_particle s = {0, 0, 0, 1.0f, 0, 0, 0, 0};
   double z0 = 0.0, z1 = 0.0;
   if (live) {
     if (role == 0u) {
-      if (g == 0) {
+      if (keep) {
+        s = old[g];
+      } else if (g == 0) {
         s = hdr->rep;
       } else {
         uint32_t o[4];
@@ -279,17 +287,17 @@ __global__ __launch_bounds__(256) void k_resample4(PftParams p, const pft_partic
           target = (v.pos[k] >> 31) ? a_large : alias_a_small(v, (uint32_t)k);
         s = old[target];
       }
-    } else if (g != 0) {
+    } else if (draw) {
       normal_pair(p, g, role, epoch, 1, z0, z1);
     }
   }
   // the step noise of ParticleXYZRPY::sample: component += (float)(z * sigma + mean), mean = 0; role r holds the pair of
   // components 2r - 2, 2r - 1 (x y | z roll | pitch yaw)
-  const float n0 = (role && g != 0) ? (float)(z0 * p.step_sigma[2u * role - 2u] + 0.0) : 0.0f;
-  const float n1 = (role && g != 0) ? (float)(z1 * p.step_sigma[2u * role - 1u] + 0.0) : 0.0f;
+  const float n0 = (role && draw) ? (float)(z0 * p.step_sigma[2u * role - 2u] + 0.0) : 0.0f;
+  const float n1 = (role && draw) ? (float)(z1 * p.step_sigma[2u * role - 1u] + 0.0) : 0.0f;
   const float nx = __shfl(n0, q0 + 1), ny = __shfl(n1, q0 + 1), nz = __shfl(n0, q0 + 2), nroll = __shfl(n1, q0 + 2),
               npitch = __shfl(n0, q0 + 3), nyaw = __shfl(n1, q0 + 3);
-  if (role == 0u && g != 0) {  // (slot 0 of the population is the representative state verbatim: no noise)
+  if (role == 0u && draw) {  // (slot 0 of the population is the representative state verbatim: no noise)
     s.x += nx; s.y += ny; s.z += nz;
     s.roll += nroll; s.pitch += npitch; s.yaw += nyaw;
   }
@@ -621,18 +629,25 @@ void pftk_resample(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t 
   if (one_lane)
     hipLaunchKernelGGL(k_resample<false>, dim3(cdiv(p.P_local, 256)), dim3(256), 0, s, p, d.part_all,
                        alias_view(d, p.P_total), (const int32_t*)nullptr, (const double*)nullptr, d.hdr, epoch, out,
-                       d.mats);
+                       d.mats, d.gate);
+  else if (d.gate)
+    hipLaunchKernelGGL((k_resample4<false, true>), dim3(cdiv(4u * p.P_local, 256)), dim3(256), 0, s, p, d.part_all,
+                       alias_view(d, p.P_total), d.hdr, epoch, out, d.mats, (const float4*)nullptr, (float*)nullptr, d.gate);
   else
-    hipLaunchKernelGGL(k_resample4<false>, dim3(cdiv(4u * p.P_local, 256)), dim3(256), 0, s, p, d.part_all,
-                       alias_view(d, p.P_total), d.hdr, epoch, out, d.mats, (const float4*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL((k_resample4<false, false>), dim3(cdiv(4u * p.P_local, 256)), dim3(256), 0, s, p, d.part_all,
+                       alias_view(d, p.P_total), d.hdr, epoch, out, d.mats, (const float4*)nullptr, (float*)nullptr, d.gate);
 }
 // resample + pose -> matrix + box partials in one launch; returns the number of partials written to d.bbox_part (0: the
 // support subset is too large for the fused form, nothing was launched)
 uint32_t pftk_resample_box(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out) {
   const uint32_t grid = cdiv(4u * p.P_local, 256);
   if (p.M_box == 0u || p.M_box > PFT_BOX_FUSED_MAX || grid > d.bbox_part_cap) return 0u;
-  hipLaunchKernelGGL(k_resample4<true>, dim3(grid), dim3(256), 0, s, p, d.part_all, alias_view(d, p.P_total), d.hdr, epoch,
-                     out, d.mats, d.ref_box, d.bbox_part);
+  if (d.gate)  // (the instance with the change-detector test: pft_compute on a handle that has a detector)
+    hipLaunchKernelGGL((k_resample4<true, true>), dim3(grid), dim3(256), 0, s, p, d.part_all, alias_view(d, p.P_total), d.hdr,
+                       epoch, out, d.mats, d.ref_box, d.bbox_part, d.gate);
+  else
+    hipLaunchKernelGGL((k_resample4<true, false>), dim3(grid), dim3(256), 0, s, p, d.part_all, alias_view(d, p.P_total), d.hdr,
+                       epoch, out, d.mats, d.ref_box, d.bbox_part, d.gate);
   return grid;
 }
 void pftk_resample_table(hipStream_t s, const PftParams& p, const pft_particle* old, const int32_t* a,
@@ -640,7 +655,7 @@ void pftk_resample_table(hipStream_t s, const PftParams& p, const pft_particle* 
   AliasView v = {};
   v.n = p.P_total;
   hipLaunchKernelGGL(k_resample<true>, dim3(cdiv(p.P_local, 256)), dim3(256), 0, s, p, old, v, a, q, hdr, epoch, out,
-                     (float*)nullptr);
+                     (float*)nullptr, (const uint32_t*)nullptr);
 }
 void pftk_pose_to_matrix(hipStream_t s, const pft_particle* p, uint32_t n, float* mats) {
   if (!n) return;

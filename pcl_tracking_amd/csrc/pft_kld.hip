@@ -30,7 +30,7 @@ __device__ __forceinline__ double kl_bound(uint32_t k, double z, double eps) {
   return (km1 / 2.0 / eps) * chi * chi * chi;
 }
 
-template <bool TABLE>
+template <bool TABLE, bool GATED>
 __global__ __launch_bounds__(KLD_THREADS) void k_resample_kld(PftParams p, PftDev d, const int32_t* __restrict__ ta,
                                                               const double* __restrict__ tq, uint32_t epoch,
                                                               pft_particle* __restrict__ out, float* __restrict__ mats,
@@ -45,6 +45,19 @@ __global__ __launch_bounds__(KLD_THREADS) void k_resample_kld(PftParams p, PftDe
   PftHeader* hdr = d.hdr;
   const pft_particle* old = d.part_all;
   const uint32_t tid = threadIdx.x, maxn = p.kld_max, n_old = hdr->p_active;
+  if (GATED && pft_unchanged(d.gate)) {  // change detection: no resample after an unchanged weight(); particle_num_ stays
+    // (the matrices are written as after a draw, from the same particles: the k_aabb launch behind this one needs them)
+    for (uint32_t i = tid; i < n_old; i += KLD_THREADS) {
+      const pft_particle x = old[i];
+      out[i] = x;
+      if (mats) {
+        float m[12];
+        pose_to_matrix(x, m);
+        store_matrix(mats, i, m);
+      }
+    }
+    return;
+  }
   const bool in_lds = maxn <= 1024u && tab_size <= 2048u;
   uint32_t* tab = in_lds ? s_tab : d.kld_table;  // [tab_size] table, then [maxn] slots, then [maxn] counts
   int32_t* bins = in_lds ? s_bins : d.kld_bins;
@@ -171,9 +184,12 @@ void pftk_resample_kld(hipStream_t s, const PftParams& p, const PftDev& d, uint3
   uint32_t tab_size = 64;
   while (tab_size < 2u * p.kld_max) tab_size <<= 1;
   if (table_a)
-    hipLaunchKernelGGL(k_resample_kld<true>, dim3(1), dim3(KLD_THREADS), 0, s, p, d, table_a, table_q, epoch, out,
+    hipLaunchKernelGGL((k_resample_kld<true, false>), dim3(1), dim3(KLD_THREADS), 0, s, p, d, table_a, table_q, epoch, out,
                        d.mats, tab_size, bins_out);
+  else if (d.gate)  // (the instance with the change-detector test: pft_compute on a handle that has a detector)
+    hipLaunchKernelGGL((k_resample_kld<false, true>), dim3(1), dim3(KLD_THREADS), 0, s, p, d, (const int32_t*)nullptr,
+                       (const double*)nullptr, epoch, out, d.mats, tab_size, bins_out);
   else
-    hipLaunchKernelGGL(k_resample_kld<false>, dim3(1), dim3(KLD_THREADS), 0, s, p, d, (const int32_t*)nullptr,
+    hipLaunchKernelGGL((k_resample_kld<false, false>), dim3(1), dim3(KLD_THREADS), 0, s, p, d, (const int32_t*)nullptr,
                        (const double*)nullptr, epoch, out, d.mats, tab_size, bins_out);
 }

@@ -442,7 +442,7 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
 // cost the headline launch 2 %
 #define PFT_LIK_RUN(UT, FA, LF) likelihood_items<UT, FA, DEBUG_NN, LF, INDIRECT>(prm, d, cx, W, n_particles, D, n_crop, omin, abl)
 
-template <bool DEBUG_NN, bool INDIRECT>
+template <bool DEBUG_NN, bool INDIRECT, bool GATED>
 __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * PFT_LIK_WGS_PER_CU) / 256) void k_likelihood(PftParams prm, PftDev d, uint32_t n_particles,
                                                                 uint32_t lds_bytes, int flags) {
   const int allow_fast = flags & 1;
@@ -453,6 +453,7 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
 #endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const PftHeader* hdr = d.hdr;
+  if (GATED && pft_unchanged(d.gate)) return;  // change detection (GATED instance only): nothing changed, the weights stay
   if (d.p_active) n_particles = *d.p_active;  // KLD variant: particle_num_ lives on the device
   const int D = hdr->depth;
   // (the host launches the form the builder recorded; a mismatch would read the wrong array: no target instead)
@@ -607,8 +608,8 @@ static int g_allow_fast = -1;
 extern "C" int pft_debug_likelihood_occupancy(void) {
   int nb = -1;
   uint32_t lds = ((uint32_t)pftk_max_lds_bytes() / (uint32_t)PFT_LIK_WGS_PER_CU) & ~255u;
-  hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_likelihood<false, false>), PFT_LIK_THREADS, lds) != hipSuccess) return -1;
+  hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_likelihood<false, false, false>), PFT_LIK_THREADS, lds) != hipSuccess) return -1;
   return nb;
 }
 
@@ -628,15 +629,14 @@ void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
   uint32_t lds = ((uint32_t)pftk_max_lds_bytes() / (uint32_t)PFT_LIK_WGS_PER_CU) & ~255u;
   const int dev = pftk_cur_device();
   if (!attr_set[dev]) {
-    const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<false, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<true, false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<false, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<true, true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set[dev] = e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && e4 == hipSuccess;
+    const void* fns[8] = {
+        reinterpret_cast<const void*>(&k_likelihood<false, false, false>), reinterpret_cast<const void*>(&k_likelihood<true, false, false>),
+        reinterpret_cast<const void*>(&k_likelihood<false, true, false>), reinterpret_cast<const void*>(&k_likelihood<true, true, false>),
+        reinterpret_cast<const void*>(&k_likelihood<false, false, true>), reinterpret_cast<const void*>(&k_likelihood<true, false, true>),
+        reinterpret_cast<const void*>(&k_likelihood<false, true, true>), reinterpret_cast<const void*>(&k_likelihood<true, true, true>)};
+    bool ok = true;
+    for (int k = 0; k < 8; k++) ok = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess && ok;
+    attr_set[dev] = ok;
   }
   {  // PFT_GENERIC_DESCENT=1: all-generic descent (A/B and parity cross-check; read per launch: tools/fuzz_parity.py draws it per case)
     const char* e = getenv("PFT_GENERIC_DESCENT");
@@ -654,12 +654,23 @@ void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
   uint32_t need = (items + (PFT_LIK_THREADS / 64) - 1) / (PFT_LIK_THREADS / 64);
   if (need == 0) need = 1;
   if (grid > need) grid = need;
+  // (GATED: pft_compute on a handle with a change detector; the default path launches the instances without the test)
+#define PFT_LIK_LAUNCH(DN, IND)                                                                                          \
+  do {                                                                                                                   \
+    if (d.gate)                                                                                                          \
+      hipLaunchKernelGGL((k_likelihood<DN, IND, true>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
+                         g_allow_fast);                                                                                  \
+    else                                                                                                                 \
+      hipLaunchKernelGGL((k_likelihood<DN, IND, false>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
+                         g_allow_fast);                                                                                  \
+  } while (0)
   if (debug_nn && leaf_indirect)
-    hipLaunchKernelGGL((k_likelihood<true, true>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, g_allow_fast);
+    PFT_LIK_LAUNCH(true, true);
   else if (debug_nn)
-    hipLaunchKernelGGL((k_likelihood<true, false>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, g_allow_fast);
+    PFT_LIK_LAUNCH(true, false);
   else if (leaf_indirect)
-    hipLaunchKernelGGL((k_likelihood<false, true>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, g_allow_fast);
+    PFT_LIK_LAUNCH(false, true);
   else
-    hipLaunchKernelGGL((k_likelihood<false, false>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, g_allow_fast);
+    PFT_LIK_LAUNCH(false, false);
+#undef PFT_LIK_LAUNCH
 }

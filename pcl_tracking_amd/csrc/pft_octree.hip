@@ -24,80 +24,7 @@
 #define TICK_NOW() 0ull
 #endif
 
-struct BuildSh {
-  double mn[3], mx[3];
-  int depth, ngrow;
-  uint32_t cur, err, carry;
-  int jump;
-  uint32_t u32s[40];
-  uint32_t gidx[PFT_MAX_GROW], gshift[PFT_MAX_GROW], gold[PFT_MAX_GROW];
-  double gmin[PFT_MAX_GROW + 1][3];
-  uint32_t lvl[PFT_MAX_DEPTH + 3];
-  // dense top levels (build_tree): per level <= J the occupancy bits in Morton order, their popcount prefix, node counts
-  uint32_t dn_bits[PFT_JUMP_MAX_LEVEL + 1][128], dn_pref[PFT_JUMP_MAX_LEVEL + 1][128], dn_cnt[PFT_JUMP_MAX_LEVEL + 1];
-};
-
-// first point: box = p +- res/2, then getKeyBitSize() pads it to depth 1 (side 2*res - eps)
-__device__ void box_init(BuildSh& S, float4 p0, double res) {
-  const double epsd = (double)FLT_EPSILON;
-  double lo[3] = {(double)p0.x - res / 2, (double)p0.y - res / 2, (double)p0.z - res / 2};
-  double hi[3] = {(double)p0.x + res / 2, (double)p0.y + res / 2, (double)p0.z + res / 2};
-  unsigned mk = 0;
-  for (int a = 0; a < 3; a++) {
-    unsigned k = (unsigned)((hi[a] - lo[a]) / res);
-    mk = k > mk ? k : mk;
-  }
-  unsigned mv = mk > 2u ? mk : 2u;
-  // getKeyBitSize: ceil(log2(max key) - eps), at least... mv is 2 for the one-point box (log(2)/log(2) == 1.0 exactly):
-  // the two double logarithms are only evaluated in the general case
-  double l2 = mv == 2u ? 1.0 : log((double)mv) / log(2.0);
-  unsigned dep = (unsigned)ceil(l2 - (double)FLT_EPSILON);
-  if (dep > 32u) dep = 32u;
-  double side = (double)(1u << dep) * res - epsd;
-  for (int a = 0; a < 3; a++) {
-    double over = (side - (hi[a] - lo[a])) / 2.0;
-    S.mn[a] = lo[a] - over;
-    S.mx[a] = hi[a] + over;
-    S.gmin[0][a] = S.mn[a];
-  }
-  S.depth = (int)dep;
-}
-
-// adoptBoundingBoxToPoint for one violating point: new root above the old one until the point fits;
-// axes without an upper violation extend downwards
-__device__ void box_grow(BuildSh& S, float4 p, uint32_t idx, double res) {
-  const double epsd = (double)FLT_EPSILON;
-  for (;;) {
-    bool lx = p.x < S.mn[0], ly = p.y < S.mn[1], lz = p.z < S.mn[2];
-    bool ux = p.x >= S.mx[0], uy = p.y >= S.mx[1], uz = p.z >= S.mx[2];
-    if (!(lx || ly || lz || ux || uy || uz)) break;
-    int g = S.ngrow;
-    if (g >= PFT_MAX_GROW || S.depth >= PFT_MAX_DEPTH) {
-      S.err |= 2u;
-      break;
-    }
-    double side = (double)(1u << S.depth) * res;
-    S.gidx[g] = idx;
-    S.gshift[g] = (ux ? 0u : 1u) | (uy ? 0u : 2u) | (uz ? 0u : 4u);
-    S.gold[g] = (uint32_t)S.depth;
-    if (!ux) S.mn[0] -= side;
-    if (!uy) S.mn[1] -= side;
-    if (!uz) S.mn[2] -= side;
-    S.depth = S.depth + 1;
-    side = (double)(1u << S.depth) * res - epsd;
-    S.mx[0] = S.mn[0] + side;
-    S.mx[1] = S.mn[1] + side;
-    S.mx[2] = S.mn[2] + side;
-    S.gmin[g + 1][0] = S.mn[0];
-    S.gmin[g + 1][1] = S.mn[1];
-    S.gmin[g + 1][2] = S.mn[2];
-    S.ngrow = g + 1;
-  }
-}
-
-__device__ __forceinline__ bool box_violates(float x, float y, float z, const double* mn, const double* mx) {
-  return (x < mn[0]) || (y < mn[1]) || (z < mn[2]) || (x >= mx[0]) || (y >= mx[1]) || (z >= mx[2]);
-}
+#include "pft_octree_box.h"  // struct BuildSh, box_init, box_grow, box_violates
 
 // Replay of the growth sequence.  The box after the first few dozen points usually contains everything,
 // so: (a) wave 0 alone handles the growth events among the first 1024 points (16 chunks of 64 held in registers, one
@@ -610,6 +537,9 @@ __device__ __forceinline__ void build_regs(const PftParams& prm, const PftDev& d
 
 // rescue != 0: launched behind the sorted builder (pft_octree_sorted.hip); returns at once unless that builder found
 // its radix passes too few for the tree's depth (error bit 3), in which case the tree is built here instead
+// GATED: the instance for pft_compute on a handle with a change detector (reads PftDev::gate); the default path launches
+// the other one, whose code is the builder's without the test
+template <bool GATED>
 __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams prm, PftDev d, uint32_t lds_bytes,
                                                                     int copy_leaf_pts, int rescue) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -621,6 +551,8 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
   // record 0 is valid memory whatever n_crop says)
   const float4 p_first = tid == 0 ? d.crop_pts[0] : make_float4(0, 0, 0, 0);
   const uint32_t n = hdr->n_crop;
+  // change detection: nothing changed, nothing to build (tested behind the loads above, which it would otherwise hold back)
+  if (GATED && pft_unchanged(d.gate)) return;
 
   STAMP(0);
   if (tid == 0) {
@@ -709,19 +641,29 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
 }
 
 // leaf-ordered point records for the likelihood kernel's leaf scan: leaf_pts[pos] = crop_pts[leaf_order[pos]]
+template <bool GATED>
 __global__ __launch_bounds__(256) void k_leaf_gather(PftDev d) {
+  if (GATED && pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   const PftHeader* hdr = d.hdr;
   const uint32_t pos = blockIdx.x * 256u + threadIdx.x;
   if (hdr->error || hdr->depth <= 0 || pos >= hdr->n_crop) return;
   d.leaf_pts[pos] = d.crop_pts[d.leaf_order[pos]];
 }
 
+#ifndef PFT_OCTREE_GATED_TU
+// The GATED instances live in pft_octree_gated.hip: instantiated here beside the default ones, they changed the default
+// builder's code (the box routines gained a second caller), and the default path must stay as it was
+extern template __global__ void k_octree_build<true>(PftParams, PftDev, uint32_t, int, int);
+extern template __global__ void k_leaf_gather<true>(PftDev);
+
 static void pftk_octree_set_attr() {
   static bool attr_set[PFT_MAX_DEVICES];
   const uint32_t lds = ((uint32_t)pftk_max_lds_bytes() - 10240u) & ~15u;
   const int dev = pftk_cur_device();
   if (!attr_set[dev])
-    attr_set[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_octree_build),
+    attr_set[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_octree_build<false>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
+                    hipFuncSetAttribute(reinterpret_cast<const void*>(&k_octree_build<true>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
@@ -739,10 +681,15 @@ bool pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t ex
   const char* e = getenv("PFT_LEAF_INDIRECT");
   const bool indirect = e ? e[0] == '1' : allow_indirect;
   const int mode = indirect ? 2 : (expected_points <= 5000u ? 1 : 0);
-  hipLaunchKernelGGL(k_octree_build, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0);
-  // at most PFT_SORTED_BUILD_MIN-ish points reach this builder in practice, but any crop (<= N) is legal
-  if (mode == 0)
-    hipLaunchKernelGGL(k_leaf_gather, dim3((d.N + 255u) / 256u ? (d.N + 255u) / 256u : 1u), dim3(256), 0, s, d);
+  const dim3 gg((d.N + 255u) / 256u ? (d.N + 255u) / 256u : 1u);
+  if (d.gate) {
+    hipLaunchKernelGGL(k_octree_build<true>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0);
+    if (mode == 0) hipLaunchKernelGGL(k_leaf_gather<true>, gg, dim3(256), 0, s, d);
+  } else {
+    hipLaunchKernelGGL(k_octree_build<false>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0);
+    // at most PFT_SORTED_BUILD_MIN-ish points reach this builder in practice, but any crop (<= N) is legal
+    if (mode == 0) hipLaunchKernelGGL(k_leaf_gather<false>, gg, dim3(256), 0, s, d);
+  }
   return indirect;
 }
 
@@ -750,5 +697,9 @@ bool pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t ex
 void pftk_octree_rescue(hipStream_t s, const PftParams& p, const PftDev& d) {
   pftk_octree_set_attr();
   const uint32_t lds = ((uint32_t)pftk_max_lds_bytes() - 10240u) & ~15u;
-  hipLaunchKernelGGL(k_octree_build, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1);
+  if (d.gate)
+    hipLaunchKernelGGL(k_octree_build<true>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1);
+  else
+    hipLaunchKernelGGL(k_octree_build<false>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1);
 }
+#endif  // PFT_OCTREE_GATED_TU

@@ -61,6 +61,7 @@ __device__ __forceinline__ bool so_violates(float x, float y, float z, const dou
 
 // per-tile AABB of the cropped cloud: {min xyz, max xyz}
 __global__ __launch_bounds__(256) void k_so_tilebox(PftDev d, float* __restrict__ tile_box) {
+  if (pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   __shared__ float sr[6][4];
   const uint32_t n = d.hdr->n_crop, t = blockIdx.x;
   if (t * SO_TILE >= n) return;
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(256) void k_so_tilebox(PftDev d, float* __restrict_
 }
 
 __global__ __launch_bounds__(1024) void k_so_replay(PftParams prm, PftDev d, const float* __restrict__ tile_box) {
+  if (pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   __shared__ ReplaySh S;
   PftHeader* hdr = d.hdr;
   const uint32_t n = hdr->n_crop, tid = threadIdx.x, nt = blockDim.x;
@@ -206,6 +208,7 @@ __global__ __launch_bounds__(1024) void k_so_replay(PftParams prm, PftDev d, con
 
 // ---- keys: final-frame key -> Morton code with the level-1 digit (x<<2|y<<1|z) most significant ----
 __global__ void k_so_keys(PftParams prm, PftDev d, SortBufs sb, uint32_t n_pad) {
+  if (pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_pad) return;
   const PftHeader* hdr = d.hdr;
@@ -247,7 +250,8 @@ __global__ void k_so_keys(PftParams prm, PftDev d, SortBufs sb, uint32_t n_pad) 
 // ---- stable LSD radix sort, 8-bit digit; one wave owns a tile of 1024 elements ----
 __global__ __launch_bounds__(64) void k_rs_hist(const unsigned long long* __restrict__ keys, uint32_t n_pad, int shift,
                                                 uint32_t* __restrict__ hist, uint32_t ntiles, const PftHeader* hdr,
-                                                int pass) {
+                                                int pass, const uint32_t* gate) {
+  if (pft_unchanged(gate)) return;
   if (pass * 8 >= 3 * hdr->depth && pass > 0) return;  // no significant bits left
   __shared__ uint32_t h[SO_BINS];
   const uint32_t t = blockIdx.x, lane = threadIdx.x;
@@ -266,7 +270,8 @@ __global__ __launch_bounds__(64) void k_rs_hist(const unsigned long long* __rest
 
 // one workgroup per digit value: exclusive scan of that bin's per-tile counts, bin total to hist[256*ntiles + b]
 __global__ __launch_bounds__(1024) void k_rs_scan(uint32_t* __restrict__ hist, uint32_t ntiles, const PftHeader* hdr,
-                                                  int pass) {
+                                                  int pass, const uint32_t* gate) {
+  if (pft_unchanged(gate)) return;
   if (pass * 8 >= 3 * hdr->depth && pass > 0) return;
   __shared__ uint32_t scr[20];
   const uint32_t b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -287,7 +292,8 @@ __global__ __launch_bounds__(64) void k_rs_scatter(const unsigned long long* __r
                                                    const uint32_t* __restrict__ vin, unsigned long long* __restrict__ kout,
                                                    uint32_t* __restrict__ vout, uint32_t n_pad, int shift,
                                                    const uint32_t* __restrict__ offs, uint32_t ntiles, const PftHeader* hdr,
-                                                   int pass) {
+                                                   int pass, const uint32_t* gate) {
+  if (pft_unchanged(gate)) return;
   const uint32_t t = blockIdx.x, lane = threadIdx.x;
   const uint32_t base = t * SO_TILE;
   n_pad = hdr->error ? 0u : hdr->n_crop;
@@ -360,6 +366,7 @@ __device__ __forceinline__ int so_first_new_level(unsigned long long ci, unsigne
 }
 
 __global__ __launch_bounds__(256) void k_so_count(PftDev d, SortBufs sb, int buf) {
+  if (pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   __shared__ uint32_t cnt[PFT_MAX_DEPTH + 2];
   const PftHeader* hdr = d.hdr;
   const uint32_t n = hdr->n_crop;
@@ -379,6 +386,7 @@ __global__ __launch_bounds__(256) void k_so_count(PftDev d, SortBufs sb, int buf
 }
 
 __global__ __launch_bounds__(1024) void k_so_scan(PftDev d, SortBufs sb, uint32_t npass) {
+  if (pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   // one wave per level: exclusive scan over the tiles; then the level offsets
   __shared__ uint32_t tot[PFT_MAX_DEPTH + 2];
   PftHeader* hdr = d.hdr;
@@ -424,6 +432,7 @@ __global__ __launch_bounds__(1024) void k_so_scan(PftDev d, SortBufs sb, uint32_
 }
 
 __global__ __launch_bounds__(256) void k_so_emit(PftDev d, SortBufs sb, int buf) {
+  if (pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   __shared__ uint32_t scr[20];
   const PftHeader* hdr = d.hdr;
   const uint32_t n = hdr->n_crop;
@@ -520,10 +529,10 @@ void pftk_octree_sorted(hipStream_t s, const PftParams& p, const PftDev& d, cons
   int buf = 0;
   for (int pass = 0; pass < npass; pass++) {
     const int shift = pass * 8;
-    hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(64), 0, s, sb.keys[buf], n_pad, shift, sb.hist, ntiles, d.hdr, pass);
-    hipLaunchKernelGGL(k_rs_scan, dim3(SO_BINS), dim3(ntiles >= 512 ? 1024 : 256), 0, s, sb.hist, ntiles, d.hdr, pass);
+    hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(64), 0, s, sb.keys[buf], n_pad, shift, sb.hist, ntiles, d.hdr, pass, d.gate);
+    hipLaunchKernelGGL(k_rs_scan, dim3(SO_BINS), dim3(ntiles >= 512 ? 1024 : 256), 0, s, sb.hist, ntiles, d.hdr, pass, d.gate);
     hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(64), 0, s, sb.keys[buf], sb.vals[buf], sb.keys[1 - buf],
-                       sb.vals[1 - buf], n_pad, shift, sb.hist, ntiles, d.hdr, pass);
+                       sb.vals[1 - buf], n_pad, shift, sb.hist, ntiles, d.hdr, pass, d.gate);
     buf = 1 - buf;
   }
   hipLaunchKernelGGL(k_so_count, dim3(ntiles), dim3(256), 0, s, d, sb, buf);

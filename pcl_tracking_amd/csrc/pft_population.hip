@@ -400,10 +400,15 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
   }
 }
 
-template <int K>
+template <int K, bool GATED>
 __global__ __launch_bounds__(PFT_POPC_THREADS) void k_population(PftParams prm, PftDev d, uint32_t n, int from_partials,
                                                                 int do_norm, int do_mean, int do_alias) {
   __shared__ PopcSh S;
+  if (GATED && pft_unchanged(d.gate)) {  // change detection: weight() found no change -- normalizeWeight() of the stored weights only
+    from_partials = 0;
+    do_mean = 0;
+    do_alias = 0;
+  }
   if (d.p_active) n = *d.p_active;  // KLD variant: particle_num_ lives on the device (the grid covers the capacity)
   population_body<K>(prm, d, n, from_partials, do_norm, do_mean, do_alias, S);
 }
@@ -461,10 +466,16 @@ __device__ __forceinline__ float seq_chain_f32(const float* b, uint32_t m4, floa
 // Thread t owns particles t, t + 1024, ..: every global read of P[i].weight in the chain phases is of a value the same
 // thread wrote, and the rounds' padding terms are +0.0 (the chains start at +0.0 and stay off -0.0, so adding +0.0 is
 // exact).  n = particles (KLD variant: the live count is read from d.p_active).
+template <bool GATED>
 __global__ __launch_bounds__(PFT_SEQ_THREADS) void k_population_seq(PftParams prm, PftDev d, uint32_t n,
                                                                     int from_partials, int do_norm, int do_mean,
                                                                     int do_alias) {
   __shared__ SeqSh S;
+  if (GATED && pft_unchanged(d.gate)) {  // change detection: weight() found no change -- normalizeWeight() of the stored weights only
+    from_partials = 0;
+    do_mean = 0;
+    do_alias = 0;
+  }
   if (d.p_active) n = *d.p_active;
   pft_particle* P = d.part_all;
   PftHeader* hdr = d.hdr;
@@ -668,9 +679,14 @@ __global__ void k_alias_materialize(const pft_particle* __restrict__ P, AliasVie
 void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n, int from_partials,
                      int do_normalize, int do_mean, int do_alias) {
   if (!n) return;
+  // (GATED: pft_compute on a handle with a change detector; the default path launches the instances without the test)
   if (p.sum_order == PFT_SUM_PCL) {
-    hipLaunchKernelGGL(k_population_seq, dim3(1), dim3(PFT_SEQ_THREADS), 0, s, p, d, n, from_partials, do_normalize,
-                       do_mean, do_alias);
+    if (d.gate)
+      hipLaunchKernelGGL(k_population_seq<true>, dim3(1), dim3(PFT_SEQ_THREADS), 0, s, p, d, n, from_partials,
+                         do_normalize, do_mean, do_alias);
+    else
+      hipLaunchKernelGGL(k_population_seq<false>, dim3(1), dim3(PFT_SEQ_THREADS), 0, s, p, d, n, from_partials,
+                         do_normalize, do_mean, do_alias);
     return;
   }
   // one particle per thread over G workgroups until G would exceed PFT_POP_WGS (the sums are the same adjacent-pair trees for
@@ -683,13 +699,23 @@ void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
   uint32_t G = 1;
   while (G * PFT_POPC_THREADS * K < n) G <<= 1;  // a power of two: the workgroups are the upper levels of the sum trees
   const dim3 grid(G), block(PFT_POPC_THREADS);
+#define PFT_POP_LAUNCH(KK)                                                                                         \
+  do {                                                                                                               \
+    if (d.gate)                                                                                                      \
+      hipLaunchKernelGGL((k_population<KK, true>), grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean,  \
+                         do_alias);                                                                                  \
+    else                                                                                                             \
+      hipLaunchKernelGGL((k_population<KK, false>), grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean, \
+                         do_alias);                                                                                  \
+  } while (0)
   switch (K) {
-    case 1: hipLaunchKernelGGL(k_population<1>, grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean, do_alias); break;
-    case 2: hipLaunchKernelGGL(k_population<2>, grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean, do_alias); break;
-    case 4: hipLaunchKernelGGL(k_population<4>, grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean, do_alias); break;
-    case 8: hipLaunchKernelGGL(k_population<8>, grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean, do_alias); break;
-    default: hipLaunchKernelGGL(k_population<16>, grid, block, 0, s, p, d, n, from_partials, do_normalize, do_mean, do_alias); break;
+    case 1: PFT_POP_LAUNCH(1); break;
+    case 2: PFT_POP_LAUNCH(2); break;
+    case 4: PFT_POP_LAUNCH(4); break;
+    case 8: PFT_POP_LAUNCH(8); break;
+    default: PFT_POP_LAUNCH(16); break;
   }
+#undef PFT_POP_LAUNCH
 }
 
 void pftk_alias_materialize(hipStream_t s, const PftDev& d, uint32_t n, int32_t* a, double* q) {

@@ -3,7 +3,7 @@
 // (:646-677), then per frame the loop over tracker_dict (:688-697: setInputCloud, compute inside try / catch (int)) and what
 // drawResult / viz_cb do with each pose (:300-326, :432-466).  The shared steps live in tracking_app.hpp.
 //
-//   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums]
+//   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
 //                     [--model-leaf L]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -27,6 +27,20 @@ int main(int argc, char** argv) {
     if (!std::strcmp(argv[i], "--raw")) raw = true;
     else if (!std::strcmp(argv[i], "--kld")) opt.use_fixed = false;
     else if (!std::strcmp(argv[i], "--pcl-sums")) opt.pcl_sums = true;
+    else if (!std::strncmp(argv[i], "--change-detector", 17) && (argv[i][17] == 0 || argv[i][17] == '=')) {
+      opt.change_detector = true;  // --change-detector[=interval,min_points,resolution]; PCL's defaults 10,10,0.01
+      if (argv[i][17] == '=') {
+        unsigned int iv = opt.cd_interval, mp = opt.cd_min_points;
+        double res = opt.cd_resolution;
+        if (std::sscanf(argv[i] + 18, "%u,%u,%lf", &iv, &mp, &res) != 3) {
+          std::fprintf(stderr, "--change-detector=interval,min_points,resolution\n");
+          return 2;
+        }
+        opt.cd_interval = iv;
+        opt.cd_min_points = mp;
+        opt.cd_resolution = res;
+      }
+    }
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -38,7 +52,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--model-leaf L]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L]\n", argv[0]);
     return 2;
   }
 

@@ -39,6 +39,9 @@ struct Options {
   double downsampling_grid_size = 0.01; // :824; 0 = the model is used as given
   unsigned threads = 16;                // :845, meaningless on the GPU
   bool pcl_sums = false;                // PCL's summation order for normalizeWeight / update (pft_config::sum_order)
+  bool change_detector = false;         // PCL's change detector (setUseChangeDetector) with the three settings below
+  unsigned int cd_interval = 10, cd_min_points = 10;
+  double cd_resolution = 0.01;
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -120,6 +123,12 @@ class TrackingApp {
       tr->setUseNormal(false);
       tr->setSeed(opt_.seed + (uint64_t)obj_id);
       tr->setSumOrder(opt_.pcl_sums ? PFT_SUM_PCL : PFT_SUM_TREE);
+      if (opt_.change_detector) {
+        tr->setIntervalOfChangeDetection(opt_.cd_interval);
+        tr->setMinPointsOfChangeDetection(opt_.cd_min_points);
+        tr->setResolutionOfChangeDetection(opt_.cd_resolution);
+        tr->setUseChangeDetector(true);
+      }
       ApproxNearestPairPointCloudCoherence<RefPointType>::Ptr coherence(new ApproxNearestPairPointCloudCoherence<RefPointType>());
       coherence->addPointCoherence(std::make_shared<DistanceCoherence<RefPointType>>());
       auto color = std::make_shared<HSVColorCoherence<RefPointType>>();

@@ -204,6 +204,17 @@ class ParticleFilterTracker {
   void setSeed(uint64_t s) { guard(); cfg_.seed = s; }      // PCL's engines are time(0)-seeded
   // PFT_SUM_TREE (default) or PFT_SUM_PCL: the order of normalizeWeight's and update()'s population sums (pft.h)
   void setSumOrder(int order) { guard(); cfg_.sum_order = order; }
+  // ParticleFilterTracker's change detector (PCL defaults: off, 10, 10, 0.01).  Not guarded: PCL allows them between
+  // frames; they reach the handle whenever it exists.  The resolution is latched at the first compute().
+  // (a setting the handle refuses -- e.g. the detector on an exact-NN handle -- is reported and not kept)
+  void setUseChangeDetector(bool use) { setChangeDetector(use, cd_interval_, cd_min_points_, cd_resolution_); }
+  bool getUseChangeDetector() const { return use_cd_; }
+  void setIntervalOfChangeDetection(unsigned int interval) { setChangeDetector(use_cd_, interval, cd_min_points_, cd_resolution_); }
+  unsigned int getIntervalOfChangeDetection() const { return cd_interval_; }
+  void setMinPointsOfChangeDetection(unsigned int n) { setChangeDetector(use_cd_, cd_interval_, n, cd_resolution_); }
+  unsigned int getMinPointsOfChangeDetection() const { return cd_min_points_; }
+  void setResolutionOfChangeDetection(double res) { setChangeDetector(use_cd_, cd_interval_, cd_min_points_, res); }
+  double getResolutionOfChangeDetection() const { return cd_resolution_; }
   void setDevice(int id) { guard(); cfg_.device_id = id; }
   // enqueue on the caller's HIP stream (hipStream_t; nullptr = the default stream) instead of a stream of the handle's own
   void setStream(void* hip_stream) { guard(); cfg_.stream = hip_stream; cfg_.stream_is_external = 1; }
@@ -308,6 +319,26 @@ class ParticleFilterTracker {
     guard();
     for (size_t i = 0; i < 6 && i < v.size(); i++) dst[i] = v[i];
   }
+  void setChangeDetector(bool use, unsigned int interval, unsigned int min_points, double res) {
+    const bool u0 = use_cd_;
+    const unsigned int i0 = cd_interval_, m0 = cd_min_points_;
+    const double r0 = cd_resolution_;
+    use_cd_ = use;
+    cd_interval_ = interval;
+    cd_min_points_ = min_points;
+    cd_resolution_ = res;
+    if (forwardChangeDetector() != PFT_OK) {
+      use_cd_ = u0;
+      cd_interval_ = i0;
+      cd_min_points_ = m0;
+      cd_resolution_ = r0;
+    }
+  }
+  int forwardChangeDetector() {
+    if (!handle_) return PFT_OK;
+    return check(pft_set_change_detector(handle_, use_cd_ ? 1 : 0, (int)cd_interval_, (int)cd_min_points_, cd_resolution_),
+                 "setUseChangeDetector");
+  }
   int check(int st, const char* what) const {
     if (st != PFT_OK)
       std::fprintf(stderr, "[pft::ParticleFilterTracker::%s] %s: %s\n", what, pft_status_string(st),
@@ -328,6 +359,7 @@ class ParticleFilterTracker {
       return false;
     }
     pft_set_trans(handle_, trans_.m);
+    if (use_cd_ || cd_interval_ != 10 || cd_min_points_ != 10 || cd_resolution_ != 0.01) forwardChangeDetector();
     if (ref_) check(pft_set_reference(handle_, ref_->points.data(), ref_->points.size()), "setReferenceCloud");
     return true;
   }
@@ -340,6 +372,9 @@ class ParticleFilterTracker {
   size_t dev_n_ = 0;
   bool throw_on_failure_ = false;
   CoherencePtr coherence_;
+  bool use_cd_ = false;
+  unsigned int cd_interval_ = 10, cd_min_points_ = 10;
+  double cd_resolution_ = 0.01;
 };
 
 // the class the reference actually news (auto_tracking.cpp:203-204); the thread count is the OpenMP team

@@ -95,6 +95,8 @@ class ParticleFilterTracker:
         self._cfg.rank = rank
         self._cfg.world_size = world_size
         self._h = None
+        # ParticleFilterTracker's change detector: use, interval, min points, resolution (PCL's constructor defaults)
+        self._cd = [False, 10, 10, 0.01]
         self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
         self._ref = None
@@ -114,6 +116,46 @@ class ParticleFilterTracker:
                 raise PftError(1, "sum_order must be one of %s" % sorted(SUM_ORDERS))
             order = SUM_ORDERS[order]
         self._cfg.sum_order = int(order)
+
+    # ---- change detection (PCL allows these at any time: forwarded to the handle whenever it exists) ----
+    def _forward_change_detector(self):
+        if self._h is not None:
+            use, interval, min_points, res = self._cd
+            self._check(self._L.pft_set_change_detector(self._h, int(use), int(interval), int(min_points), float(res)))
+
+    def _set_cd(self, k, v):
+        old = list(self._cd)
+        self._cd[k] = v
+        try:
+            self._forward_change_detector()
+        except PftError:
+            self._cd = old
+            raise
+
+    def setUseChangeDetector(self, use):
+        self._set_cd(0, bool(use))
+
+    def getUseChangeDetector(self):
+        return self._cd[0]
+
+    def setIntervalOfChangeDetection(self, interval):
+        self._set_cd(1, int(interval))
+
+    def getIntervalOfChangeDetection(self):
+        return self._cd[1]
+
+    def setMinPointsOfChangeDetection(self, n):
+        self._set_cd(2, int(n))
+
+    def getMinPointsOfChangeDetection(self):
+        return self._cd[2]
+
+    def setResolutionOfChangeDetection(self, res):
+        """latched at the first compute(), as PCL creates its detector there"""
+        self._set_cd(3, float(res))
+
+    def getResolutionOfChangeDetection(self):
+        return self._cd[3]
 
     def setTrans(self, m):
         self._trans = np.ascontiguousarray(m, np.float32).reshape(4, 4)
@@ -186,6 +228,8 @@ class ParticleFilterTracker:
                 raise PftError(st)
             self._h = h
             self._check(self._L.pft_set_trans(self._h, _ptr(self._trans)))
+            if self._cd != [False, 10, 10, 0.01]:
+                self._forward_change_detector()
             if self._ref is not None:
                 self._check(self._L.pft_set_reference(self._h, _ptr(self._ref), len(self._ref)))
 
@@ -280,6 +324,31 @@ class ParticleFilterTracker:
         return dict(raw=raw, nn_idx=nn_idx, nn_d2=nn_d2, bbox=bbox, crop_idx=crop, octree_depth=depth.value,
                     octree_min=mn, octree_max=mx, n_leaves=nl.value, n_words=nn.value, point_keys=keys,
                     scan_queries=q.value, scan_points=s.value)
+
+    def debugChangeState(self, which=0):
+        """the change detector's state: dict(gate, counter, box (min xyz, max xyz), depth, ring (k, 5): tested, changed,
+        new voxels, new points, counter after -- oldest first --, n_calls).  which=1: the instance of debugChangeDetect"""
+        self._ensure()
+        gate, counter, n_calls = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        depth = C.c_int32()
+        box = np.zeros(6, np.float64)
+        ring = np.zeros((_lib.PFT_CD_RING, 5), np.uint32)
+        self._check(self._L.pft_debug_change_state(self._h, which, C.byref(gate), C.byref(counter), _ptr(box),
+                                                   C.byref(depth), _ptr(ring), C.byref(n_calls)))
+        k = min(n_calls.value, _lib.PFT_CD_RING)
+        return dict(gate=gate.value, counter=counter.value, box=box, depth=depth.value, ring=ring[:k].copy(),
+                    n_calls=n_calls.value)
+
+    def debugChangeDetect(self, cloud, min_points, resolution, reset):
+        """one change-detector test on an explicit cloud (an instance apart from the tracker's) -> indices of the points
+        in new voxels of at least min_points points, ascending"""
+        self._ensure()
+        cloud = np.ascontiguousarray(cloud, POINT_DTYPE)
+        out = np.zeros(max(len(cloud), 1), np.uint32)
+        n = C.c_size_t()
+        self._check(self._L.pft_debug_change_detect(self._h, _ptr(cloud), len(cloud), int(min_points), float(resolution),
+                                                    int(bool(reset)), _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
 
     def debugSetLimits(self, max_words=0, sorted_npass=0):
         """error-path tests: lower the octree node capacity / fix the sorted builder's radix passes"""
@@ -416,9 +485,10 @@ class KLDAdaptiveParticleFilterOMPTracker(ParticleFilterTracker):
         return out[:n.value].copy(), bins[:n.value].copy(), k.value
 
 
-def make_reference_tracker(particle_num=400, seed=1, kld=False, **kw):
+def make_reference_tracker(particle_num=400, seed=1, kld=False, change_detector=None, **kw):
     """A tracker configured exactly as /root/reference/src/auto_tracking.cpp:187-254 does; kld=True takes the
-    use_fixed == false branch (:207-222), the reference's runtime default."""
+    use_fixed == false branch (:207-222), the reference's runtime default.  change_detector=(interval, min_points,
+    resolution) also turns PCL's change detector on (the reference leaves it off)."""
     if kld:
         t = KLDAdaptiveParticleFilterOMPTracker(threads=16, seed=seed, **kw)
         t.setMaximumParticleNum(500)
@@ -447,4 +517,10 @@ def make_reference_tracker(particle_num=400, seed=1, kld=False, **kw):
     coherence.setSearchMethod(OctreeSearch(0.01))
     coherence.setMaximumDistance(0.1)
     t.setCloudCoherence(coherence)
+    if change_detector is not None:
+        interval, min_points, resolution = change_detector
+        t.setIntervalOfChangeDetection(interval)
+        t.setMinPointsOfChangeDetection(min_points)
+        t.setResolutionOfChangeDetection(resolution)
+        t.setUseChangeDetector(True)
     return t
