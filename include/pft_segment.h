@@ -1,0 +1,104 @@
+/*
+ * pft_segment.h -- C ABI of model creation on the device: the two model-creation nodes of the reference
+ * (cmaestre/pcl_tracking, PCL 1.8.0 classes), exported by the same libpft_hip.so as pft.h.
+ *
+ *   create_model_planar_segmentation.cpp:131-203  removeZeroPoints, SACSegmentation (SACMODEL_PLANE, SAC_RANSAC,
+ *                                                 1000 iterations, 0.015 m), ExtractIndices (negative), PassThrough
+ *                                                 y then x, EuclideanClusterExtraction (0.02 m, 500 .. 25 000 points)
+ *   create_model.cpp:131-179                      the same without the plane: PassThrough z, y, x, then the clustering
+ *   params.yaml segm_limits                       the box ("normal table")
+ *
+ * One handle runs the stages in the reference's order as ONE device pipeline over a cloud of 32-byte PCL points:
+ *   1. transform (optional, a 4x4 camera->base matrix standing in for the tf lookup, pft/common.hpp operation order)
+ *   2. removeZeroPoints on the transformed coordinates (NaN, or all of |x|, |y|, |z| below 0.01, is dropped)
+ *   3. plane (optional): RANSAC as SACSegmentation runs it (random = false: mt19937 seeded 12345), refit, inliers
+ *   4. ExtractIndices negative: the plane's final inliers are removed (nothing when no plane is found)
+ *   5. PassThrough box: per-axis enable, inclusive limits, in the base frame
+ *   6. EuclideanClusterExtraction: clusters of min..max points, by size descending, ties by smallest index
+ * The output holds each cluster's indices into the caller's INPUT cloud (ascending) and the input's own points.
+ * There is no CPU path.  DESIGN.md section 3.7 states the rules and their confidence.
+ */
+#ifndef PFT_SEGMENT_H
+#define PFT_SEGMENT_H
+
+#include "pft.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct pft_segment pft_segment;
+
+enum { PFT_PLANE_FOUND = 0, PFT_PLANE_NONE = 1, PFT_PLANE_DISABLED = 2 };
+
+typedef struct pft_segment_config {
+  uint32_t abi_version;        /* PFT_ABI_VERSION */
+  int32_t device_id;
+  void* stream;                /* hipStream_t to run on when stream_is_external, else the handle creates one */
+  int32_t stream_is_external;
+  /* 1. camera -> base (tf lookup, create_model_planar_segmentation.cpp:119), row-major */
+  int32_t transform_enable;
+  float transform[16];
+  /* 3. SACSegmentation (:161-167) */
+  int32_t plane_enable;
+  int32_t max_iterations;      /* setMaxIterations (1000); at most 1919 */
+  double distance_threshold;   /* setDistanceThreshold (0.015) */
+  double probability;          /* setProbability (PCL default 0.99) */
+  uint32_t seed;               /* SampleConsensusModel with random = false: 12345 */
+  int32_t optimize_coefficients; /* setOptimizeCoefficients (PCL default true) */
+  /* 5. PassThrough box (params.yaml segm_limits), base frame, inclusive; axis 0 = x, 1 = y, 2 = z */
+  int32_t box_enable[3];
+  float box_min[3], box_max[3];
+  /* 6. EuclideanClusterExtraction (:184-189) */
+  double cluster_tolerance;    /* 0.02 */
+  int32_t min_cluster_size;    /* 500 */
+  int32_t max_cluster_size;    /* 25 000; min > max: no cluster can be kept, the clustering is skipped */
+  uint32_t max_points;         /* initial capacity; grows on demand */
+} pft_segment_config;
+
+typedef struct pft_segment_plane {
+  int32_t status;              /* PFT_PLANE_FOUND / _NONE (fewer than 3 points, or no good sample) / _DISABLED */
+  uint32_t n_valid;            /* points after removeZeroPoints: the cloud RANSAC runs on */
+  float coefficients[4];       /* final model (refined when optimize_coefficients), ax + by + cz + d */
+  float ransac_coefficients[4];/* the best RANSAC hypothesis before the refit */
+  int32_t sample[3];           /* its sample, indices into the removeZeroPoints output */
+  uint32_t ransac_inliers;     /* inliers of the best hypothesis */
+  uint32_t inliers;            /* final inliers (removed by ExtractIndices negative) */
+  uint32_t iterations;         /* RandomSampleConsensus::iterations_ */
+  uint32_t hypotheses_scored;  /* hypotheses the device scored (whole batches) */
+  uint32_t n_survivors;        /* points handed to the clustering */
+} pft_segment_plane;
+
+/* the reference's planar node: transform off, plane on, box x and y of the "normal table" limits, clusters 0.02 m,
+ * 500 .. 25 000 points.  create_model.cpp is the same with plane_enable = 0 and box_enable[2] = 1. */
+void pft_segment_default_config(pft_segment_config* cfg);
+int pft_segment_create(const pft_segment_config* cfg, pft_segment** out);
+void pft_segment_destroy(pft_segment* s);
+const char* pft_segment_last_error_string(const pft_segment* s);
+
+/* run the pipeline over n points in host / device memory; returns when the clusters are known */
+int pft_segment_apply(pft_segment* s, const pft_point_xyzrgba* host_points, size_t n);
+int pft_segment_apply_device(pft_segment* s, const pft_point_xyzrgba* device_points, size_t n);
+
+int pft_segment_get_plane(const pft_segment* s, pft_segment_plane* plane);
+/* plane inlier indices into the input cloud, ascending: which = 0 the final inliers, 1 those of the best RANSAC
+ * hypothesis (before the refit) */
+int pft_segment_get_plane_inliers(pft_segment* s, int which, int32_t* host_idx, size_t capacity, size_t* n);
+int pft_segment_cluster_count(const pft_segment* s, size_t* n_clusters);
+int pft_segment_cluster_sizes(const pft_segment* s, uint32_t* sizes, size_t capacity);
+/* all clusters one after the other, in cluster order: indices into the input cloud / the input's points */
+int pft_segment_get_cluster_indices(pft_segment* s, int32_t* host_idx, size_t capacity, size_t* n_total);
+int pft_segment_get_cluster_points(pft_segment* s, pft_point_xyzrgba* host_pts, size_t capacity, size_t* n_total);
+/* GPU time of the last apply, milliseconds, without the host's header reads between stages; stage_ms (may be NULL)
+ * receives PFT_SEGMENT_STAGES values */
+enum { PFT_SEGMENT_STAGES = 7 }; /* compaction, sample stream, scoring, replay, refit, clustering, output */
+int pft_segment_last_ms(const pft_segment* s, double* ms, double* stage_ms);
+
+/* the hypotheses of the last apply in draw order, as far as the RANSAC loop consumed them: 3 sample indices (into
+ * the removeZeroPoints output) and the inlier count of each; n = RandomSampleConsensus::iterations_ */
+int pft_debug_segment_hypotheses(pft_segment* s, int32_t* samples, uint32_t* counts, size_t capacity, size_t* n);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

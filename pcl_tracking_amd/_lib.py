@@ -55,6 +55,34 @@ class FilterConfig(C.Structure):
 
 VOXEL_NONE, VOXEL_APPROX, VOXEL_EXACT = 0, 1, 2
 
+
+class SegmentConfig(C.Structure):
+    """pft_segment_config (include/pft_segment.h)"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("device_id", C.c_int32), ("stream", C.c_void_p),
+        ("stream_is_external", C.c_int32),
+        ("transform_enable", C.c_int32), ("transform", C.c_float * 16),
+        ("plane_enable", C.c_int32), ("max_iterations", C.c_int32), ("distance_threshold", C.c_double),
+        ("probability", C.c_double), ("seed", C.c_uint32), ("optimize_coefficients", C.c_int32),
+        ("box_enable", C.c_int32 * 3), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+        ("cluster_tolerance", C.c_double), ("min_cluster_size", C.c_int32), ("max_cluster_size", C.c_int32),
+        ("max_points", C.c_uint32),
+    ]
+
+
+class SegmentPlane(C.Structure):
+    """pft_segment_plane (include/pft_segment.h)"""
+    _fields_ = [
+        ("status", C.c_int32), ("n_valid", C.c_uint32), ("coefficients", C.c_float * 4),
+        ("ransac_coefficients", C.c_float * 4), ("sample", C.c_int32 * 3), ("ransac_inliers", C.c_uint32),
+        ("inliers", C.c_uint32), ("iterations", C.c_uint32), ("hypotheses_scored", C.c_uint32),
+        ("n_survivors", C.c_uint32),
+    ]
+
+
+PLANE_FOUND, PLANE_NONE, PLANE_DISABLED = 0, 1, 2
+SEGMENT_STAGES = ("compaction", "sample", "score", "replay", "refit", "cluster", "output")
+
 # every symbol include/*.h declare: (name, restype, argtypes)
 _vp, _sz, _i32, _u32, _u64, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint64, C.c_double
 _P = C.POINTER
@@ -125,6 +153,21 @@ SYMBOLS = [
     ("pft_filter_get_output", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_filter_get_pass_indices", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_filter_last_ms", C.c_int, [_vp, _P(_f64)]),
+    # include/pft_segment.h
+    ("pft_segment_default_config", None, [_P(SegmentConfig)]),
+    ("pft_segment_create", C.c_int, [_P(SegmentConfig), _P(_vp)]),
+    ("pft_segment_destroy", None, [_vp]),
+    ("pft_segment_last_error_string", C.c_char_p, [_vp]),
+    ("pft_segment_apply", C.c_int, [_vp, _vp, _sz]),
+    ("pft_segment_apply_device", C.c_int, [_vp, _vp, _sz]),
+    ("pft_segment_get_plane", C.c_int, [_vp, _P(SegmentPlane)]),
+    ("pft_segment_get_plane_inliers", C.c_int, [_vp, C.c_int, _vp, _sz, _P(_sz)]),
+    ("pft_segment_cluster_count", C.c_int, [_vp, _P(_sz)]),
+    ("pft_segment_cluster_sizes", C.c_int, [_vp, _vp, _sz]),
+    ("pft_segment_get_cluster_indices", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_segment_get_cluster_points", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_segment_last_ms", C.c_int, [_vp, _P(_f64), _vp]),
+    ("pft_debug_segment_hypotheses", C.c_int, [_vp, _vp, _vp, _sz, _P(_sz)]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

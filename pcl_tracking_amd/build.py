@@ -11,9 +11,9 @@ CSRC = os.path.join(_HERE, "csrc")
 OUT_DIR = os.path.join(_HERE, "_build")
 LIB = os.path.join(OUT_DIR, "libpft_hip.so")
 SOURCES = ["pft_kernels.hip", "pft_octree.hip", "pft_octree_gated.hip", "pft_octree_sorted.hip", "pft_likelihood.hip", "pft_population.hip", "pft_kld.hip", "pft_change.hip", "pft_exact_nn.hip", "pft_hull.hip", "pft_api.hip",
-           "pft_filters.hip"]
+           "pft_filters.hip", "pft_segment.hip"]
 HEADERS = ["pft_internal.h", "pft_device_utils.h", "pft_octree_box.h", os.path.join("..", "..", "include", "pft.h"),
-           os.path.join("..", "..", "include", "pft_filters.h")]
+           os.path.join("..", "..", "include", "pft_filters.h"), os.path.join("..", "..", "include", "pft_segment.h")]
 
 # -ffp-contract=off: PCL's float arithmetic on x86-64 has no FMA contraction; the greedy octree descent
 # compares float sums, so contraction would flip near-ties (DESIGN.md "numerics").
@@ -61,8 +61,9 @@ def build(force=False, verbose=False, extra_flags=()):
 EXAMPLES_DIR = os.path.join(_HERE, "examples")
 EXAMPLE_BIN = os.path.join(OUT_DIR, "auto_tracking_amd")
 DIST_EXAMPLE_BIN = os.path.join(OUT_DIR, "dist_tracking_amd")
+CREATE_MODEL_BIN = os.path.join(OUT_DIR, "create_model_amd")
 _EXAMPLE_DEPS = [os.path.join(EXAMPLES_DIR, "tracking_app.hpp")] + [
-    os.path.join(_HERE, "include", "pft", h) for h in ("particle_filter_tracker.hpp", "filters.hpp", "pcd_io.hpp", "common.hpp", "id_exchange.hpp")]
+    os.path.join(_HERE, "include", "pft", h) for h in ("particle_filter_tracker.hpp", "filters.hpp", "pcd_io.hpp", "common.hpp", "id_exchange.hpp", "segmentation.hpp")]
 
 
 def _build_host_program(src, out, extra, force, verbose):
@@ -97,7 +98,14 @@ def build_dist_example(force=False, verbose=False):
     return _build_host_program(os.path.join(EXAMPLES_DIR, "dist_tracking_amd.cpp"), DIST_EXAMPLE_BIN, extra, force, verbose)
 
 
+def build_create_model_example(force=False, verbose=False):
+    """the model-creation driver (create_model_planar_segmentation.cpp / create_model.cpp without ROS) over
+    pft/segmentation.hpp: writes <j>.pcd per cluster for auto_tracking_amd"""
+    return _build_host_program(os.path.join(EXAMPLES_DIR, "create_model_amd.cpp"), CREATE_MODEL_BIN, [], force, verbose)
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_example(force="--force" in sys.argv, verbose=True))
     print(build_dist_example(force="--force" in sys.argv, verbose=True))
+    print(build_create_model_example(force="--force" in sys.argv, verbose=True))

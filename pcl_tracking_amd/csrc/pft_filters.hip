@@ -264,6 +264,20 @@ __global__ __launch_bounds__(64) void k_f_rs_scatter(const uint32_t* __restrict_
   }
 }
 
+int pftk_radix_sort_pairs(hipStream_t s, uint32_t* key[2], uint32_t* val[2], uint32_t n, int bits, uint32_t* hist) {
+  const uint32_t ntiles = (n + F_TILE - 1) / F_TILE;
+  int cur = 0;
+  if (n == 0) return cur;
+  for (int shift = 0; shift < bits; shift += 8) {
+    hipLaunchKernelGGL(k_f_rs_hist, dim3(ntiles), dim3(64), 0, s, key[cur], n, shift, hist, ntiles);
+    hipLaunchKernelGGL(k_f_rs_scan, dim3(F_BINS), dim3(F_THREADS), 0, s, hist, ntiles, (uint32_t)F_BINS);
+    hipLaunchKernelGGL(k_f_rs_scatter, dim3(ntiles), dim3(64), 0, s, key[cur], val[cur], key[1 - cur], val[1 - cur], n,
+                       shift, hist, ntiles);
+    cur = 1 - cur;
+  }
+  return cur;
+}
+
 // VoxelGrid: run heads in sorted order, per-tile head counts
 __global__ __launch_bounds__(F_THREADS) void k_f_heads_exact(FParams p, FDev d, const uint32_t* __restrict__ skey) {
   __shared__ uint32_t su[20];
@@ -1062,15 +1076,7 @@ static int run_pipeline(pft_filter* f, const pft_point_xyzrgba* d_in, size_t n) 
       hipLaunchKernelGGL(k_f_bounds, dim3(1), dim3(F_THREADS), 0, s, p, d, ntiles);
       hipLaunchKernelGGL(k_f_keys_exact, dim3(nblk), dim3(F_THREADS), 0, s, p, d);
     }
-    int cur = 0;
-    for (int pass = 0; pass < npass; pass++) {
-      const int shift = 8 * pass;
-      hipLaunchKernelGGL(k_f_rs_hist, dim3(ntiles), dim3(64), 0, s, d.key[cur], p.n, shift, d.hist, ntiles);
-      hipLaunchKernelGGL(k_f_rs_scan, dim3(F_BINS), dim3(F_THREADS), 0, s, d.hist, ntiles, (uint32_t)F_BINS);
-      hipLaunchKernelGGL(k_f_rs_scatter, dim3(ntiles), dim3(64), 0, s, d.key[cur], d.val[cur], d.key[1 - cur],
-                         d.val[1 - cur], p.n, shift, d.hist, ntiles);
-      cur = 1 - cur;
-    }
+    const int cur = pftk_radix_sort_pairs(s, d.key, d.val, p.n, 8 * npass, d.hist);
     const uint32_t* skey = d.key[cur];
     const uint32_t* sval = d.val[cur];
     if (p.mode == PFT_VOXEL_EXACT) {

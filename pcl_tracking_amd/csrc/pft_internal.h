@@ -291,3 +291,7 @@ void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
 void pftk_alias_materialize(hipStream_t s, const PftDev& d, uint32_t n, int32_t* a, double* q);
 int pftk_max_lds_bytes();
 int pftk_cur_device();  // current HIP device ordinal, clamped to [0, PFT_MAX_DEVICES)
+// stable LSD radix sort (pft_filters.hip) of (key, val) pairs by the low `bits` bits of the key, 8 bits per pass;
+// key[cur] / val[cur] hold the input, the return value is the index of the buffers that hold the output.
+// hist: >= 256 * ceil(n / 1024) + 256 words.
+int pftk_radix_sort_pairs(hipStream_t s, uint32_t* key[2], uint32_t* val[2], uint32_t n, int bits, uint32_t* hist);

@@ -1,0 +1,1467 @@
+// pft_segment.hip -- model creation on the device (include/pft_segment.h): the stages of the reference's
+// create_model_planar_segmentation.cpp:131-203 / create_model.cpp:131-179 as one chain of launches on one stream.
+//
+//   compaction   k_sg_zero (transform + removeZeroPoints flags), k_sg_scan, k_sg_emit: ordered stream compaction
+//                (per-tile counts, one-workgroup scan, scatter), the same three kernels serve every compaction below
+//   sample       k_sg_sample: one workgroup replays boost::mt19937 (state in LDS, the 624-word twist split over the
+//                lanes) and drawIndexSample's swaps (a sparse map in LDS), emitting good samples in draw order
+//   scoring      k_sg_score: a tile of points per workgroup against a batch of SG_BATCH planes in LDS; exact counts
+//   replay       k_sg_replay: RandomSampleConsensus::computeModel's loop over the scored batch, in one lane
+//   refit        k_sg_select + compaction of the best hypothesis' inliers, k_sg_refit: the nine sequential float sums
+//                of computeMeanAndCovarianceMatrix (nine lanes) and pcl::eigen33 (one lane)
+//   clustering   survivors sorted by a grid-cell key (the radix sort of pft_filters.hip), lock-free union-find over
+//                neighbour cells, component sizes, the size filter, the ordering rule, a stable sort by cluster rank
+//
+// Each recalled PCL rule has ONE switch point here, marked "RULE <name>", mirrored in tests/segment_model.py.
+#include <math.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "pft_device_utils.h"
+#include "../../include/pft_segment.h"
+
+#define SG_TILE 1024u
+#define SG_THREADS 256
+#define SG_BATCH 128u        // hypotheses per scoring batch
+#define SG_MAPCAP 8192u      // sparse map of drawIndexSample's swaps (LDS), power of two
+#define SG_MAPMAX 6144u      // entries allowed (load factor 0.75)
+#define SG_MAX_ITER 1919     // the sampler draws whole batches: 3 + 3 hmax <= SG_MAPMAX with hmax = 1920
+#define SG_SAMPLE_CHECKS 1000u  // SampleConsensusModel::max_sample_checks_
+#define SG_EMPTY 0xFFFFFFFFu
+#define SG_OVERFLOW 0xFFFFFFFEu  // sample slot: the sparse map filled up before this sample could be drawn
+#define SG_CELL_SLACK 1.03125    // cell side = tol / 2 * (1 + 2^-5): see cell_coord
+#define SG_MAX_AXIS_CELLS (1u << 17)
+#define SG_SCORE_PTS 8u      // points per thread in k_sg_score
+
+enum { SG_ERR_MAP = 1u };
+static_assert(3u + 3u * (((SG_MAX_ITER + 1u) + SG_BATCH - 1u) / SG_BATCH * SG_BATCH) <= SG_MAPMAX,
+              "the sparse map holds every position the sampler's whole batches can touch without redraws");
+
+struct SgHdr {
+  // RandomSampleConsensus state, carried from batch to batch
+  double k;
+  int32_t best_count, best_h;
+  uint32_t iterations, decided, skipped;
+  uint32_t n_valid, n_ransac_inl, n_fin, n_surv;
+  uint32_t err;
+  float coef_ransac[4];
+  float coef_final[4];
+  uint32_t n_cells, n_clusters, n_total;
+  float bmin[3], bmax[3];
+  // sampler state (mt19937 and the sparse map live in HBM between batches)
+  uint32_t mt_pos, map_count, emitted;
+};
+
+struct SgHyp {
+  int32_t* sample;   // [hmax][3], SG_EMPTY in [0] = no sample could be drawn, SG_OVERFLOW = the sparse map is full
+  float4* coef;      // [hmax]
+  uint32_t* count;   // [hmax]
+};
+
+struct SgParams {
+  uint32_t n;
+  int transform_enable;
+  float T[12];
+  float zero_thr;    // 0.01 as the float compare of fabs(float) < 0.01 (double) needs it
+  float dist_thr;    // distance threshold, same
+  double log_probability;
+  int max_iterations;
+  uint32_t seed;
+  int box_enable[3];
+  float box_min[3], box_max[3];
+  float tol2;        // (float)(tol * tol)
+  float inv_cell;    // 1 / (tol / 2 * SG_CELL_SLACK)
+  uint32_t nx, ny, nz;
+  uint32_t min_size, max_size;
+};
+
+// smallest float f with (double)x < thr <=> x < f for every float x: how `float < double` compares
+static float float_bound_below(double thr) {
+  float f = (float)thr;
+  if ((double)f < thr) f = nextafterf(f, INFINITY);
+  return f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// ordered stream compaction: per-tile counts of a flag array, one-workgroup scan, scatter of the kept positions
+__device__ __forceinline__ void sg_tile_count(const uint8_t* flag, uint32_t n, uint32_t* tile) {
+  __shared__ uint32_t su[20];
+  const uint32_t t = blockIdx.x, i0 = t * SG_TILE + threadIdx.x * 4u;
+  uint32_t c = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) c += (i0 + k < n) ? flag[i0 + k] : 0u;
+  uint32_t tot;
+  block_excl_scan<uint32_t>(c, su, &tot);
+  if (threadIdx.x == 0) tile[t] = tot;
+}
+
+// in-place exclusive scan of tile[0..ntiles) (ntiles from the device when n_dev != null); total to *out
+__global__ __launch_bounds__(1024) void k_sg_scan(uint32_t* tile, uint32_t ntiles_max, const uint32_t* n_dev,
+                                                  uint32_t* out) {
+  __shared__ uint32_t scr[20];
+  const uint32_t ntiles = n_dev ? (*n_dev + SG_TILE - 1) / SG_TILE : ntiles_max;
+  uint32_t carry = 0;
+  for (uint32_t t0 = 0; t0 < ntiles; t0 += blockDim.x) {
+    const uint32_t t = t0 + threadIdx.x;
+    const uint32_t v = t < ntiles ? tile[t] : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_excl_scan<uint32_t>(v, scr, &tot);
+    if (t < ntiles) tile[t] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) *out = carry;
+}
+
+// out[pos] = map ? map[i] : i for every flagged i, in order; optional gather of float4 src[i] to dst[pos]
+__global__ __launch_bounds__(SG_THREADS) void k_sg_emit(const uint8_t* __restrict__ flag, uint32_t n_max,
+                                                        const uint32_t* n_dev, const uint32_t* __restrict__ tile,
+                                                        const uint32_t* __restrict__ map, uint32_t* __restrict__ out,
+                                                        const float4* __restrict__ src, float4* __restrict__ dst) {
+  __shared__ uint32_t su[20];
+  const uint32_t n = n_dev ? *n_dev : n_max;
+  const uint32_t t = blockIdx.x, i0 = t * SG_TILE + threadIdx.x * 4u;
+  if (t * SG_TILE >= n) return;  // (workgroup-uniform)
+  uint32_t f[4], c = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    f[k] = (i0 + k < n) ? flag[i0 + k] : 0u;
+    c += f[k];
+  }
+  uint32_t tot;
+  uint32_t pos = tile[t] + block_excl_scan<uint32_t>(c, su, &tot);
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (f[k]) {
+      const uint32_t i = i0 + k;
+      out[pos] = map ? map[i] : i;
+      if (dst) dst[pos] = src[i];
+      pos++;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// 1 + 2: transform (pft/common.hpp transformPointCloud: ((T0 x + T1 y) + T2 z) + T3, unfused) and removeZeroPoints
+// (create_model_planar_segmentation.cpp:59-77) on the transformed coordinates
+__global__ __launch_bounds__(SG_THREADS) void k_sg_zero(SgParams p, const pft_point_xyzrgba* __restrict__ in,
+                                                        float4* __restrict__ tx, uint8_t* __restrict__ flag,
+                                                        uint32_t* __restrict__ tile) {
+  const uint32_t i0 = blockIdx.x * SG_TILE + threadIdx.x * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t i = i0 + k;
+    if (i >= p.n) break;
+    const float4 q = *reinterpret_cast<const float4*>(in + i);
+    float x = q.x, y = q.y, z = q.z;
+    if (p.transform_enable) xform(p.T, q.x, q.y, q.z, x, y, z);
+    // RULE zero: dropped when all of |x|, |y|, |z| < 0.01 (float against double) or any coordinate is NaN
+    const bool zero = fabsf(x) < p.zero_thr && fabsf(y) < p.zero_thr && fabsf(z) < p.zero_thr;
+    const bool keep = !zero && !__builtin_isnan(x) && !__builtin_isnan(y) && !__builtin_isnan(z);
+    tx[i] = make_float4(x, y, z, 1.0f);
+    flag[i] = keep ? 1 : 0;
+  }
+  sg_tile_count(flag, p.n, tile);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// 3. RANSAC.  RULE rng: boost::uniform_int<>(0, INT_MAX) over boost::mt19937 reduces to engine() >> 1 (bucket size 2).
+#define MT_N 624
+#define MT_M 397
+__device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
+  y ^= y >> 11;
+  y ^= (y << 7) & 0x9d2c5680u;
+  y ^= (y << 15) & 0xefc60000u;
+  y ^= y >> 18;
+  return y;
+}
+__device__ __forceinline__ uint32_t mt_next_word(uint32_t a, uint32_t b, uint32_t c) {  // a = mt[i], b = mt[i+1], c = mt[i+M]
+  const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
+  return c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+}
+
+// the sequential twist in four dependency phases: [0,227) reads old words only, [227,454) reads the first phase's
+// output, [454,623) the second's, 623 reads mt[0] and mt[396]
+__device__ void mt_twist(uint32_t* mt) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lo[4] = {0, 227, 454, 623}, hi[4] = {227, 454, 623, 624};
+  for (int ph = 0; ph < 4; ph++) {
+    uint32_t v[2] = {0, 0};
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      const uint32_t i = lo[ph] + tid + r * SG_THREADS;
+      if (i < hi[ph]) v[r] = mt_next_word(mt[i], mt[(i + 1) % MT_N], mt[(i + MT_M) % MT_N]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+      const uint32_t i = lo[ph] + tid + r * SG_THREADS;
+      if (i < hi[ph]) mt[i] = v[r];
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ uint32_t map_slot(uint32_t key) { return (key * 2654435761u) >> (32 - 13); }
+__device__ __forceinline__ uint32_t map_get(const uint32_t* mk, const uint32_t* mv, uint32_t key) {
+  for (uint32_t s = map_slot(key);; s = (s + 1u) & (SG_MAPCAP - 1u)) {
+    if (mk[s] == key) return mv[s];
+    if (mk[s] == SG_EMPTY) return key;  // untouched position of shuffled_indices_ = its own index
+  }
+}
+__device__ __forceinline__ bool map_set(uint32_t* mk, uint32_t* mv, uint32_t* count, uint32_t key, uint32_t val) {
+  for (uint32_t s = map_slot(key);; s = (s + 1u) & (SG_MAPCAP - 1u)) {
+    if (mk[s] == key) {
+      mv[s] = val;
+      return true;
+    }
+    if (mk[s] == SG_EMPTY) {
+      if (*count >= SG_MAPMAX) return false;
+      mk[s] = key;
+      mv[s] = val;
+      (*count)++;
+      return true;
+    }
+  }
+}
+
+// RULE good: isSampleGood -- dy1dy2 = (p1 - p0) / (p2 - p0); good iff dy1dy2[0] != dy1dy2[1] || dy1dy2[2] != dy1dy2[1]
+__device__ __forceinline__ bool sample_good(float4 a, float4 b, float4 c) {
+  const float r0 = (b.x - a.x) / (c.x - a.x), r1 = (b.y - a.y) / (c.y - a.y), r2 = (b.z - a.z) / (c.z - a.z);
+  return r0 != r1 || r2 != r1;
+}
+
+// RULE coef: computeModelCoefficients -- cross product as PCL writes it, normalize() = divide by sqrt of the squared
+// norm ((a0^2 + a1^2) + (a2^2 + 0^2), the 4-lane reduction), then d = -((c0 x + c1 y) + (c2 z + 0 * 1))
+__device__ __forceinline__ float4 plane_of(float4 p0, float4 p1, float4 p2) {
+  const float ax = p1.x - p0.x, ay = p1.y - p0.y, az = p1.z - p0.z;
+  const float bx = p2.x - p0.x, by = p2.y - p0.y, bz = p2.z - p0.z;
+  float c0 = ay * bz - az * by;
+  float c1 = az * bx - ax * bz;
+  float c2 = ax * by - ay * bx;
+  const float sq = (c0 * c0 + c1 * c1) + (c2 * c2 + 0.0f * 0.0f);
+  const float nrm = sqrtf(sq);
+  c0 = c0 / nrm;
+  c1 = c1 / nrm;
+  c2 = c2 / nrm;
+  const float c3 = 0.0f / nrm;
+  const float dot = (c0 * p0.x + c1 * p0.y) + (c2 * p0.z + c3 * 1.0f);
+  return make_float4(c0, c1, c2, -1.0f * dot);
+}
+
+// RULE dist: |c . (x, y, z, 1)| with the 4-lane reduction (a0 + a1) + (a2 + a3), compared strictly (float vs double)
+__device__ __forceinline__ bool within(float4 c, float4 q, float thr) {
+  const float d = (c.x * q.x + c.y * q.y) + (c.z * q.z + c.w * 1.0f);
+  return fabsf(d) < thr;
+}
+
+struct SgSampler {
+  uint32_t* mt;      // [624]
+  uint32_t* mk;      // [SG_MAPCAP]
+  uint32_t* mv;      // [SG_MAPCAP]
+};
+
+// one workgroup: the samples of batch b (hypotheses b*SG_BATCH ..), in draw order
+__global__ __launch_bounds__(SG_THREADS) void k_sg_sample(SgParams p, SgHdr* __restrict__ h, SgSampler st, SgHyp hy,
+                                                          const float4* __restrict__ pts, uint32_t b) {
+  __shared__ uint32_t smt[MT_N];
+  __shared__ uint32_t sout[MT_N];
+  __shared__ uint32_t mk[SG_MAPCAP];
+  __shared__ uint32_t mv[SG_MAPCAP];
+  __shared__ uint32_t s_pos, s_done, s_count;
+  const uint32_t tid = threadIdx.x;
+  if (h->decided) return;  // (uniform) an earlier batch ended the loop
+  const uint32_t n = h->n_valid;
+  if (b == 0) {
+    for (uint32_t k = tid; k < SG_MAPCAP; k += SG_THREADS) mk[k] = SG_EMPTY;
+    if (tid == 0) {  // std::mt19937 / boost::mt19937 seed(s)
+      uint32_t x = p.seed;
+      smt[0] = x;
+      for (uint32_t i = 1; i < MT_N; i++) {
+        x = 1812433253u * (x ^ (x >> 30)) + i;
+        smt[i] = x;
+      }
+      s_pos = MT_N;
+      s_count = 0;
+    }
+  } else {
+    for (uint32_t k = tid; k < SG_MAPCAP; k += SG_THREADS) {
+      mk[k] = st.mk[k];
+      mv[k] = st.mv[k];
+    }
+    for (uint32_t k = tid; k < MT_N; k += SG_THREADS) smt[k] = st.mt[k];
+    if (tid == 0) {
+      s_pos = h->mt_pos;
+      s_count = h->map_count;
+    }
+  }
+  if (tid == 0) s_done = 0;
+  __syncthreads();
+  for (uint32_t k = tid; k < MT_N; k += SG_THREADS) sout[k] = mt_temper(smt[k]);
+  __syncthreads();
+  // lane 0 keeps the draw state in registers across refills: position i in drawIndexSample, failed draws so far
+  uint32_t hcur = b * SG_BATCH, hend = hcur + SG_BATCH, di = 0, fails = 0;
+  uint32_t cnt = s_count;
+  for (;;) {
+    if (tid == 0) {
+      uint32_t pos = s_pos;
+      bool stop = false;
+      if (n < 3) {  // getSamples: fewer indices than the sample size -> no sample
+        hy.sample[3 * hcur] = (int32_t)SG_EMPTY;
+        stop = true;
+      }
+      while (!stop && pos < MT_N) {
+        // RULE draw: swap(shuffled[i], shuffled[i + rnd() % (n - i)]), shuffled never reset between samples
+        const uint32_t r = sout[pos++] >> 1;
+        const uint32_t j = di + r % (n - di);
+        const uint32_t a = map_get(mk, mv, di), c = map_get(mk, mv, j);
+        if (!map_set(mk, mv, &cnt, di, c) || !map_set(mk, mv, &cnt, j, a)) {
+          // only an error if the RANSAC loop gets as far as this sample (k_sg_replay)
+          hy.sample[3 * hcur] = (int32_t)SG_OVERFLOW;
+          stop = true;
+          break;
+        }
+        if (++di < 3) continue;
+        di = 0;
+        const uint32_t s0 = map_get(mk, mv, 0), s1 = map_get(mk, mv, 1), s2 = map_get(mk, mv, 2);
+        const float4 q0 = pts[s0], q1 = pts[s1], q2 = pts[s2];
+        if (sample_good(q0, q1, q2)) {
+          hy.sample[3 * hcur] = (int32_t)s0;
+          hy.sample[3 * hcur + 1] = (int32_t)s1;
+          hy.sample[3 * hcur + 2] = (int32_t)s2;
+          hy.coef[hcur] = plane_of(q0, q1, q2);
+          hcur++;
+          fails = 0;
+          if (hcur == hend) {
+            stop = true;
+            break;
+          }
+        } else if (++fails == SG_SAMPLE_CHECKS) {  // RULE checks: 1000 failed draws -> empty sample, loop breaks
+          hy.sample[3 * hcur] = (int32_t)SG_EMPTY;
+          stop = true;
+          break;
+        }
+      }
+      s_pos = pos;
+      s_done = stop ? 1u : 0u;
+      s_count = cnt;
+    }
+    __syncthreads();
+    if (s_done) break;
+    mt_twist(smt);  // all 624 tempered words consumed
+    for (uint32_t k = tid; k < MT_N; k += SG_THREADS) sout[k] = mt_temper(smt[k]);
+    if (tid == 0) s_pos = 0;
+    __syncthreads();
+  }
+  // state for the next batch
+  for (uint32_t k = tid; k < SG_MAPCAP; k += SG_THREADS) {
+    st.mk[k] = mk[k];
+    st.mv[k] = mv[k];
+  }
+  for (uint32_t k = tid; k < MT_N; k += SG_THREADS) st.mt[k] = smt[k];
+  if (tid == 0) {
+    h->mt_pos = s_pos;
+    h->map_count = s_count;
+    h->emitted = (b + 1u) * SG_BATCH;  // hypotheses this and the earlier batches drew and scored
+  }
+}
+
+// counts of the batch's hypotheses over all points: SG_SCORE_PTS points per thread, planes from LDS, ballot counts
+__global__ __launch_bounds__(SG_THREADS) void k_sg_score(SgParams p, const SgHdr* __restrict__ h, SgHyp hy,
+                                                         const float4* __restrict__ pts, uint32_t b) {
+  __shared__ float4 sc[SG_BATCH];
+  __shared__ uint32_t scnt[SG_BATCH];
+  if (h->decided) return;
+  const uint32_t n = h->n_valid;
+  const uint32_t base = blockIdx.x * (SG_THREADS * SG_SCORE_PTS);
+  if (base >= n) return;  // (uniform)
+  const uint32_t tid = threadIdx.x, h0 = b * SG_BATCH;
+  if (tid < SG_BATCH) {
+    const bool ok = (uint32_t)hy.sample[3 * (h0 + tid)] < SG_OVERFLOW;
+    sc[tid] = ok ? hy.coef[h0 + tid] : make_float4(NAN, NAN, NAN, NAN);
+    scnt[tid] = 0;
+  }
+  float4 q[SG_SCORE_PTS];
+#pragma unroll
+  for (uint32_t k = 0; k < SG_SCORE_PTS; k++) {
+    const uint32_t i = base + k * SG_THREADS + tid;
+    q[k] = i < n ? pts[i] : make_float4(NAN, NAN, NAN, NAN);
+  }
+  __syncthreads();
+  for (uint32_t j = 0; j < SG_BATCH; j++) {
+    const float4 c = sc[j];
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < SG_SCORE_PTS; k++) cnt += (uint32_t)__popcll(__ballot(within(c, q[k], p.dist_thr)));
+    if (lane_id() == 0 && cnt) atomicAdd(&scnt[j], cnt);
+  }
+  __syncthreads();
+  if (tid < SG_BATCH && scnt[tid]) atomicAdd(&hy.count[h0 + tid], scnt[tid]);
+}
+
+// RULE loop: RandomSampleConsensus::computeModel over the batch, one lane, double precision as upstream
+__global__ __launch_bounds__(64) void k_sg_replay(SgParams p, SgHdr* __restrict__ h, SgHyp hy, uint32_t b) {
+  if (threadIdx.x != 0 || h->decided) return;
+  const uint32_t n = h->n_valid;
+  const double one_over_indices = 1.0 / (double)n;
+  double k = h->k;
+  int32_t best = h->best_count, best_h = h->best_h;
+  uint32_t it = h->iterations;
+  bool decided = false;
+  for (uint32_t hh = b * SG_BATCH; hh < (b + 1) * SG_BATCH; hh++) {
+    if (!((double)it < k)) {  // while (iterations_ < k && skipped_count < max_skip)
+      decided = true;
+      break;
+    }
+    if ((uint32_t)hy.sample[3 * hh] == SG_OVERFLOW) {  // the sample the loop needs next was never drawn
+      h->err |= SG_ERR_MAP;
+      decided = true;
+      break;
+    }
+    if (hy.sample[3 * hh] == (int32_t)SG_EMPTY) {  // "No samples could be selected!"
+      decided = true;
+      break;
+    }
+    const int32_t c = (int32_t)hy.count[hh];
+    if (c > best) {
+      best = c;
+      best_h = (int32_t)hh;
+      const double w = (double)best * one_over_indices;
+      double p_no_outliers = 1.0 - pow(w, 3.0);
+      p_no_outliers = fmax(DBL_EPSILON, p_no_outliers);
+      p_no_outliers = fmin(1.0 - DBL_EPSILON, p_no_outliers);
+      k = p.log_probability / log(p_no_outliers);
+    }
+    ++it;
+    if ((int)it > p.max_iterations) {  // "RANSAC reached the maximum number of trials."
+      decided = true;
+      break;
+    }
+  }
+  h->k = k;
+  h->best_count = best;
+  h->best_h = best_h;
+  h->iterations = it;
+  if (decided) {
+    h->decided = 1;
+    if (best_h >= 0) {
+      const float4 c = hy.coef[best_h];
+      h->coef_ransac[0] = c.x;
+      h->coef_ransac[1] = c.y;
+      h->coef_ransac[2] = c.z;
+      h->coef_ransac[3] = c.w;
+    }
+  }
+}
+
+// flags of the points within the distance of a plane (coef from the header: 0 = best hypothesis, 1 = final);
+// with box: also the survivor flags (not an inlier, inside the box)
+__global__ __launch_bounds__(SG_THREADS) void k_sg_select(SgParams p, const SgHdr* __restrict__ h, int which,
+                                                          const float4* __restrict__ pts, uint8_t* __restrict__ flag,
+                                                          uint32_t* __restrict__ tile, uint8_t* __restrict__ sflag,
+                                                          uint32_t* __restrict__ stile) {
+  const uint32_t n = h->n_valid;
+  if (blockIdx.x * SG_TILE >= n) return;  // (uniform)
+  const bool have = h->best_h >= 0;
+  const float* cf = which ? h->coef_final : h->coef_ransac;
+  const float4 c = make_float4(cf[0], cf[1], cf[2], cf[3]);
+  const uint32_t i0 = blockIdx.x * SG_TILE + threadIdx.x * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t i = i0 + k;
+    if (i >= n) break;
+    const float4 q = pts[i];
+    const bool in = have && within(c, q, p.dist_thr);
+    flag[i] = in ? 1 : 0;
+    if (sflag) {
+      // RULE box: PassThrough per enabled axis, inclusive float limits; the chain is the AND of the ranges
+      bool keep = !in;
+      const float v[3] = {q.x, q.y, q.z};
+#pragma unroll
+      for (int a = 0; a < 3; a++)
+        if (p.box_enable[a] && (v[a] < p.box_min[a] || v[a] > p.box_max[a])) keep = false;
+      sflag[i] = keep ? 1 : 0;
+    }
+  }
+  sg_tile_count(flag, n, tile);
+  if (sflag) sg_tile_count(sflag, n, stile);
+}
+
+// RULE eigen: pcl::computeRoots / computeRoots2 / eigen33 (smallest eigenvalue's vector) in float
+__device__ void sg_roots2(float b, float c, float* r) {
+  r[0] = 0.0f;
+  float d = (float)((double)(b * b) - 4.0 * (double)c);
+  if (d < 0.0f) d = 0.0f;
+  const float sd = sqrtf(d);
+  r[2] = 0.5f * (b + sd);
+  r[1] = 0.5f * (b - sd);
+}
+__device__ void sg_roots(const float* m, float* r) {  // m row-major 3x3
+  const float m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[4], m12 = m[5], m22 = m[8];
+  const float c0 = m00 * m11 * m22 + 2.0f * m01 * m02 * m12 - m00 * m12 * m12 - m11 * m02 * m02 - m22 * m01 * m01;
+  const float c1 = m00 * m11 - m01 * m01 + m00 * m22 - m02 * m02 + m11 * m22 - m12 * m12;
+  const float c2 = m00 + m11 + m22;
+  if (fabsf(c0) < FLT_EPSILON) {
+    sg_roots2(c2, c1, r);
+    return;
+  }
+  const float s_inv3 = (float)(1.0 / 3.0);
+  const float s_sqrt3 = sqrtf(3.0f);
+  const float c2_over_3 = c2 * s_inv3;
+  float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
+  if (a_over_3 > 0.0f) a_over_3 = 0.0f;
+  const float half_b = 0.5f * (c0 + c2_over_3 * (2.0f * c2_over_3 * c2_over_3 - c1));
+  float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
+  if (q > 0.0f) q = 0.0f;
+  const float rho = sqrtf(-a_over_3);
+  const float theta = atan2f(sqrtf(-q), half_b) * s_inv3;
+  const float ct = cosf(theta), st = sinf(theta);
+  r[0] = c2_over_3 + 2.0f * rho * ct;
+  r[1] = c2_over_3 - rho * (ct + s_sqrt3 * st);
+  r[2] = c2_over_3 - rho * (ct - s_sqrt3 * st);
+  float t;
+  if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
+  if (r[1] >= r[2]) {
+    t = r[1]; r[1] = r[2]; r[2] = t;
+    if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
+  }
+  if (r[0] <= 0.0f) sg_roots2(c2, c1, r);
+}
+__device__ void sg_eigen33(const float* mat, float* vec) {
+  float scale = 0.0f;
+  for (int k = 0; k < 9; k++) scale = fmaxf(scale, fabsf(mat[k]));
+  if (scale <= FLT_MIN) scale = 1.0f;
+  float m[9];
+  for (int k = 0; k < 9; k++) m[k] = mat[k] / scale;
+  float r[3];
+  sg_roots(m, r);
+  m[0] -= r[0];
+  m[4] -= r[0];
+  m[8] -= r[0];
+  float v[3][3];
+  const int ra[3] = {0, 0, 1}, rb[3] = {1, 2, 2};
+  float len[3];
+  for (int k = 0; k < 3; k++) {
+    const float* a = m + 3 * ra[k];
+    const float* b = m + 3 * rb[k];
+    v[k][0] = a[1] * b[2] - a[2] * b[1];
+    v[k][1] = a[2] * b[0] - a[0] * b[2];
+    v[k][2] = a[0] * b[1] - a[1] * b[0];
+    len[k] = v[k][0] * v[k][0] + (v[k][1] * v[k][1] + v[k][2] * v[k][2]);  // Vector3f::squaredNorm
+  }
+  int pick = 2;
+  if (len[0] >= len[1] && len[0] >= len[2]) pick = 0;
+  else if (len[1] >= len[0] && len[1] >= len[2]) pick = 1;
+  const float s = sqrtf(len[pick]);
+  vec[0] = v[pick][0] / s;
+  vec[1] = v[pick][1] / s;
+  vec[2] = v[pick][2] / s;
+}
+
+// RULE refit: optimizeModelCoefficients -- nine float accumulators summed in inlier index order, divided by the
+// count, covariance accu[i] - mean * mean, eigen33, d = -((e0 c0 + e1 c1) + (e2 c2 + 0 * 1)).  Fewer than 4 inliers:
+// the coefficients stay.  One workgroup: the points are staged in LDS, nine lanes of wave 0 run the dependent adds.
+#define SG_REFIT_THREADS 1024u
+#define SG_REFIT_STAGE 4096u
+__global__ __launch_bounds__(SG_REFIT_THREADS) void k_sg_refit(SgParams p, SgHdr* __restrict__ h, int optimize,
+                                                              const float4* __restrict__ pts,
+                                                              const uint32_t* __restrict__ inl) {
+  __shared__ float4 stage[SG_REFIT_STAGE];
+  __shared__ float accu[9];
+  const uint32_t tid = threadIdx.x, m = h->n_ransac_inl;
+  const bool have = h->best_h >= 0;
+  if (!have) return;  // (uniform)
+  if (!optimize || m < 4) {
+    if (tid < 4) h->coef_final[tid] = h->coef_ransac[tid];
+    return;
+  }
+  // lane t: accu[t] += a * b with (a, b) = (x,x) (x,y) (x,z) (y,y) (y,z) (z,z), then (x,w) (y,w) (z,w): w = 1.0f, so
+  // the product is the coordinate itself, exactly
+  const int ia[9] = {0, 0, 0, 1, 1, 2, 0, 1, 2}, ib[9] = {0, 1, 2, 1, 2, 2, 3, 3, 3};
+  const int my_a = tid < 9 ? ia[tid] : 0, my_b = tid < 9 ? ib[tid] : 3;
+  const float* sf = reinterpret_cast<const float*>(stage);
+  float acc = 0.0f;
+  for (uint32_t s0 = 0; s0 < m; s0 += SG_REFIT_STAGE) {
+    const uint32_t cnt = min(SG_REFIT_STAGE, m - s0);
+    for (uint32_t k = tid; k < cnt; k += SG_REFIT_THREADS) stage[k] = pts[inl[s0 + k]];
+    __syncthreads();
+    if (tid < 9) {
+#pragma unroll 8
+      for (uint32_t k = 0; k < cnt; k++) acc += sf[4 * k + my_a] * sf[4 * k + my_b];
+    }
+    __syncthreads();
+  }
+  if (tid < 9) accu[tid] = acc / (float)m;
+  __syncthreads();
+  if (tid == 0) {
+    float cov[9];
+    cov[0] = accu[0] - accu[6] * accu[6];
+    cov[1] = accu[1] - accu[6] * accu[7];
+    cov[2] = accu[2] - accu[6] * accu[8];
+    cov[4] = accu[3] - accu[7] * accu[7];
+    cov[5] = accu[4] - accu[7] * accu[8];
+    cov[8] = accu[5] - accu[8] * accu[8];
+    cov[3] = cov[1];
+    cov[6] = cov[2];
+    cov[7] = cov[5];
+    float e[3];
+    sg_eigen33(cov, e);
+    const float dot = (e[0] * accu[6] + e[1] * accu[7]) + (e[2] * accu[8] + 0.0f * 1.0f);
+    h->coef_final[0] = e[0];
+    h->coef_final[1] = e[1];
+    h->coef_final[2] = e[2];
+    h->coef_final[3] = -1.0f * dot;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// 6. clustering over the survivors (m points, spts[j] in survivor order = ascending input index)
+__global__ __launch_bounds__(SG_THREADS) void k_sg_bounds(const SgHdr* __restrict__ h, const float4* __restrict__ spts,
+                                                          float* __restrict__ part) {
+  __shared__ float sf[6][20];
+  const uint32_t m = h->n_surv;
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t i = blockIdx.x * SG_THREADS + threadIdx.x; i < m; i += gridDim.x * SG_THREADS) {
+    const float4 q = spts[i];
+    mn[0] = fminf(mn[0], q.x); mn[1] = fminf(mn[1], q.y); mn[2] = fminf(mn[2], q.z);
+    mx[0] = fmaxf(mx[0], q.x); mx[1] = fmaxf(mx[1], q.y); mx[2] = fmaxf(mx[2], q.z);
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float lo = block_reduce<float>(mn[a], sf[a], OpMinF(), INFINITY);
+    const float hi = block_reduce<float>(mx[a], sf[3 + a], OpMaxF(), -INFINITY);
+    if (threadIdx.x == 0) {
+      part[blockIdx.x * 6 + a] = lo;
+      part[blockIdx.x * 6 + 3 + a] = hi;
+    }
+  }
+}
+__global__ __launch_bounds__(SG_THREADS) void k_sg_bounds2(SgHdr* __restrict__ h, const float* __restrict__ part,
+                                                           uint32_t nparts) {
+  __shared__ float sf[6][20];
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (uint32_t t = threadIdx.x; t < nparts; t += SG_THREADS)
+    for (int a = 0; a < 3; a++) {
+      mn[a] = fminf(mn[a], part[t * 6 + a]);
+      mx[a] = fmaxf(mx[a], part[t * 6 + 3 + a]);
+    }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    mn[a] = block_reduce<float>(mn[a], sf[a], OpMinF(), INFINITY);
+    mx[a] = block_reduce<float>(mx[a], sf[3 + a], OpMaxF(), -INFINITY);
+  }
+  if (threadIdx.x == 0)
+    for (int a = 0; a < 3; a++) {
+      h->bmin[a] = mn[a];
+      h->bmax[a] = mx[a];
+    }
+}
+
+// Cell side s = tol / 2 * (1 + 2^-5).  Inside a cell the diagonal is sqrt(3) s = 0.893 tol < tol, so every point of a
+// cell joins the cell's first point.  Two points within tol of each other differ by less than 2 / (1 + 2^-5) = 1.939 in
+// exact scaled coordinates; the two roundings of (v - lo) * inv add at most 2^-22 U (U the largest scaled coordinate,
+// at most 2^17 per axis, checked on the host) = 0.031, so the computed difference stays below 2 and the pair is at most
+// 2 cells apart on every axis: the 5 x 5 x 5 block holds every neighbour.
+__device__ __forceinline__ uint32_t cell_coord(float v, float lo, float inv, uint32_t nmax) {
+  const float f = floorf((v - lo) * inv);
+  if (!(f > 0.0f)) return 0u;
+  const uint32_t c = (uint32_t)fminf(f, (float)(nmax - 1u));
+  return c < nmax ? c : nmax - 1u;
+}
+
+// cell key of every survivor (cell side tol / 2), value = survivor index
+__global__ __launch_bounds__(SG_THREADS) void k_sg_cellkey(SgParams p, const SgHdr* __restrict__ h,
+                                                           const float4* __restrict__ spts, uint32_t* __restrict__ key,
+                                                           uint32_t* __restrict__ val, uint32_t m) {
+  const uint32_t i = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (i >= m) return;
+  const float4 q = spts[i];
+  const uint32_t ix = cell_coord(q.x, h->bmin[0], p.inv_cell, p.nx);
+  const uint32_t iy = cell_coord(q.y, h->bmin[1], p.inv_cell, p.ny);
+  const uint32_t iz = cell_coord(q.z, h->bmin[2], p.inv_cell, p.nz);
+  key[i] = ix + p.nx * (iy + p.ny * iz);
+  val[i] = i;
+}
+
+// run heads of the sorted keys, per tile; then (k_sg_cells) cell ids, cell starts, the sorted points and the
+// within-cell forest: every point hangs under its cell's first (= smallest) survivor index
+__global__ __launch_bounds__(SG_THREADS) void k_sg_heads(const uint32_t* __restrict__ skey, uint32_t m,
+                                                         uint8_t* __restrict__ head, uint32_t* __restrict__ tile) {
+  const uint32_t i0 = blockIdx.x * SG_TILE + threadIdx.x * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t j = i0 + k;
+    if (j < m) head[j] = (j == 0 || skey[j - 1] != skey[j]) ? 1 : 0;
+  }
+  __syncthreads();
+  sg_tile_count(head, m, tile);
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sg_cells(const uint32_t* __restrict__ skey,
+                                                         const uint32_t* __restrict__ sval, uint32_t m,
+                                                         const uint8_t* __restrict__ head,
+                                                         const uint32_t* __restrict__ tile,
+                                                         uint32_t* __restrict__ cell_start, uint32_t* __restrict__ cell_key,
+                                                         const float4* __restrict__ spts, float4* __restrict__ sorted,
+                                                         uint32_t* __restrict__ cell_of) {
+  __shared__ uint32_t su[20];
+  const uint32_t t = blockIdx.x, i0 = t * SG_TILE + threadIdx.x * 4u;
+  uint32_t f[4], c = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    f[k] = (i0 + k < m) ? head[i0 + k] : 0u;
+    c += f[k];
+  }
+  uint32_t tot;
+  uint32_t run = tile[t] + block_excl_scan<uint32_t>(c, su, &tot);  // heads before i0
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t j = i0 + k;
+    if (j >= m) break;
+    if (f[k]) {
+      cell_start[run] = j;
+      cell_key[run] = skey[j];
+      run++;
+    }
+    cell_of[j] = run - 1u;
+    sorted[j] = spts[sval[j]];
+  }
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sg_forest(const uint32_t* __restrict__ sval, uint32_t m,
+                                                          const uint32_t* __restrict__ cell_of,
+                                                          const uint32_t* __restrict__ cell_start,
+                                                          uint32_t* __restrict__ parent) {
+  const uint32_t j = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (j >= m) return;
+  parent[sval[j]] = sval[cell_start[cell_of[j]]];
+}
+
+__device__ __forceinline__ uint32_t uf_load(const uint32_t* a) {
+  return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// parent[x] <= x everywhere; a root is its component's smallest survivor index
+__device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x) {
+  uint32_t p = uf_load(parent + x);
+  while (p != x) {
+    const uint32_t g = uf_load(parent + p);
+    if (g != p) atomicMin(parent + x, g);  // path halving: any ancestor is a valid parent
+    x = p;
+    p = g;
+  }
+  return x;
+}
+__device__ __forceinline__ void uf_union(uint32_t* parent, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    if (a == b) return;
+    if (a > b) {
+      const uint32_t t = a;
+      a = b;
+      b = t;
+    }
+    const uint32_t old = atomicCAS(parent + b, b, a);  // hook the larger root under the smaller
+    if (old == b) return;
+    b = old;
+  }
+}
+
+// RULE link: two points are connected iff ((dx^2 + dy^2) + dz^2) < (float)(tol^2).  Work item = (cell, one of the 62
+// neighbour offsets of the 5x5x5 block that come after it): the pair is tested until one pair of points connects.
+__global__ __launch_bounds__(SG_THREADS) void k_sg_link(SgParams p, const SgHdr* __restrict__ h,
+                                                        const uint32_t* __restrict__ cell_start,
+                                                        const uint32_t* __restrict__ cell_key,
+                                                        const uint32_t* __restrict__ sval,
+                                                        const float4* __restrict__ sorted, uint32_t m,
+                                                        uint32_t* __restrict__ parent) {
+  const uint32_t nc = h->n_cells;
+  const uint64_t total = (uint64_t)nc * 62u;
+  for (uint64_t w = (uint64_t)blockIdx.x * SG_THREADS + threadIdx.x; w < total; w += (uint64_t)gridDim.x * SG_THREADS) {
+    const uint32_t c = (uint32_t)(w / 62u), L = 63u + (uint32_t)(w % 62u);
+    const int dz = (int)(L / 25u) - 2, dy = (int)((L / 5u) % 5u) - 2, dx = (int)(L % 5u) - 2;
+    const uint32_t key = cell_key[c];
+    const int ix = (int)(key % p.nx), iy = (int)((key / p.nx) % p.ny), iz = (int)(key / p.nx / p.ny);
+    const int jx = ix + dx, jy = iy + dy, jz = iz + dz;
+    if (jx < 0 || jy < 0 || jz < 0 || jx >= (int)p.nx || jy >= (int)p.ny || jz >= (int)p.nz) continue;
+    const uint32_t key2 = (uint32_t)jx + p.nx * ((uint32_t)jy + p.ny * (uint32_t)jz);
+    uint32_t lo = c + 1u, hi = nc;  // key2 > key: search the cells after c
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (cell_key[mid] < key2) lo = mid + 1u; else hi = mid;
+    }
+    if (lo >= nc || cell_key[lo] != key2) continue;
+    const uint32_t c2 = lo;
+    const uint32_t a0 = cell_start[c], a1 = c + 1u < nc ? cell_start[c + 1u] : m;
+    const uint32_t b0 = cell_start[c2], b1 = c2 + 1u < nc ? cell_start[c2 + 1u] : m;
+    const uint32_t fa = sval[a0], fb = sval[b0];
+    if (uf_find(parent, fa) == uf_find(parent, fb)) continue;
+    bool linked = false;
+    for (uint32_t a = a0; a < a1 && !linked; a++) {
+      const float4 qa = sorted[a];
+      for (uint32_t b = b0; b < b1; b++) {
+        const float4 qb = sorted[b];
+        const float ddx = qa.x - qb.x, ddy = qa.y - qb.y, ddz = qa.z - qb.z;
+        if ((ddx * ddx + ddy * ddy) + ddz * ddz < p.tol2) {
+          linked = true;
+          break;
+        }
+      }
+    }
+    if (linked) uf_union(parent, fa, fb);
+  }
+}
+
+// final labels (root = smallest survivor index of the component) and component sizes
+__global__ __launch_bounds__(SG_THREADS) void k_sg_label(uint32_t m, uint32_t* __restrict__ parent,
+                                                         uint32_t* __restrict__ label, uint32_t* __restrict__ csize) {
+  const uint32_t j = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t r = uf_find(parent, j);
+  label[j] = r;
+  atomicAdd(&csize[r], 1u);
+}
+
+// RULE size: a component is kept iff min <= size <= max; flags of the kept roots
+__global__ __launch_bounds__(SG_THREADS) void k_sg_roots(SgParams p, uint32_t m, const uint32_t* __restrict__ label,
+                                                         const uint32_t* __restrict__ csize, uint8_t* __restrict__ flag,
+                                                         uint32_t* __restrict__ tile) {
+  const uint32_t i0 = blockIdx.x * SG_TILE + threadIdx.x * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t j = i0 + k;
+    if (j < m) flag[j] = (label[j] == j && csize[j] >= p.min_size && csize[j] <= p.max_size) ? 1 : 0;
+  }
+  __syncthreads();
+  sg_tile_count(flag, m, tile);
+}
+
+// RULE order: clusters by size descending, ties by smallest index ascending -- key max_size - size, stable sort of
+// the roots (which are in ascending order)
+__global__ __launch_bounds__(SG_THREADS) void k_sg_order_keys(SgParams p, uint32_t nc, const uint32_t* __restrict__ roots,
+                                                              const uint32_t* __restrict__ csize,
+                                                              uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+  const uint32_t r = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (r >= nc) return;
+  key[r] = p.max_size - csize[roots[r]];
+  val[r] = roots[r];
+}
+
+// cluster rank of every root, the sizes in cluster order
+__global__ __launch_bounds__(SG_THREADS) void k_sg_rank(uint32_t nc, const uint32_t* __restrict__ oroot,
+                                                        const uint32_t* __restrict__ csize, uint32_t* __restrict__ crank,
+                                                        uint32_t* __restrict__ sizes) {
+  const uint32_t r = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (r >= nc) return;
+  crank[oroot[r]] = r;
+  sizes[r] = csize[oroot[r]];
+}
+
+// sort key of every survivor: its cluster's rank, nc for the dropped ones
+__global__ __launch_bounds__(SG_THREADS) void k_sg_member_keys(uint32_t m, uint32_t nc, const uint32_t* __restrict__ label,
+                                                               const uint32_t* __restrict__ crank,
+                                                               uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+  const uint32_t j = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t r = crank[label[j]];
+  key[j] = r < nc ? r : nc;
+  val[j] = j;
+}
+
+__global__ __launch_bounds__(SG_THREADS) void k_sg_output(uint32_t total, const uint32_t* __restrict__ sval,
+                                                          const uint32_t* __restrict__ surv_in,
+                                                          const pft_point_xyzrgba* __restrict__ in,
+                                                          int32_t* __restrict__ out_idx,
+                                                          pft_point_xyzrgba* __restrict__ out_pts) {
+  const uint32_t q = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (q >= total) return;
+  const uint32_t i = surv_in[sval[q]];
+  out_idx[q] = (int32_t)i;
+  const float4* s = reinterpret_cast<const float4*>(in + i);
+  float4* o = reinterpret_cast<float4*>(out_pts + q);
+  o[0] = s[0];
+  o[1] = s[1];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+#define SCHK(s, call)                                                \
+  do {                                                               \
+    hipError_t e_ = (call);                                          \
+    if (e_ != hipSuccess) {                                          \
+      (s)->err = std::string(#call) + ": " + hipGetErrorString(e_);  \
+      return PFT_ERR_HIP;                                            \
+    }                                                                \
+  } while (0)
+
+#define SG_NEV 96
+
+struct SgBufs {
+  pft_point_xyzrgba* in_own;
+  float4* tx;        // transformed, input order
+  uint8_t* flag;     // removeZero / inlier flags
+  uint8_t* flag2;    // survivor flags
+  uint32_t* tile;
+  uint32_t* tile2;
+  uint32_t* comp_idx;   // compacted -> input index
+  float4* comp_pts;     // compacted transformed points
+  uint32_t* inl_idx;    // best-hypothesis inliers (compacted indices)
+  uint32_t* fin_idx;    // final inliers (input indices)
+  uint32_t* surv_in;    // survivor -> input index
+  float4* spts;         // survivor points (transformed)
+  uint32_t* key[2];
+  uint32_t* val[2];
+  uint32_t* hist;
+  float4* sorted;
+  uint32_t* cell_start;
+  uint32_t* cell_key;
+  uint32_t* cell_of;
+  uint32_t* parent;
+  uint32_t* label;
+  uint32_t* csize;
+  uint32_t* roots;
+  uint32_t* crank;
+  uint32_t* sizes;
+  float* bpart;
+  int32_t* out_idx;
+  pft_point_xyzrgba* out_pts;
+};
+
+struct pft_segment {
+  pft_segment_config cfg;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  std::string err;
+  size_t cap = 0;
+  SgBufs b = {};
+  SgHdr* hdr = nullptr;
+  SgHdr* host_hdr = nullptr;  // pinned copy
+  SgSampler smp = {};
+  SgHyp hyp = {};
+  uint32_t hmax = 0;
+  hipEvent_t ev[SG_NEV] = {};
+  int ev_stage[SG_NEV] = {};
+  int nev = 0;
+  // results of the last apply
+  bool have_result = false;
+  SgHdr res = {};
+  size_t n_in = 0;
+  std::vector<uint32_t> sizes;
+  double last_ms = 0.0, stage_ms[PFT_SEGMENT_STAGES] = {};
+};
+
+template <typename T>
+static hipError_t salloc(T** p, size_t n) {
+  return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
+}
+template <typename T>
+static void sfree(T*& p) {
+  if (p) hipFree((void*)p);
+  p = nullptr;
+}
+
+static void free_buffers(pft_segment* s) {
+  SgBufs& b = s->b;
+  sfree(b.in_own); sfree(b.tx); sfree(b.flag); sfree(b.flag2); sfree(b.tile); sfree(b.tile2); sfree(b.comp_idx);
+  sfree(b.comp_pts); sfree(b.inl_idx); sfree(b.fin_idx); sfree(b.surv_in); sfree(b.spts);
+  for (int k = 0; k < 2; k++) {
+    sfree(b.key[k]);
+    sfree(b.val[k]);
+  }
+  sfree(b.hist); sfree(b.sorted); sfree(b.cell_start); sfree(b.cell_key); sfree(b.cell_of); sfree(b.parent);
+  sfree(b.label); sfree(b.csize); sfree(b.roots); sfree(b.crank); sfree(b.sizes); sfree(b.bpart); sfree(b.out_idx);
+  sfree(b.out_pts);
+  s->cap = 0;
+}
+
+static int ensure_capacity(pft_segment* s, size_t n) {
+  if (n <= s->cap) return PFT_OK;
+  if (s->stream) SCHK(s, hipStreamSynchronize(s->stream));
+  free_buffers(s);
+  size_t cap = n < SG_TILE ? SG_TILE : n;
+  cap = (cap + SG_TILE - 1) / SG_TILE * SG_TILE;
+  const size_t nt = cap / SG_TILE;
+  SgBufs& b = s->b;
+  SCHK(s, salloc(&b.in_own, cap));
+  SCHK(s, salloc(&b.tx, cap));
+  SCHK(s, salloc(&b.flag, cap));
+  SCHK(s, salloc(&b.flag2, cap));
+  SCHK(s, salloc(&b.tile, nt));
+  SCHK(s, salloc(&b.tile2, nt));
+  SCHK(s, salloc(&b.comp_idx, cap));
+  SCHK(s, salloc(&b.comp_pts, cap));
+  SCHK(s, salloc(&b.inl_idx, cap));
+  SCHK(s, salloc(&b.fin_idx, cap));
+  SCHK(s, salloc(&b.surv_in, cap));
+  SCHK(s, salloc(&b.spts, cap));
+  for (int k = 0; k < 2; k++) {
+    SCHK(s, salloc(&b.key[k], cap));
+    SCHK(s, salloc(&b.val[k], cap));
+  }
+  SCHK(s, salloc(&b.hist, 256 * nt + 256));
+  SCHK(s, salloc(&b.sorted, cap));
+  SCHK(s, salloc(&b.cell_start, cap));
+  SCHK(s, salloc(&b.cell_key, cap));
+  SCHK(s, salloc(&b.cell_of, cap));
+  SCHK(s, salloc(&b.parent, cap));
+  SCHK(s, salloc(&b.label, cap));
+  SCHK(s, salloc(&b.csize, cap));
+  SCHK(s, salloc(&b.roots, cap));
+  SCHK(s, salloc(&b.crank, cap));
+  SCHK(s, salloc(&b.sizes, cap));
+  SCHK(s, salloc(&b.bpart, 6 * 1024));
+  SCHK(s, salloc(&b.out_idx, cap));
+  SCHK(s, salloc(&b.out_pts, cap));
+  s->cap = cap;
+  return PFT_OK;
+}
+
+extern "C" void pft_segment_default_config(pft_segment_config* c) {
+  if (!c) return;
+  memset(c, 0, sizeof(*c));
+  c->abi_version = PFT_ABI_VERSION;
+  for (int k = 0; k < 16; k++) c->transform[k] = (k % 5 == 0) ? 1.0f : 0.0f;
+  c->plane_enable = 1;                // create_model_planar_segmentation.cpp:161-167
+  c->max_iterations = 1000;
+  c->distance_threshold = 0.015;
+  c->probability = 0.99;              // SampleConsensus::probability_ default
+  c->seed = 12345u;                   // SampleConsensusModel(random = false)
+  c->optimize_coefficients = 1;       // SACSegmentation default
+  c->box_enable[0] = c->box_enable[1] = 1;  // PassThrough y then x (:178-188); create_model.cpp adds z
+  c->box_min[0] = 0.45f;  c->box_max[0] = 1.1f;   // params.yaml segm_limits, "normal table"
+  c->box_min[1] = -0.6f;  c->box_max[1] = 0.6f;
+  c->box_min[2] = -0.17f; c->box_max[2] = 0.2f;
+  c->cluster_tolerance = 0.02;        // :186-188
+  c->min_cluster_size = 500;
+  c->max_cluster_size = 25000;
+  c->max_points = 960 * 540;          // Kinect2 qhd
+}
+
+extern "C" int pft_segment_create(const pft_segment_config* cfg, pft_segment** out) {
+  if (!cfg || !out) return PFT_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (cfg->abi_version != PFT_ABI_VERSION) return PFT_ERR_INVALID_ARG;
+  if (cfg->max_iterations < 0 || cfg->max_iterations > SG_MAX_ITER) return PFT_ERR_INVALID_ARG;
+  if (!(cfg->distance_threshold >= 0.0) || !(cfg->probability > 0.0 && cfg->probability < 1.0)) return PFT_ERR_INVALID_ARG;
+  if (!(cfg->cluster_tolerance > 0.0) || cfg->min_cluster_size < 0 || cfg->max_cluster_size < 1) return PFT_ERR_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PFT_ERR_NO_DEVICE;  // no CPU path
+  if (cfg->device_id < 0 || cfg->device_id >= ndev) return PFT_ERR_INVALID_ARG;
+  if (hipSetDevice(cfg->device_id) != hipSuccess) return PFT_ERR_NO_DEVICE;
+  pft_segment* s = new pft_segment();
+  s->cfg = *cfg;
+  bool ok = true;
+  if (cfg->stream_is_external) {
+    s->stream = reinterpret_cast<hipStream_t>(cfg->stream);
+  } else {
+    ok = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess;
+    s->own_stream = ok;
+  }
+  for (int k = 0; ok && k < SG_NEV; k++) ok = hipEventCreate(&s->ev[k]) == hipSuccess;
+  s->hmax = ((uint32_t)cfg->max_iterations + 1u + SG_BATCH - 1u) / SG_BATCH * SG_BATCH;
+  if (ok)
+    ok = salloc(&s->hdr, 1) == hipSuccess &&
+         hipHostMalloc(reinterpret_cast<void**>(&s->host_hdr), sizeof(SgHdr), hipHostMallocDefault) == hipSuccess &&
+         salloc(&s->smp.mt, MT_N) == hipSuccess && salloc(&s->smp.mk, SG_MAPCAP) == hipSuccess &&
+         salloc(&s->smp.mv, SG_MAPCAP) == hipSuccess && salloc(&s->hyp.sample, 3 * (size_t)s->hmax) == hipSuccess &&
+         salloc(&s->hyp.coef, s->hmax) == hipSuccess && salloc(&s->hyp.count, s->hmax) == hipSuccess;
+  if (ok) ok = ensure_capacity(s, cfg->max_points ? cfg->max_points : SG_TILE) == PFT_OK;
+  if (!ok) {
+    pft_segment_destroy(s);
+    return PFT_ERR_HIP;
+  }
+  *out = s;
+  return PFT_OK;
+}
+
+extern "C" void pft_segment_destroy(pft_segment* s) {
+  if (!s) return;
+  if (s->stream) hipStreamSynchronize(s->stream);
+  free_buffers(s);
+  sfree(s->hdr);
+  if (s->host_hdr) hipHostFree(s->host_hdr);
+  sfree(s->smp.mt); sfree(s->smp.mk); sfree(s->smp.mv);
+  sfree(s->hyp.sample); sfree(s->hyp.coef); sfree(s->hyp.count);
+  for (int k = 0; k < SG_NEV; k++)
+    if (s->ev[k]) hipEventDestroy(s->ev[k]);
+  if (s->own_stream && s->stream) hipStreamDestroy(s->stream);
+  delete s;
+}
+
+extern "C" const char* pft_segment_last_error_string(const pft_segment* s) { return s ? s->err.c_str() : "null handle"; }
+
+// an event after the launches of one stage: the time since the previous event is booked to that stage (stage -1: an
+// event right after a host synchronisation, whose gap is host idle time and booked nowhere)
+static int mark(pft_segment* s, int stage) {
+  if (s->nev >= SG_NEV) return PFT_OK;  // (cannot happen: at most 3 per batch + 16)
+  SCHK(s, hipEventRecord(s->ev[s->nev], s->stream));
+  s->ev_stage[s->nev] = stage;
+  s->nev++;
+  return PFT_OK;
+}
+#define MARK(st)                         \
+  do {                                   \
+    int r_ = mark(s, (st));              \
+    if (r_ != PFT_OK) return r_;         \
+  } while (0)
+
+enum { ST_COMPACT = 0, ST_SAMPLE, ST_SCORE, ST_REPLAY, ST_REFIT, ST_CLUSTER, ST_OUTPUT };
+
+static int read_hdr(pft_segment* s) {
+  SCHK(s, hipMemcpyAsync(s->host_hdr, s->hdr, sizeof(SgHdr), hipMemcpyDeviceToHost, s->stream));
+  SCHK(s, hipStreamSynchronize(s->stream));
+  SCHK(s, hipGetLastError());
+  return PFT_OK;
+}
+
+static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t n) {
+  const pft_segment_config& c = s->cfg;
+  hipStream_t st = s->stream;
+  SgBufs& b = s->b;
+  SgParams p = {};
+  p.n = n;
+  p.transform_enable = c.transform_enable;
+  for (int k = 0; k < 12; k++) p.T[k] = c.transform[k];
+  p.zero_thr = float_bound_below(0.01);
+  p.dist_thr = float_bound_below(c.distance_threshold);
+  p.log_probability = log(1.0 - c.probability);
+  p.max_iterations = c.max_iterations;
+  p.seed = c.seed;
+  for (int a = 0; a < 3; a++) {
+    p.box_enable[a] = c.box_enable[a];
+    p.box_min[a] = c.box_min[a];
+    p.box_max[a] = c.box_max[a];
+  }
+  p.tol2 = (float)(c.cluster_tolerance * c.cluster_tolerance);
+  p.inv_cell = (float)(2.0 / (c.cluster_tolerance * SG_CELL_SLACK));
+  p.min_size = (uint32_t)c.min_cluster_size;
+  p.max_size = (uint32_t)c.max_cluster_size;
+  const uint32_t ntiles = (n + SG_TILE - 1) / SG_TILE;
+  SgHdr h0 = {};
+  h0.k = 1.0;
+  h0.best_count = -INT32_MAX;
+  h0.best_h = -1;
+  s->nev = 0;
+  SCHK(s, hipMemcpyAsync(s->hdr, &h0, sizeof(SgHdr), hipMemcpyHostToDevice, st));
+  MARK(ST_COMPACT);
+  // 1 + 2: transform, removeZeroPoints, compaction (indices into the input, transformed points)
+  hipLaunchKernelGGL(k_sg_zero, dim3(ntiles), dim3(SG_THREADS), 0, st, p, d_in, b.tx, b.flag, b.tile);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles, (const uint32_t*)nullptr, &s->hdr->n_valid);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag, n, (const uint32_t*)nullptr, b.tile,
+                     (const uint32_t*)nullptr, b.comp_idx, b.tx, b.comp_pts);
+  MARK(ST_COMPACT);
+  const uint32_t* n_valid = &s->hdr->n_valid;
+  if (c.plane_enable) {
+    // 3. RANSAC in batches; every launch after the deciding batch returns at once
+    SCHK(s, hipMemsetAsync(s->hyp.count, 0, s->hmax * sizeof(uint32_t), st));
+    const uint32_t nscore = (n + SG_THREADS * SG_SCORE_PTS - 1) / (SG_THREADS * SG_SCORE_PTS);
+    for (uint32_t bt = 0; bt * SG_BATCH < s->hmax; bt++) {
+      hipLaunchKernelGGL(k_sg_sample, dim3(1), dim3(SG_THREADS), 0, st, p, s->hdr, s->smp, s->hyp,
+                         (const float4*)b.comp_pts, bt);
+      MARK(ST_SAMPLE);
+      hipLaunchKernelGGL(k_sg_score, dim3(nscore), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, s->hyp,
+                         (const float4*)b.comp_pts, bt);
+      MARK(ST_SCORE);
+      hipLaunchKernelGGL(k_sg_replay, dim3(1), dim3(64), 0, st, p, s->hdr, s->hyp, bt);
+      MARK(ST_REPLAY);
+    }
+    // inliers of the best hypothesis, refit, final inliers + survivors
+    hipLaunchKernelGGL(k_sg_select, dim3(ntiles), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, 0,
+                       (const float4*)b.comp_pts, b.flag, b.tile, (uint8_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles, n_valid, &s->hdr->n_ransac_inl);
+    hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag, n, n_valid, b.tile,
+                       (const uint32_t*)nullptr, b.inl_idx, (const float4*)nullptr, (float4*)nullptr);
+    hipLaunchKernelGGL(k_sg_refit, dim3(1), dim3(SG_REFIT_THREADS), 0, st, p, s->hdr, c.optimize_coefficients,
+                       (const float4*)b.comp_pts, (const uint32_t*)b.inl_idx);
+    MARK(ST_REFIT);
+  }
+  // 4 + 5: ExtractIndices negative, PassThrough box (no plane: every point is a non-inlier)
+  hipLaunchKernelGGL(k_sg_select, dim3(ntiles), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, 1,
+                     (const float4*)b.comp_pts, b.flag, b.tile, b.flag2, b.tile2);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles, n_valid, &s->hdr->n_fin);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag, n, n_valid, b.tile,
+                     (const uint32_t*)b.comp_idx, b.fin_idx, (const float4*)nullptr, (float4*)nullptr);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile2, ntiles, n_valid, &s->hdr->n_surv);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag2, n, n_valid, b.tile2,
+                     (const uint32_t*)b.comp_idx, b.surv_in, (const float4*)b.comp_pts, b.spts);
+  const uint32_t nbparts = 1024;
+  hipLaunchKernelGGL(k_sg_bounds, dim3(nbparts), dim3(SG_THREADS), 0, st, (const SgHdr*)s->hdr, (const float4*)b.spts,
+                     b.bpart);
+  hipLaunchKernelGGL(k_sg_bounds2, dim3(1), dim3(SG_THREADS), 0, st, s->hdr, (const float*)b.bpart, nbparts);
+  MARK(ST_COMPACT);
+  int r = read_hdr(s);  // the survivor count and their bounds size the clustering
+  if (r != PFT_OK) return r;
+  SgHdr* H = s->host_hdr;
+  if (H->err & SG_ERR_MAP) {
+    s->err = "RANSAC: the sparse map of drawIndexSample's swaps is full (too many degenerate samples)";
+    return PFT_ERR_CAPACITY;
+  }
+  const uint32_t m = H->n_surv;
+  uint32_t nc = 0, total = 0;
+  s->sizes.clear();
+  MARK(-1);  // host round trip: booked to no stage
+  // RULE size: no cluster can be kept when min > max or when there are fewer survivors than min
+  const bool cluster = m > 0 && p.min_size <= p.max_size && m >= p.min_size;
+  if (cluster) {
+    uint64_t dims[3];
+    for (int a = 0; a < 3; a++) {
+      const float ext = (H->bmax[a] - H->bmin[a]) * p.inv_cell;
+      if (!(ext < 4.0e9f)) {
+        s->err = "clustering: survivor bounding box too large for the cell grid (non-finite or far points)";
+        return PFT_ERR_CAPACITY;
+      }
+      dims[a] = (uint64_t)floorf(ext) + 1u;
+      if (dims[a] > SG_MAX_AXIS_CELLS) {
+        s->err = "clustering: the survivors' bounding box spans more than 2^17 cells of side tolerance / 2 on one axis";
+        return PFT_ERR_CAPACITY;
+      }
+    }
+    if (dims[0] * dims[1] * dims[2] >= 0xFFFFFFFFull) {
+      s->err = "clustering: more than 2^32 cells of side tolerance / 2 over the survivors' bounding box";
+      return PFT_ERR_CAPACITY;
+    }
+    p.nx = (uint32_t)dims[0];
+    p.ny = (uint32_t)dims[1];
+    p.nz = (uint32_t)dims[2];
+    const uint64_t ncell_grid = dims[0] * dims[1] * dims[2];
+    int bits = 0;
+    while (bits < 32 && (1ull << bits) < ncell_grid) bits++;
+    const uint32_t mt = (m + SG_TILE - 1) / SG_TILE, mb = (m + SG_THREADS - 1) / SG_THREADS;
+    hipLaunchKernelGGL(k_sg_cellkey, dim3(mb), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, (const float4*)b.spts,
+                       b.key[0], b.val[0], m);
+    int cur = pftk_radix_sort_pairs(st, b.key, b.val, m, bits, b.hist);
+    const uint32_t* skey = b.key[cur];
+    const uint32_t* sval = b.val[cur];
+    hipLaunchKernelGGL(k_sg_heads, dim3(mt), dim3(SG_THREADS), 0, st, skey, m, b.flag, b.tile);
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, mt, (const uint32_t*)nullptr, &s->hdr->n_cells);
+    hipLaunchKernelGGL(k_sg_cells, dim3(mt), dim3(SG_THREADS), 0, st, skey, sval, m, (const uint8_t*)b.flag,
+                       (const uint32_t*)b.tile, b.cell_start, b.cell_key, (const float4*)b.spts, b.sorted, b.cell_of);
+    hipLaunchKernelGGL(k_sg_forest, dim3(mb), dim3(SG_THREADS), 0, st, sval, m, (const uint32_t*)b.cell_of,
+                       (const uint32_t*)b.cell_start, b.parent);
+    const uint32_t nlink = (uint32_t)std::min<uint64_t>(((uint64_t)m * 62u + SG_THREADS - 1) / SG_THREADS, 8192u);
+    hipLaunchKernelGGL(k_sg_link, dim3(nlink), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr,
+                       (const uint32_t*)b.cell_start, (const uint32_t*)b.cell_key, sval, (const float4*)b.sorted, m,
+                       b.parent);
+    SCHK(s, hipMemsetAsync(b.csize, 0, m * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_sg_label, dim3(mb), dim3(SG_THREADS), 0, st, m, b.parent, b.label, b.csize);
+    hipLaunchKernelGGL(k_sg_roots, dim3(mt), dim3(SG_THREADS), 0, st, p, m, (const uint32_t*)b.label,
+                       (const uint32_t*)b.csize, b.flag, b.tile);
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, mt, (const uint32_t*)nullptr, &s->hdr->n_clusters);
+    hipLaunchKernelGGL(k_sg_emit, dim3(mt), dim3(SG_THREADS), 0, st, b.flag, m, (const uint32_t*)nullptr, b.tile,
+                       (const uint32_t*)nullptr, b.roots, (const float4*)nullptr, (float4*)nullptr);
+    MARK(ST_CLUSTER);
+    r = read_hdr(s);
+    if (r != PFT_OK) return r;
+    MARK(-1);
+    nc = H->n_clusters;
+    if (nc > 0) {
+      const uint32_t nb = (nc + SG_THREADS - 1) / SG_THREADS;
+      hipLaunchKernelGGL(k_sg_order_keys, dim3(nb), dim3(SG_THREADS), 0, st, p, nc, (const uint32_t*)b.roots,
+                         (const uint32_t*)b.csize, b.key[0], b.val[0]);
+      int kbits = 0;
+      while (kbits < 32 && (1ull << kbits) <= (uint64_t)(p.max_size - std::min(p.min_size, p.max_size))) kbits++;
+      cur = pftk_radix_sort_pairs(st, b.key, b.val, nc, kbits, b.hist);
+      SCHK(s, hipMemsetAsync(b.crank, 0xFF, m * sizeof(uint32_t), st));
+      hipLaunchKernelGGL(k_sg_rank, dim3(nb), dim3(SG_THREADS), 0, st, nc, (const uint32_t*)b.val[cur],
+                         (const uint32_t*)b.csize, b.crank, b.sizes);
+      hipLaunchKernelGGL(k_sg_member_keys, dim3(mb), dim3(SG_THREADS), 0, st, m, nc, (const uint32_t*)b.label,
+                         (const uint32_t*)b.crank, b.key[0], b.val[0]);
+      int rbits = 0;
+      while ((1ull << rbits) <= (uint64_t)nc) rbits++;
+      cur = pftk_radix_sort_pairs(st, b.key, b.val, m, rbits, b.hist);
+      MARK(ST_CLUSTER);
+      s->sizes.resize(nc);
+      SCHK(s, hipMemcpyAsync(s->sizes.data(), b.sizes, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      SCHK(s, hipStreamSynchronize(st));
+      MARK(-1);
+      for (uint32_t k = 0; k < nc; k++) total += s->sizes[k];
+      hipLaunchKernelGGL(k_sg_output, dim3((total + SG_THREADS - 1) / SG_THREADS), dim3(SG_THREADS), 0, st, total,
+                         (const uint32_t*)b.val[cur], (const uint32_t*)b.surv_in, d_in, b.out_idx, b.out_pts);
+      MARK(ST_OUTPUT);
+    }
+  }
+  SCHK(s, hipGetLastError());
+  r = read_hdr(s);
+  if (r != PFT_OK) return r;
+  s->res = *H;
+  s->res.n_clusters = nc;
+  s->res.n_total = total;
+  s->last_ms = 0.0;
+  for (int k = 0; k < PFT_SEGMENT_STAGES; k++) s->stage_ms[k] = 0.0;
+  for (int e = 1; e < s->nev; e++) {
+    float ms = 0.0f;
+    SCHK(s, hipEventElapsedTime(&ms, s->ev[e - 1], s->ev[e]));
+    if (s->ev_stage[e] < 0) continue;  // the gap spans a host synchronisation
+    s->stage_ms[s->ev_stage[e]] += ms;
+    s->last_ms += ms;
+  }
+  return PFT_OK;
+}
+
+static int apply_common(pft_segment* s, const pft_point_xyzrgba* pts, size_t n, bool on_device) {
+  if (!s || (!pts && n)) return PFT_ERR_INVALID_ARG;
+  if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
+  s->have_result = false;
+  SCHK(s, hipSetDevice(s->cfg.device_id));
+  if (n == 0) {  // empty input cloud: no plane, no clusters
+    s->res = SgHdr();
+    s->res.best_h = -1;
+    s->sizes.clear();
+    s->n_in = 0;
+    s->last_ms = 0.0;
+    for (int k = 0; k < PFT_SEGMENT_STAGES; k++) s->stage_ms[k] = 0.0;
+    s->have_result = true;
+    return PFT_OK;
+  }
+  int r = ensure_capacity(s, n);
+  if (r != PFT_OK) return r;
+  const pft_point_xyzrgba* d_in = pts;
+  if (!on_device) {
+    if (n) SCHK(s, hipMemcpyAsync(s->b.in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, s->stream));
+    d_in = s->b.in_own;
+  }
+  r = run_pipeline(s, d_in, (uint32_t)n);
+  if (r != PFT_OK) return r;
+  s->n_in = n;
+  s->have_result = true;
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_apply(pft_segment* s, const pft_point_xyzrgba* host_points, size_t n) {
+  return apply_common(s, host_points, n, false);
+}
+extern "C" int pft_segment_apply_device(pft_segment* s, const pft_point_xyzrgba* device_points, size_t n) {
+  return apply_common(s, device_points, n, true);
+}
+
+extern "C" int pft_segment_get_plane(const pft_segment* s, pft_segment_plane* pl) {
+  if (!s || !pl) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  const SgHdr& h = s->res;
+  memset(pl, 0, sizeof(*pl));
+  pl->n_valid = h.n_valid;
+  pl->n_survivors = h.n_surv;
+  if (!s->cfg.plane_enable) {
+    pl->status = PFT_PLANE_DISABLED;
+    return PFT_OK;
+  }
+  pl->iterations = h.iterations;
+  pl->hypotheses_scored = h.emitted;
+  if (h.best_h < 0) {
+    pl->status = PFT_PLANE_NONE;
+    pl->sample[0] = pl->sample[1] = pl->sample[2] = -1;
+    return PFT_OK;
+  }
+  pl->status = PFT_PLANE_FOUND;
+  for (int k = 0; k < 4; k++) {
+    pl->coefficients[k] = h.coef_final[k];
+    pl->ransac_coefficients[k] = h.coef_ransac[k];
+  }
+  pl->ransac_inliers = h.n_ransac_inl;
+  pl->inliers = h.n_fin;
+  int32_t smp[3];
+  pft_segment* sm = const_cast<pft_segment*>(s);
+  if (hipMemcpy(smp, s->hyp.sample + 3 * (size_t)h.best_h, sizeof(smp), hipMemcpyDeviceToHost) != hipSuccess) {
+    sm->err = "hipMemcpy of the best sample failed";
+    return PFT_ERR_HIP;
+  }
+  for (int k = 0; k < 3; k++) pl->sample[k] = smp[k];
+  return PFT_OK;
+}
+
+// the best hypothesis' inliers are kept as compacted indices; mapped to the input on the way out
+__global__ void k_sg_map_idx(uint32_t n, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ map,
+                             int32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (int32_t)map[idx[i]];
+}
+
+extern "C" int pft_segment_get_plane_inliers(pft_segment* s, int which, int32_t* host_idx, size_t capacity, size_t* n) {
+  if (!s || !n || (which != 0 && which != 1)) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  const bool have = s->cfg.plane_enable && s->res.best_h >= 0;
+  const uint32_t cnt = !have ? 0u : (which == 0 ? s->res.n_fin : s->res.n_ransac_inl);
+  *n = cnt;
+  if (cnt > capacity) return PFT_ERR_CAPACITY;
+  if (!cnt) return PFT_OK;
+  if (!host_idx) return PFT_ERR_INVALID_ARG;
+  const int32_t* src = reinterpret_cast<const int32_t*>(s->b.fin_idx);
+  if (which == 1) {  // crank is scratch once an apply has finished
+    int32_t* tmp = reinterpret_cast<int32_t*>(s->b.crank);
+    hipLaunchKernelGGL(k_sg_map_idx, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, cnt,
+                       (const uint32_t*)s->b.inl_idx, (const uint32_t*)s->b.comp_idx, tmp);
+    SCHK(s, hipGetLastError());
+    src = tmp;
+  }
+  SCHK(s, hipMemcpyAsync(host_idx, src, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  SCHK(s, hipStreamSynchronize(s->stream));
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_cluster_count(const pft_segment* s, size_t* n_clusters) {
+  if (!s || !n_clusters) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  *n_clusters = s->res.n_clusters;
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_cluster_sizes(const pft_segment* s, uint32_t* sizes, size_t capacity) {
+  if (!s) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  if (s->sizes.size() > capacity) return PFT_ERR_CAPACITY;
+  if (!s->sizes.empty()) {
+    if (!sizes) return PFT_ERR_INVALID_ARG;
+    memcpy(sizes, s->sizes.data(), s->sizes.size() * sizeof(uint32_t));
+  }
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_get_cluster_indices(pft_segment* s, int32_t* host_idx, size_t capacity, size_t* n_total) {
+  if (!s || !n_total) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  *n_total = s->res.n_total;
+  if (s->res.n_total > capacity) return PFT_ERR_CAPACITY;
+  if (!s->res.n_total) return PFT_OK;
+  if (!host_idx) return PFT_ERR_INVALID_ARG;
+  SCHK(s, hipMemcpyAsync(host_idx, s->b.out_idx, s->res.n_total * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  SCHK(s, hipStreamSynchronize(s->stream));
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_get_cluster_points(pft_segment* s, pft_point_xyzrgba* host_pts, size_t capacity,
+                                              size_t* n_total) {
+  if (!s || !n_total) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  *n_total = s->res.n_total;
+  if (s->res.n_total > capacity) return PFT_ERR_CAPACITY;
+  if (!s->res.n_total) return PFT_OK;
+  if (!host_pts) return PFT_ERR_INVALID_ARG;
+  SCHK(s, hipMemcpyAsync(host_pts, s->b.out_pts, s->res.n_total * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost,
+                         s->stream));
+  SCHK(s, hipStreamSynchronize(s->stream));
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_last_ms(const pft_segment* s, double* ms, double* stage_ms) {
+  if (!s || !ms) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  *ms = s->last_ms;
+  if (stage_ms)
+    for (int k = 0; k < PFT_SEGMENT_STAGES; k++) stage_ms[k] = s->stage_ms[k];
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_segment_hypotheses(pft_segment* s, int32_t* samples, uint32_t* counts, size_t capacity,
+                                            size_t* n) {
+  if (!s || !n) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  const size_t cnt = s->cfg.plane_enable ? s->res.iterations : 0;
+  *n = cnt;
+  if (cnt > capacity) return PFT_ERR_CAPACITY;
+  if (!cnt) return PFT_OK;
+  if (!samples || !counts) return PFT_ERR_INVALID_ARG;
+  SCHK(s, hipMemcpy(samples, s->hyp.sample, 3 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  SCHK(s, hipMemcpy(counts, s->hyp.count, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return PFT_OK;
+}

@@ -3,7 +3,7 @@
 // that auto_tracking.cpp once loaded directly (pcl::io::loadPCDFile, :741): PCD v0.7, DATA ascii, binary or binary_compressed,
 // fields x y z and rgba (TYPE U) or rgb (TYPE F, packed bits).  Host-side I/O only; other
 // fields are skipped.  DATA binary_compressed (LZF; what pcl::PCDWriter::writeBinaryCompressed and pcl_convert_pcd_ascii_binary
-// produce) is read too.
+// produce) is read too.  writePCDFile writes the files the model-creation nodes write (ascii, or binary).
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -197,6 +197,41 @@ inline int loadPCDFile(const std::string& path, PointCloud<PointXYZRGBA>& cloud)
   cloud.height = (uint32_t)height;
   cloud.is_dense = dense;
   return 0;
+}
+
+// pcl::PCDWriter::write<PointXYZRGBA>(path, cloud, binary): PCD v0.7 with fields x y z rgba (TYPE F F F U), one row,
+// viewpoint the identity.  binary = false is what the reference's model-creation nodes call
+// (create_model_planar_segmentation.cpp:243, PCL's writeASCII, 8 significant digits, "nan"); binary = true writes the
+// packed 16-byte records, which keeps every bit of the points.  Returns 0 on success, -1 on failure.
+inline int writePCDFile(const std::string& path, const PointCloud<PointXYZRGBA>& cloud, bool binary) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) return -1;
+  const size_t n = cloud.points.size();
+  std::fprintf(f,
+               "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgba\nSIZE 4 4 4 4\nTYPE F F F U\n"
+               "COUNT 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA %s\n",
+               n, n, binary ? "binary" : "ascii");
+  bool ok = true;
+  for (size_t i = 0; i < n && ok; i++) {
+    const PointXYZRGBA& q = cloud.points[i];
+    if (binary) {
+      unsigned char rec[16];
+      std::memcpy(rec, &q.x, 4);
+      std::memcpy(rec + 4, &q.y, 4);
+      std::memcpy(rec + 8, &q.z, 4);
+      std::memcpy(rec + 12, &q.rgba, 4);
+      ok = std::fwrite(rec, 1, 16, f) == 16;
+    } else {
+      const float v[3] = {q.x, q.y, q.z};
+      for (int k = 0; k < 3 && ok; k++) {
+        if (v[k] != v[k]) ok = std::fprintf(f, "nan ") > 0;
+        else ok = std::fprintf(f, "%.8g ", (double)v[k]) > 0;
+      }
+      if (ok) ok = std::fprintf(f, "%u\n", (unsigned)q.rgba) > 0;
+    }
+  }
+  if (std::fclose(f) != 0) ok = false;
+  return ok ? 0 : -1;
 }
 
 }  // namespace io
