@@ -207,8 +207,20 @@ int pft_debug_get_host_stat(pft_tracker* t, uint32_t out4[4]);
 int pft_debug_get_ticks(pft_tracker* t, uint64_t* ticks32);
 /* descent statistics of the last pft_eval_weights call that asked for the NN arrays: [0..10] queries by
  * number of generic levels, [11] queries that used the jump table, [12] wave iterations, [13..15] sums of
- * the per-wave maxima of generic levels / fast levels / leaf size, [16..26] wave iterations by max generic */
+ * the per-wave maxima of generic levels / fast levels / leaf size, [16..26] wave iterations by max generic,
+ * [27..29] zero, [30] reference points the particles' bounding box is taken over (the hull subset), [31] all reference
+ * points (the exact-NN mode puts its own bookkeeping into [8..13]) */
 int pft_debug_get_descent_stats(pft_tracker* t, uint64_t* dbg32);
+/* the same call's queries by number of "hard" generic steps (the per-axis nearest child is absent): 0, 1, 2, 3, >= 4 */
+int pft_debug_get_hard_steps(pft_tracker* t, uint64_t out5[5]);
+/* what the likelihood kernel chose in the last pft_eval_weights call that asked for the NN arrays (zero otherwise):
+ * out4[0] bit 0 valid, bits 1-2 LDS layout (0 node words + u16 leaf starts, 1 u32 node words, 2 branch levels only,
+ * 3 hybrid: top words in LDS), bits 3-4 descent (0 fast, 1 table generic, 2 no centre tables), bit 5 the instance reads
+ * leaf records through leaf_order, bit 6 the builder's leaf_indirect, bit 7 the fast descent's jump table was dropped to
+ * make the node words fit, bits 8-11 jump level used (0: none);
+ * out4[1] node words held in LDS by the hybrid layout, out4[2] the workgroup's LDS bytes, out4[3] the fast descent's
+ * margin in leaf cells (float bits) */
+int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4]);
 /* host-only (no device needed): the positions of the reference points the bounding box of the particles' transformed
  * clouds is taken over (A3: calcBoundingBox of the tracker that /root/reference/src/auto_tracking.cpp:691-693 runs) -- the
  * convex hull's vertices plus the shell the float evaluation can reach; `keep` has room for n indices (ascending),

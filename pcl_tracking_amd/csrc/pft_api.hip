@@ -1434,6 +1434,7 @@ extern "C" int pft_eval_weights(pft_tracker* t, const pft_particle* particles, s
   d.bbox6 = t->d_bbox6;
   HIPCHK(t, hipMemcpyAsync(t->d_dbg_part, particles, P * sizeof(pft_particle), hipMemcpyHostToDevice, t->stream));
   HIPCHK(t, hipMemsetAsync(&t->d_hdr->stat_queries, 0, (2 + 32) * sizeof(unsigned long long), t->stream));
+  HIPCHK(t, hipMemsetAsync(t->d_hdr->dbg_hard, 0, sizeof(t->d_hdr->dbg_hard) + sizeof(t->d_hdr->lik_layout), t->stream));
   pftk_pose_to_matrix(t->stream, t->d_dbg_part, (uint32_t)P, t->d_mats);
   stage_aabb(t, d, (uint32_t)P, false);
   stage_crop_octree_likelihood(t, d, (uint32_t)P, want_nn, true, true);
@@ -1538,6 +1539,24 @@ extern "C" int pft_debug_get_descent_stats(pft_tracker* t, uint64_t* dbg32) {
     dbg32[12] = h.eg_ncells;
     dbg32[13] = h.n_crop;
   }
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4]) {
+  if (!t || !out4) return PFT_ERR_INVALID_ARG;
+  PftHeader h;
+  int r = read_hdr(t, &h);
+  if (r != PFT_OK) return r;
+  memcpy(out4, h.lik_layout, sizeof(h.lik_layout));
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_get_hard_steps(pft_tracker* t, uint64_t out5[5]) {
+  if (!t || !out5) return PFT_ERR_INVALID_ARG;
+  PftHeader h;
+  int r = read_hdr(t, &h);
+  if (r != PFT_OK) return r;
+  for (int i = 0; i < 5; i++) out5[i] = h.dbg_hard[i];
   return PFT_OK;
 }
 

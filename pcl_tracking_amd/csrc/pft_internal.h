@@ -130,6 +130,14 @@ struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (
   unsigned long long eq_totals;     // (64-query blocks << 32) | queries of the cells allotted so far (k_ec_slots)
   alignas(128) uint32_t crop_ticket;  // one-pass crop: workgroups take their logical index here (the last one resets it)
   uint32_t pop_bar[4];   // population kernel: arrival counters of its three device-scope barriers + "done" (self-resetting)
+  // DEBUG_NN likelihood instance: queries by number of "hard" generic steps (0, 1, 2, 3, >= 4), then (directly after it:
+  // pft_eval_weights clears both with one memset) the instance's choice (workgroup 0, thread 0; cleared by pft_eval_weights, read by
+  // pft_debug_get_likelihood_layout): [0] bit 0 valid, bits 1-2 layout (0 node words + u16 leaf starts, 1 u32 node words,
+  // 2 branch levels only, 3 hybrid), bits 3-4 descent (0 fast, 1 table generic, 2 no table), bit 5 INDIRECT instance,
+  // bit 6 leaf_indirect, bit 7 the jump table dropped to make the words fit, bits 8-11 J used; [1] n_lds_words (hybrid);
+  // [2] lds_bytes; [3] margin_cells (float bits)
+  unsigned long long dbg_hard[5];
+  uint32_t lik_layout[4];
 };
 
 struct PftDev {  // device pointers (host-side struct, passed by value)

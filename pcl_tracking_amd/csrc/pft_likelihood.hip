@@ -359,7 +359,7 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
           }
           for (int h_ = 0; h_ <= 4; h_++) {
             const unsigned long long m_ = __ballot(hb == h_);
-            if (m_ && lane == first) atomicAdd(&d.hdr->dbg[27 + h_], (unsigned long long)__popcll(m_));
+            if (m_ && lane == first) atomicAdd(&d.hdr->dbg_hard[h_], (unsigned long long)__popcll(m_));
           }
           const unsigned long long mj_ = __ballot(dbg_jump != 0);
           if (mj_ && lane == first) atomicAdd(&d.hdr->dbg[11], (unsigned long long)__popcll(mj_));
@@ -496,6 +496,7 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
   // found by tools/fuzz_parity.py: this layout used to read the tables regardless, and a 12-level tree over a 41 m crop box
   // sent every query to one leaf)
   const bool branch_only = use_tab && !fits_with_jump && leaf16 && (size_t)used + jump_bytes + branch_bytes <= (size_t)lds_bytes;
+  const bool jump_dropped = !fits_with_jump && fits_without_jump && !branch_only && J > 0;
   if (!fits_with_jump && fits_without_jump && !branch_only) {
     J = 0;
     jump_bytes = 0;
@@ -506,6 +507,15 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
   uint16_t* lleaf = reinterpret_cast<uint16_t*>(smem + used + branch_bytes);
   const bool words_in_lds = !branch_only && (size_t)used + branch_bytes + leaf_bytes <= (size_t)lds_bytes;
   const uint32_t n_lds_words = (words_in_lds || branch_only) ? 0u : min(n_words, (lds_bytes - used) / 4u);
+  if (DEBUG_NN && blockIdx.x == 0 && threadIdx.x == 0) {  // which branch below runs (PftHeader::lik_layout)
+    const uint32_t layout = branch_only ? 2u : words_in_lds ? (leaf16 ? 0u : 1u) : 3u;
+    const uint32_t descent = fast ? 0u : use_tab ? 1u : 2u;
+    d.hdr->lik_layout[0] = 1u | (layout << 1) | (descent << 3) | (INDIRECT ? 32u : 0u) | (hdr->leaf_indirect ? 64u : 0u) |
+                           (jump_dropped ? 128u : 0u) | ((uint32_t)J << 8);
+    d.hdr->lik_layout[1] = n_lds_words;
+    d.hdr->lik_layout[2] = lds_bytes;
+    d.hdr->lik_layout[3] = __float_as_uint(hdr->margin_cells);
+  }
 
   for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) {
     lut_h[i] = (float)i / 180.0f;

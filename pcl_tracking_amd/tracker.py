@@ -17,6 +17,18 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+LIK_LAYOUTS = ("u16_leaf_starts", "u32_words", "branch_only", "hybrid")  # PftHeader::lik_layout bits 1-2
+LIK_DESCENTS = ("fast", "table_generic", "no_table")  # bits 3-4
+
+
+def decode_likelihood_layout(out4):
+    """pft_debug_get_likelihood_layout's four words -> dict (valid False: no DEBUG_NN likelihood launch recorded)"""
+    w = int(out4[0])
+    return dict(valid=bool(w & 1), layout=LIK_LAYOUTS[(w >> 1) & 3], descent=LIK_DESCENTS[min((w >> 3) & 3, 2)],
+                indirect=bool(w & 32), leaf_indirect=bool(w & 64), jump_dropped=bool(w & 128), J=(w >> 8) & 15,
+                n_lds_words=int(out4[1]), lds_bytes=int(out4[2]), margin_cells=float(np.uint32(out4[3]).view(np.float32)))
+
+
 class DistanceCoherence:
     """pcl::tracking::DistanceCoherence (auto_tracking.cpp:240-242)"""
 
@@ -321,9 +333,11 @@ class ParticleFilterTracker:
             self._check(self._L.pft_debug_get_point_keys(self._h, _ptr(keys), n.value))
         q, s = C.c_uint64(), C.c_uint64()
         self._check(self._L.pft_debug_get_scan_stats(self._h, C.byref(q), C.byref(s)))
+        lay = np.zeros(4, np.uint32)
+        self._check(self._L.pft_debug_get_likelihood_layout(self._h, _ptr(lay)))
         return dict(raw=raw, nn_idx=nn_idx, nn_d2=nn_d2, bbox=bbox, crop_idx=crop, octree_depth=depth.value,
                     octree_min=mn, octree_max=mx, n_leaves=nl.value, n_words=nn.value, point_keys=keys,
-                    scan_queries=q.value, scan_points=s.value)
+                    scan_queries=q.value, scan_points=s.value, lik_layout=decode_likelihood_layout(lay))
 
     def debugChangeState(self, which=0):
         """the change detector's state: dict(gate, counter, box (min xyz, max xyz), depth, ring (k, 5): tested, changed,

@@ -488,9 +488,9 @@ def test_compute_other_iteration_counts(gpu, orc, data, iters):
 
 
 def test_eval_weights_deep_tree_branch_levels_only_in_lds(gpu, orc, data):
-    """a depth-10 tree (5 mm leaves) whose centre tables, jump table and branch levels fit the likelihood kernel's 80 KiB
-    of LDS but whose leaf starts do not: the kernel then reads the leaf starts from L2 (third LDS layout of
-    pft_likelihood.hip); the layout is asserted from the tree's sizes so that this case keeps covering it"""
+    """a depth-10 tree (5 mm leaves) whose penalty table, centre tables, jump table and branch levels fit the likelihood
+    kernel's LDS but whose leaf starts do not: the kernel then reads the leaf starts from L2 (the branch-only layout of
+    pft_likelihood.hip); the layout the kernel recorded is asserted so that this case keeps covering it"""
     P, res = 64, 0.005
     model, cloud = scene.make_model(2048), scene.make_scene(50000)
     g = gpu.make_reference_tracker(particle_num=P, seed=1)
@@ -511,18 +511,16 @@ def test_eval_weights_deep_tree_branch_levels_only_in_lds(gpu, orc, data):
     gt = scene.model_gt_pose()
     p = np.zeros(P, scene.PARTICLE_DTYPE)
     for k, name in enumerate(("x", "y", "z")):
-        p[name] = gt[k] + rng.normal(0, 0.2, P)
+        p[name] = gt[k] + rng.normal(0, 0.18, P)  # (0.2 gives 10 464 branch words: one penalty table too many)
     for k, name in enumerate(("roll", "pitch", "yaw")):
-        p[name] = gt[3 + k] + rng.normal(0, 0.2, P)
+        p[name] = gt[3 + k] + rng.normal(0, 0.18, P)
     p["w"] = 1.0
     p["weight"] = 1.0 / P
     G = g.evalWeights(p, want_nn=True)
     O = o.eval_weights(p, want_nn=True, mats=g.debugPoseToMatrix(p))
-    D, nl, nw = G["octree_depth"], G["n_leaves"], G["n_words"]
-    leaf_start = nw - nl - 1
-    base = 2048 + 3 * (2 << D) * 4 + (2 << 12)
+    D, rec = G["octree_depth"], G["lik_layout"]
     assert D == O["octree_depth"] == 10
-    assert base + leaf_start * 4 <= 80 * 1024 < base + leaf_start * 4 + (nl + 1) * 2, (D, leaf_start, nl)
+    assert rec["valid"] and (rec["layout"], rec["descent"], rec["J"]) == ("branch_only", "fast", 4), rec
     np.testing.assert_array_equal(G["crop_idx"], O["crop_idx"])
     np.testing.assert_array_equal(G["nn_idx"], O["nn_idx"])
     np.testing.assert_array_equal(G["nn_d2"], O["nn_d2"])
@@ -1013,9 +1011,10 @@ def test_leaf_records_copied_or_followed_give_the_same_bits(gpu, data, P, monkey
 
 def test_deep_tree_without_centre_tables_in_the_branch_only_layout(gpu, orc):
     """Found by tools/fuzz_parity.py (round 3): wild particles (0.5 m / 1 rad spread) give a crop box of tens of metres, the
-    octree gets 12 levels (> PFT_TABLE_MAX_DEPTH: no centre tables, all-generic descent), and with ~20 000 cropped points
-    the likelihood kernel keeps the branch levels in LDS and the leaf starts in L2 -- a layout whose dispatch used to take
-    the table-reading descent regardless, sending every query to one leaf."""
+    octree gets 12 levels (> PFT_TABLE_MAX_DEPTH: no centre tables, all-generic descent), and ~20 000 cropped points used
+    to select the branch-only layout (branch levels in LDS, leaf starts in L2), whose dispatch took the table-reading
+    descent regardless and sent every query to one leaf.  The branch-only layout now requires the centre tables: this tree
+    takes the hybrid layout (top words in LDS) with the no-table descent, which the kernel's record must show."""
     model = scene.make_model(65, seed=65)
     cloud = scene.make_scene(20000)
     g, o = make_pair(gpu, orc, model, cloud, 700)
@@ -1030,3 +1029,5 @@ def test_deep_tree_without_centre_tables_in_the_branch_only_layout(gpu, orc):
     np.testing.assert_array_equal(G["nn_d2"].view(np.uint32), O["nn_d2"].view(np.uint32))
     assert ulp_diff(G["raw"], O["raw"]).max() <= 1
     assert len(np.unique(G["nn_idx"])) > 1000
+    rec = G["lik_layout"]
+    assert rec["valid"] and (rec["layout"], rec["descent"], rec["J"]) == ("hybrid", "no_table", 0), rec

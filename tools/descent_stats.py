@@ -23,12 +23,15 @@ st = t.evalWeights(p, want_nn=True)
 d = np.zeros(32, np.uint64)
 t._check(t._L.pft_debug_get_descent_stats(t._h, d.ctypes.data_as(C.c_void_p)))
 d = d.astype(np.float64)
+hard = np.zeros(5, np.uint64)
+t._check(t._L.pft_debug_get_hard_steps(t._h, hard.ctypes.data_as(C.c_void_p)))
+hard = hard.astype(np.float64)
 q = d[:11].sum()
 print("crop", len(st["crop_idx"]), "depth", st["octree_depth"], "leaves", st["n_leaves"], "words", st["n_words"],
       "kbar", st["scan_points"] / max(1, st["scan_queries"]))
 print("queries by #generic levels:", (d[:11] / q).round(4), "mean", (d[:11] * np.arange(11)).sum() / q)
 print("jump used:", d[11] / q)
-print("queries by #hard steps (ideal child missing) 0,1,2,3,4+:", (d[27:32] / q).round(4), "mean", (d[27:32] * np.arange(5)).sum() / q)
+print("queries by #hard steps (ideal child missing) 0,1,2,3,4+:", (hard / q).round(4), "mean", (hard * np.arange(5)).sum() / q)
 wi = d[12]
 print("per wave-iteration: max generic %.2f  max fast %.2f  max leaf %.2f" % (d[13] / wi, d[14] / wi, d[15] / wi))
 print("wave iterations by max generic:", (d[16:27] / wi).round(4))

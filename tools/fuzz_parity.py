@@ -38,6 +38,7 @@ import test_gpu_parity as TP  # noqa: E402
 KEYS = ("x", "y", "z", "roll", "pitch", "yaw")
 _scene_cache = {}
 LAST = {}  # description of the case being run (printed when it fails)
+LAYOUTS = {}  # likelihood layout code (DESIGN.md "likelihood layouts") -> weight evaluations of this campaign that ran it
 
 
 def cached_scene(kind, n):
@@ -142,6 +143,11 @@ def eval_case(rng, env):
     p = TP.particles_around(pose, P, int(rng.integers(1, 1 << 30)), sig_t, sig_r)
     mats = g.debugPoseToMatrix(p)
     G = g.evalWeights(p, want_nn=True)
+    rec = G["lik_layout"]
+    lay = "%s/%s%s/%s" % (rec["layout"], rec["descent"], "/nojump" if rec["jump_dropped"] else "",
+                          "indirect" if rec["indirect"] else "direct") if rec["valid"] else "none"
+    LAST["layout"] = lay
+    LAYOUTS[lay] = LAYOUTS.get(lay, 0) + 1
     O = o.eval_weights(p, want_nn=True, mats=mats)
     LAST.update(crop=len(O["crop_idx"]), depth_dev=int(G["octree_depth"]), depth_orc=int(O["octree_depth"]), leaves_dev=int(G["n_leaves"]),
                 omin=[float(v) for v in O["octree_min"]], omax=[float(v) for v in O["octree_max"]])
@@ -410,23 +416,31 @@ def campaign(minutes, seed, max_cases=None, verbose=True):
     t_end = time.time() + minutes * 60.0
     n = {"eval": 0, "track": 0, "filter": 0, "shard": 0, "exact": 0}
     failed = []
+    LAYOUTS.clear()
     t0 = time.time()
     case = 0
     while time.time() < t_end and (max_cases is None or case < max_cases):
         case += 1
         cseed = int(rng.integers(1, 1 << 62))
         kind, env = "?", {}
+        LAST.clear()
         try:
             kind, env, (desc, note) = run_case(cseed)
             n[kind] += 1
         except Exception as e:  # noqa: BLE001  (the campaign goes on; the case is reported with its seed)
-            failed.append((kind, cseed, repr(e)[:300], dict(LAST)))
+            lay = LAST.get("layout", "not reached")
+            failed.append((kind, cseed, "layout %s: %s" % (lay, repr(e)[:300]), dict(LAST)))
             if verbose:
-                print("FAILED case seed %d env %s: %s\n   case: %s" % (cseed, env, repr(e)[:500], LAST), flush=True)
+                print("FAILED case seed %d env %s layout %s: %s\n   case: %s" % (cseed, env, lay, repr(e)[:500], LAST),
+                      flush=True)
         if verbose and case % 25 == 0:
             print("%5d cases in %.0f s (%s), failures %d" % (case, time.time() - t0, n, len(failed)), flush=True)
     for k in ("PFT_FORCE_BUILDER", "PFT_LEAF_INDIRECT", "PFT_GENERIC_DESCENT"):
         os.environ.pop(k, None)
+    if verbose:
+        print("likelihood layouts of the weight evaluations:")
+        for lay in sorted(LAYOUTS):
+            print("   %6d  %s" % (LAYOUTS[lay], lay))
     return n, failed
 
 
