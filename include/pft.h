@@ -162,6 +162,44 @@ int pft_debug_change_state(pft_tracker* t, int which, uint32_t* gate, uint32_t* 
 int pft_debug_change_detect(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, int min_points, double resolution,
                             int reset, uint32_t* new_idx, size_t cap, size_t* n_new);
 
+/* ---- object report (drawResult + viz_cb, auto_tracking.cpp:301-326, :432-470): the full-resolution model moved by the
+ *      result pose, its centroid (the position the node publishes) and its principal-axis box (viz.addCube) ----
+ * Opt-in per handle and computed on the device, after pft_compute, on the handle's stream:
+ *   transform   pose_to_matrix(representative state) on the device (double cos / sin rounded to float), T[2][3] += -0.005f
+ *   tracked     ((T0 x + T1 y) + T2 z) + T3 per row for every report point; the other fields are copied
+ *   centroid    compute3DCentroid of the tracked cloud ([3] = 1)
+ *   covariance  computeCovarianceMatrixNormalized (row-major, symmetric)
+ *   eigenvalues SelfAdjointEigenSolver<Matrix3f>, ascending; axes = its eigenvectors with col 2 = col 0 x col 1 (row-major)
+ *   box_*       getMinMax3D of the tracked cloud in the principal frame (p2w = [axes^T | -(axes^T centroid)]);
+ *               box_centre = axes * (max + min) / 2 + centroid, box_quat = Quaternion(axes) {x, y, z, w}, box_size = max - min
+ * The sums follow pft_config::sum_order: PFT_SUM_TREE adjacent-pair trees in float, PFT_SUM_PCL index-order float chains
+ * (the centroid is then PCL's bit for bit whenever the transform is). */
+typedef struct pft_object_report {
+  float transform[16];   /* row-major 4x4, the offset included */
+  float centroid[4];
+  float covariance[9];
+  float eigenvalues[3];
+  float axes[9];
+  float box_min[3], box_max[3], box_centre[3];
+  float box_quat[4];
+  float box_size[3];
+  uint32_t n_points;
+  uint32_t info;         /* 0 success, 1 the eigen solver did not converge within 90 iterations */
+  uint32_t pad[1];
+} pft_object_report;     /* 240 B */
+
+/* reference_dict[obj] (:675): host pointer, copied; may be called again at any time.  PFT_ERR_INVALID_ARG for n == 0, a
+ * non-finite coordinate, or a sharded handle (world_size > 1) */
+int pft_set_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n);
+/* enqueues the report on the handle's stream (never synchronises); it reads the representative state on the device, so
+ * it follows the pft_compute calls before it in stream order.  PFT_ERR_STATE before the first pft_compute or without a
+ * report cloud */
+int pft_report(pft_tracker* t);
+/* synchronises and copies the last report out; device-side failures are reported as by pft_get_result */
+int pft_get_report(pft_tracker* t, pft_object_report* out);
+/* tracked_cloud_dict[obj] (:325): the report cloud moved by the last report's transform; *n = its size, up to cap copied */
+int pft_get_tracked_cloud(pft_tracker* t, pft_point_xyzrgba* out, size_t cap, size_t* n);
+
 /* ---- multi-GPU phase API (one handle per rank; the collectives between the phases are issued by
  *      the host layer on the same stream, see pcl_tracking_amd/dist.py and DESIGN.md) ----
  * The host layer owns three device buffers and binds them once:

@@ -41,6 +41,16 @@ class Config(C.Structure):
     ]
 
 
+class ObjectReport(C.Structure):
+    """pft_object_report (include/pft.h): drawResult + viz_cb of one object, 240 bytes"""
+    _fields_ = [
+        ("transform", C.c_float * 16), ("centroid", C.c_float * 4), ("covariance", C.c_float * 9),
+        ("eigenvalues", C.c_float * 3), ("axes", C.c_float * 9), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+        ("box_centre", C.c_float * 3), ("box_quat", C.c_float * 4), ("box_size", C.c_float * 3),
+        ("n_points", C.c_uint32), ("info", C.c_uint32), ("pad", C.c_uint32 * 1),
+    ]
+
+
 class FilterConfig(C.Structure):
     """pft_filter_config (include/pft_filters.h)"""
     _fields_ = [
@@ -137,6 +147,10 @@ SYMBOLS = [
     ("pft_get_change_detector", C.c_int, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_int), _P(_f64)]),
     ("pft_debug_change_state", C.c_int, [_vp, C.c_int, _P(_u32), _P(_u32), _vp, _P(_i32), _vp, _P(_u32)]),
     ("pft_debug_change_detect", C.c_int, [_vp, _vp, _sz, C.c_int, _f64, C.c_int, _vp, _sz, _P(_sz)]),
+    ("pft_set_report_cloud", C.c_int, [_vp, _vp, _sz]),
+    ("pft_report", C.c_int, [_vp]),
+    ("pft_get_report", C.c_int, [_vp, _P(ObjectReport)]),
+    ("pft_get_tracked_cloud", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_kld_normal_quantile", _f64, [_f64]),
     ("pft_kld_bound", _f64, [C.c_int, _f64, _f64]),
     ("pft_profile_enable", C.c_int, [_vp, C.c_int]),

@@ -133,6 +133,14 @@ struct pft_tracker {
   bool sv_cd_valid = false;
   uint32_t sv_cd_counter = 0;
 
+  // object report (pft_set_report_cloud / pft_report): the report cloud, its tracked copy and the report itself
+  pft_point_xyzrgba* d_rep_pts = nullptr;
+  pft_point_xyzrgba* d_rep_tracked = nullptr;
+  pft_object_report* d_report = nullptr;
+  uint32_t rep_n = 0, rep_cap = 0;
+  uint32_t rep_tracked_n = 0;  // points of the tracked cloud the last pft_report wrote (0: none, or the buffer was replaced)
+  bool rep_issued = false;     // a pft_report has been enqueued: d_report holds (or will hold) its result
+
   // state
   bool has_ref = false, has_input = false, initialized = false, changed = false;
   uint32_t resample_epoch = 0;
@@ -680,6 +688,7 @@ extern "C" void pft_destroy(pft_tracker* t) {
   dfree(t->d_dbg_hdr); dfree(t->d_dbg_f);
   dfree(t->sv_part); dfree(t->sv_alias_list); dfree(t->sv_alias_pref); dfree(t->sv_alias_pos); dfree(t->sv_hdr);
   cd_free(t->cd); cd_free(t->cd_dbg);
+  dfree(t->d_rep_pts); dfree(t->d_rep_tracked); dfree(t->d_report);
   dfree(t->sv_cd); dfree(t->sv_cd_key[0]); dfree(t->sv_cd_key[1]); dfree(t->sv_cd_cnt[0]); dfree(t->sv_cd_cnt[1]);
   if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
   delete t;
@@ -1862,5 +1871,83 @@ extern "C" int pft_debug_change_detect(pft_tracker* t, const pft_point_xyzrgba* 
       k++;
     }
   if (n_new) *n_new = k;
+  return check_device_error(t);
+}
+
+// ---- object report (pft_report.hip) ----
+extern "C" int pft_set_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size != 1) {
+    t->err = "the object report is not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (!pts || n == 0) {
+    t->err = "pft_set_report_cloud: empty report cloud";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
+  for (size_t i = 0; i < n; i++)  // the reference's cloud went through removeZeroPoints
+    if (!std::isfinite(pts[i].x) || !std::isfinite(pts[i].y) || !std::isfinite(pts[i].z)) {
+      t->err = "pft_set_report_cloud: point " + std::to_string(i) + " has a non-finite coordinate";
+      return PFT_ERR_INVALID_ARG;
+    }
+  hipSetDevice(t->cfg.device_id);
+  HIPCHK(t, hipStreamSynchronize(t->stream));  // a report in flight may still read the previous cloud
+  if (!t->d_report) HIPCHK(t, dalloc(&t->d_report, 1));
+  if (n > t->rep_cap) {
+    dfree(t->d_rep_pts);
+    dfree(t->d_rep_tracked);
+    t->rep_cap = 0;
+    t->rep_tracked_n = 0;
+    HIPCHK(t, dalloc(&t->d_rep_pts, n));
+    HIPCHK(t, dalloc(&t->d_rep_tracked, n));
+    t->rep_cap = (uint32_t)n;
+  }
+  HIPCHK(t, hipMemcpyAsync(t->d_rep_pts, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  t->rep_n = (uint32_t)n;
+  return PFT_OK;
+}
+
+extern "C" int pft_report(pft_tracker* t) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!t->initialized) {
+    t->err = "pft_report before the first pft_compute: there is no result yet";
+    return PFT_ERR_STATE;
+  }
+  if (!t->rep_n) {
+    t->err = "pft_report without a report cloud (pft_set_report_cloud)";
+    return PFT_ERR_STATE;
+  }
+  hipSetDevice(t->cfg.device_id);
+  pftk_report(t->stream, t->d_rep_pts, t->rep_n, t->d_hdr, t->prm.sum_order, t->d_rep_tracked, t->d_report);
+  HIPCHK(t, hipGetLastError());
+  t->rep_issued = true;
+  t->rep_tracked_n = t->rep_n;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_report(pft_tracker* t, pft_object_report* out) {
+  if (!t || !out) return PFT_ERR_INVALID_ARG;
+  if (!t->rep_issued) {
+    t->err = "pft_get_report before the first pft_report";
+    return PFT_ERR_STATE;
+  }
+  HIPCHK(t, hipMemcpyAsync(out, t->d_report, sizeof(pft_object_report), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  return check_device_error(t);
+}
+
+extern "C" int pft_get_tracked_cloud(pft_tracker* t, pft_point_xyzrgba* out, size_t cap, size_t* n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!t->rep_issued || !t->rep_tracked_n) {
+    t->err = "pft_get_tracked_cloud: no tracked cloud (no pft_report since the report cloud last grew)";
+    return PFT_ERR_STATE;
+  }
+  if (n) *n = t->rep_tracked_n;
+  if (!out) return PFT_OK;
+  const size_t c = cap < t->rep_tracked_n ? cap : t->rep_tracked_n;
+  HIPCHK(t, hipMemcpyAsync(out, t->d_rep_tracked, c * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
   return check_device_error(t);
 }

@@ -245,6 +245,9 @@ void pftk_change_detect(hipStream_t s, const PftChangeBufs& b, const float4* pts
                         const PftChangeArgs& a, uint32_t* host_stat);
 
 // launchers
+// the object report (pft_report.hip): one workgroup reads hdr->rep, writes the tracked cloud and the report
+void pftk_report(hipStream_t s, const pft_point_xyzrgba* pts, uint32_t n, const PftHeader* hdr, int sum_order,
+                 pft_point_xyzrgba* tracked, pft_object_report* out);
 void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, int argorder, float4* xyz,
                          float4* hsv);
 void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out);

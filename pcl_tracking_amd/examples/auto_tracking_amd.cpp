@@ -4,7 +4,7 @@
 // drawResult / viz_cb do with each pose (:300-326, :432-466).  The shared steps live in tracking_app.hpp.
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
-//                     [--model-leaf L]
+//                     [--model-leaf L] [--device-report]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
 // *.pcd = PCD v0.7 ascii / binary / binary_compressed with fields x y z rgba (what create_model.cpp:219-222 writes);
@@ -12,7 +12,9 @@
 // camera frame.  Without --raw the frames are already filtered and downsampled; with --raw they are sensor frames and
 // go through cloud_cb's front end first (:637 filterPassThrough, :683 gridSampleApprox) on the device, the result
 // staying in HBM for all the trackers.  Every object is an independent handle on its own HIP stream: the loop below
-// enqueues all of them before it reads any result, so they overlap on the GPU.
+// enqueues all of them before it reads any result, so they overlap on the GPU.  --device-report moves drawResult / viz_cb to
+// the device as well (pft_report after each compute, still before any result is read): the object line then takes its
+// centroid from the report, and a `box` line follows with viz_cb's principal-axis box.
 #include <cstdlib>
 
 #include "tracking_app.hpp"
@@ -27,6 +29,7 @@ int main(int argc, char** argv) {
     if (!std::strcmp(argv[i], "--raw")) raw = true;
     else if (!std::strcmp(argv[i], "--kld")) opt.use_fixed = false;
     else if (!std::strcmp(argv[i], "--pcl-sums")) opt.pcl_sums = true;
+    else if (!std::strcmp(argv[i], "--device-report")) opt.device_report = true;
     else if (!std::strncmp(argv[i], "--change-detector", 17) && (argv[i][17] == 0 || argv[i][17] == '=')) {
       opt.change_detector = true;  // --change-detector[=interval,min_points,resolution]; PCL's defaults 10,10,0.01
       if (argv[i][17] == '=') {
@@ -52,7 +55,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report]\n", argv[0]);
     return 2;
   }
 
@@ -81,9 +84,16 @@ int main(int argc, char** argv) {
       } catch (int e) {
         std::fprintf(stderr, "Object not recognized (%s)\n", pft_status_string(e));
       }
+      if (opt.device_report) kv.second->computeReport();
     }
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
+      if (opt.device_report) {
+        const pft_object_report rep = kv.second->getReport();
+        printObjectLine(f + 1, kv.first, result, rep.centroid);
+        printBoxLine(f + 1, kv.first, rep);
+        continue;
+      }
       float centroid[4];
       v.objectPosition(kv.first, result, centroid);
       printObjectLine(f + 1, kv.first, result, centroid);

@@ -7,6 +7,7 @@
 //   objectPosition()     drawResult + viz_cb: the full-resolution model moved by the result pose
 //                        (5 mm towards the camera "for better visualization") and its centroid,
 //                        which the node publishes as the object's position                       :300-326, :432-466
+//   --device-report      the same on the device (pft_report), with viz_cb's principal-axis box       :432-466
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -42,6 +43,7 @@ struct Options {
   bool change_detector = false;         // PCL's change detector (setUseChangeDetector) with the three settings below
   unsigned int cd_interval = 10, cd_min_points = 10;
   double cd_resolution = 0.01;
+  bool device_report = false;           // drawResult + viz_cb on the device: setReportCloud / computeReport / getReport
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -176,6 +178,7 @@ class TrackingApp {
       kv.second->setReferenceCloud(transed_ref_downsampled);
       kv.second->setTrans(trans);
       reference_dict[obj_id] = transed_ref;
+      if (opt_.device_report) kv.second->setReportCloud(transed_ref);
       kv.second->setMinIndices((int)ref_cloud->points.size() / 2);
     }
     return true;
@@ -203,6 +206,13 @@ class TrackingApp {
 inline void printObjectLine(size_t frame, int obj_id, const ParticleT& r, const float c[4]) {
   std::printf("frame %zu object %d pose %.9g %.9g %.9g %.9g %.9g %.9g  centroid %.9g %.9g %.9g\n", frame, obj_id, r.x, r.y, r.z,
               r.roll, r.pitch, r.yaw, c[0], c[1], c[2]);
+}
+
+// viz_cb's box (viz.addCube(tfinal, qfinal, size...)) from the device report: centre, quaternion {x, y, z, w}, size
+inline void printBoxLine(size_t frame, int obj_id, const pft_object_report& r) {
+  std::printf("frame %zu object %d box %.9g %.9g %.9g  quat %.9g %.9g %.9g %.9g  size %.9g %.9g %.9g\n", frame, obj_id,
+              r.box_centre[0], r.box_centre[1], r.box_centre[2], r.box_quat[0], r.box_quat[1], r.box_quat[2], r.box_quat[3],
+              r.box_size[0], r.box_size[1], r.box_size[2]);
 }
 
 }  // namespace app

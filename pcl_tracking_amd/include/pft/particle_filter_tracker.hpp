@@ -307,6 +307,37 @@ class ParticleFilterTracker {
     if (handle_) check(pft_get_fit_ratio(handle_, &v), "getFitRatio");
     return v;
   }
+  // ---- object report (drawResult :301-326 + viz_cb :432-470, on the device) ----
+  // reference_dict[obj]: the re-centred, full-resolution model the result pose moves; may be replaced at any time
+  int setReportCloud(const PointCloudInConstPtr& cloud) {
+    report_cloud_ = cloud;
+    if (!handle_ || !report_cloud_) return PFT_OK;
+    return check(pft_set_report_cloud(handle_, report_cloud_->points.data(), report_cloud_->points.size()), "setReportCloud");
+  }
+  // enqueues the report of the last compute() on the tracker's stream; nothing waits
+  int computeReport() {
+    if (!handle_) return check(PFT_ERR_STATE, "computeReport");
+    return check(pft_report(handle_), "computeReport");
+  }
+  // waits for the last computeReport(): transform, centroid, covariance, axes and the principal-axis box
+  pft_object_report getReport() const {
+    pft_object_report r;
+    std::memset(&r, 0, sizeof(r));
+    if (handle_) check(pft_get_report(handle_, &r), "getReport");
+    return r;
+  }
+  // tracked_cloud_dict[obj] (:325): the report cloud moved by the last report's transform
+  void getTrackedCloud(PointCloudIn& cloud) const {
+    cloud.points.clear();
+    size_t n = 0;
+    if (handle_ && check(pft_get_tracked_cloud(handle_, nullptr, 0, &n), "getTrackedCloud") == PFT_OK && n) {
+      cloud.points.resize(n);
+      check(pft_get_tracked_cloud(handle_, cloud.points.data(), n, &n), "getTrackedCloud");
+    }
+    cloud.width = (uint32_t)cloud.points.size();
+    cloud.height = 1;
+  }
+
   int getIterationNum() const { return cfg_.iteration_num; }
   int getParticleNum() const { return cfg_.particle_num; }
   pft_tracker* nativeHandle() { return handle_; }
@@ -361,13 +392,15 @@ class ParticleFilterTracker {
     pft_set_trans(handle_, trans_.m);
     if (use_cd_ || cd_interval_ != 10 || cd_min_points_ != 10 || cd_resolution_ != 0.01) forwardChangeDetector();
     if (ref_) check(pft_set_reference(handle_, ref_->points.data(), ref_->points.size()), "setReferenceCloud");
+    if (report_cloud_)
+      check(pft_set_report_cloud(handle_, report_cloud_->points.data(), report_cloud_->points.size()), "setReportCloud");
     return true;
   }
 
   pft_config cfg_;
   pft_tracker* handle_;
   Affine3f trans_;
-  PointCloudInConstPtr ref_, input_;
+  PointCloudInConstPtr ref_, input_, report_cloud_;
   const pft_point_xyzrgba* dev_input_ = nullptr;
   size_t dev_n_ = 0;
   bool throw_on_failure_ = false;

@@ -3,6 +3,7 @@ meaning as the calls at /root/reference/src/auto_tracking.cpp:201-254, 270, 309-
 implemented over the C ABI of include/pft.h.  All compute runs in the HIP library; nothing here
 computes on the CPU."""
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -27,6 +28,35 @@ def decode_likelihood_layout(out4):
     return dict(valid=bool(w & 1), layout=LIK_LAYOUTS[(w >> 1) & 3], descent=LIK_DESCENTS[min((w >> 3) & 3, 2)],
                 indirect=bool(w & 32), leaf_indirect=bool(w & 64), jump_dropped=bool(w & 128), J=(w >> 8) & 15,
                 n_lds_words=int(out4[1]), lds_bytes=int(out4[2]), margin_cells=float(np.uint32(out4[3]).view(np.float32)))
+
+
+@dataclass
+class ObjectReport:
+    """pft_object_report as NumPy arrays (float32): what drawResult and viz_cb compute from one result"""
+    transform: np.ndarray    # 4x4, the pose's matrix with T[2][3] += -0.005f
+    centroid: np.ndarray     # 4, [3] = 1
+    covariance: np.ndarray   # 3x3
+    eigenvalues: np.ndarray  # 3, ascending
+    axes: np.ndarray         # 3x3, the eigenvectors as columns, col 2 = col 0 x col 1
+    box_min: np.ndarray      # 3, in the principal frame
+    box_max: np.ndarray
+    box_centre: np.ndarray   # 3, viz_cb's tfinal
+    box_quat: np.ndarray     # 4, viz_cb's qfinal as (x, y, z, w)
+    box_size: np.ndarray     # 3
+    n_points: int
+    info: int                # 0 success, 1 the eigen solver did not converge
+
+    FIELDS = ("transform", "centroid", "covariance", "eigenvalues", "axes", "box_min", "box_max", "box_centre", "box_quat",
+              "box_size")
+
+    @classmethod
+    def from_struct(cls, r):
+        shapes = {"transform": (4, 4), "covariance": (3, 3), "axes": (3, 3)}
+        kw = {}
+        for f in cls.FIELDS:
+            a = np.array(getattr(r, f), dtype=np.float32)
+            kw[f] = a.reshape(shapes[f]) if f in shapes else a
+        return cls(n_points=int(r.n_points), info=int(r.info), **kw)
 
 
 class DistanceCoherence:
@@ -112,6 +142,7 @@ class ParticleFilterTracker:
         self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
         self._ref = None
+        self._report_cloud = None
         self._keep = None
         self.threads = threads  # OpenMP thread count of the reference; meaningless on the GPU
 
@@ -244,6 +275,8 @@ class ParticleFilterTracker:
                 self._forward_change_detector()
             if self._ref is not None:
                 self._check(self._L.pft_set_reference(self._h, _ptr(self._ref), len(self._ref)))
+            if self._report_cloud is not None:
+                self._check(self._L.pft_set_report_cloud(self._h, _ptr(self._report_cloud), len(self._report_cloud)))
 
     def close(self):
         if self._h is not None:
@@ -303,6 +336,38 @@ class ParticleFilterTracker:
         v = C.c_double()
         self._check(self._L.pft_get_fit_ratio(self._h, C.byref(v)))
         return v.value
+
+    # ---- object report (drawResult + viz_cb on the device) ----
+    def setReportCloud(self, cloud):
+        """reference_dict[obj]: the re-centred, full-resolution model the result pose moves (copied; may be replaced)"""
+        self._report_cloud = np.ascontiguousarray(cloud, POINT_DTYPE)
+        if self._h is not None:
+            self._check(self._L.pft_set_report_cloud(self._h, _ptr(self._report_cloud), len(self._report_cloud)))
+
+    def computeReport(self):
+        """enqueues the report of the last compute() on the tracker's stream; nothing waits"""
+        if self._h is None:
+            raise PftError(7, "computeReport before the first compute()")
+        self._check(self._L.pft_report(self._h))
+
+    def getReport(self):
+        """waits for the last computeReport(); returns ObjectReport (float32 arrays: transform 4x4, centroid 4,
+        covariance 3x3, eigenvalues 3, axes 3x3, box_min / box_max / box_centre / box_size 3, box_quat 4 (x, y, z, w))"""
+        if self._h is None:
+            raise PftError(7, "getReport before the first compute()")
+        r = _lib.ObjectReport()
+        self._check(self._L.pft_get_report(self._h, C.byref(r)))
+        return ObjectReport.from_struct(r)
+
+    def getTrackedCloud(self):
+        """tracked_cloud_dict[obj]: the report cloud moved by the last report's transform"""
+        if self._h is None:
+            raise PftError(7, "getTrackedCloud before the first compute()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_tracked_cloud(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, POINT_DTYPE)
+        self._check(self._L.pft_get_tracked_cloud(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     # ---- test hooks (stage-level parity against the oracle) ----
     def setParticles(self, p):
