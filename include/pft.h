@@ -267,8 +267,8 @@ int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4]);
 int pft_debug_aabb_support_subset(const pft_point_xyzrgba* pts, size_t n, uint32_t* keep, size_t* n_keep);
 #ifdef PFT_DIAG
 /* diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG; never in libpft_hip.so): skip stages of the
- * likelihood kernel for timing (bit0 generic levels, bit1 leaf scan, bit2 coherence); results are wrong while set */
-void pft_debug_set_ablate(int mask);
+ * handle's likelihood kernel for timing (bit0 generic levels, bit1 leaf scan, bit2 coherence); results are wrong while set */
+void pft_debug_set_ablate(pft_tracker* t, int mask);
 #endif
 /* diagnostic: resident likelihood workgroups per CU according to the HIP occupancy API */
 int pft_debug_likelihood_occupancy(void);

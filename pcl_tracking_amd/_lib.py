@@ -188,7 +188,7 @@ SYMBOLS = [
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present
 DIAG_SYMBOLS = [
-    ("pft_debug_set_ablate", None, [C.c_int]),
+    ("pft_debug_set_ablate", None, [_vp, C.c_int]),
 ]
 
 _lib = None

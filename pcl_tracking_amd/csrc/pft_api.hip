@@ -70,7 +70,8 @@ struct pft_tracker {
   unsigned long long* d_pt_key64 = nullptr;
   SortBufs sort = {};
   uint32_t* h_stat = nullptr;   // pinned, device-visible
-  int force_builder = 0;        // PFT_FORCE_BUILDER: 1 single workgroup, 2 sorted
+  PftSwitches sw = {};          // the path switches, read once by pft_create
+  bool leaf_indirect = false;   // leaf-record form of the last tree built (PftSwitches::leaf_indirect and the size rule)
   int force_npass = 0;          // test hook (pft_debug_set_limits): radix passes of the sorted builder, 0 = from the last depth
   uint32_t inject_error = 0;    // test hook (pft_debug_inject_error): bits OR-ed into PftHeader::error after the next crop
   double* d_partial = nullptr;
@@ -527,6 +528,32 @@ static int cd_reserve(pft_tracker* t, CdInst& c, uint32_t cap, bool debug) {
   return PFT_OK;
 }
 
+// the only reader of the environment: a switch changed later affects the handles created after the change
+PftSwitches pft_read_switches() {
+  auto on = [](const char* name) { return getenv(name) != nullptr; };
+  auto is1 = [](const char* name) { const char* e = getenv(name); return e && e[0] == '1'; };
+  PftSwitches w = {};
+  w.graph = is1("PFT_GRAPH");
+  if (const char* b = getenv("PFT_FORCE_BUILDER")) w.builder = !strcmp(b, "single") ? 1 : (!strcmp(b, "sorted") ? 2 : 0);
+  w.leaf_indirect = on("PFT_LEAF_INDIRECT") ? (int)is1("PFT_LEAF_INDIRECT") : -1;
+  w.aabb_full = on("PFT_AABB_FULL");
+  w.resample_one_lane = on("PFT_RESAMPLE_ONE_LANE");
+  w.split_resample = on("PFT_SPLIT_RESAMPLE") || w.resample_one_lane;  // (the one-lane kernel is a resample of its own)
+  w.crop_two_pass = on("PFT_CROP_TWO_PASS");
+  w.generic_descent = is1("PFT_GENERIC_DESCENT");
+  w.exact_path = on("PFT_EXACT_SHELLS_ONLY") ? PftExactPath::shells : on("PFT_EXACT_PER_QUERY") ? PftExactPath::per_query : PftExactPath::sorted;
+#ifdef PFT_DIAG
+  if (const char* a = getenv("PFT_ABLATE")) w.ablate = atoi(a);  // bit0 generic levels, bit1 leaf scan, bit2 coherence
+  w.skip_octree = on("PFT_DEBUG_SKIP_OCTREE");
+#endif
+  return w;
+}
+
+#ifdef PFT_DIAG
+// timing experiments only (tools/lik_microbench.py): the handle's stage ablation mask.  Not in the product library.
+extern "C" void pft_debug_set_ablate(pft_tracker* t, int mask) { if (t) t->sw.ablate = mask; }
+#endif
+
 extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   if (!cfg || !out) return PFT_ERR_INVALID_ARG;
   *out = nullptr;
@@ -562,10 +589,8 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
     t->own_stream = true;
   }
   for (int i = 0; i < 16; i++) t->trans[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-  {
-    const char* ge = getenv("PFT_GRAPH");
-    t->use_graph = ge && ge[0] == '1' && t->own_stream;
-  }
+  t->sw = pft_read_switches();
+  t->use_graph = t->sw.graph && t->own_stream;
 
   PftParams& p = t->prm;
   memset(&p, 0, sizeof(p));
@@ -639,10 +664,6 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   }
   A(hipHostMalloc(reinterpret_cast<void**>(&t->h_stat), 8 * sizeof(uint32_t), hipHostMallocMapped));
   if (t->h_stat) for (int i = 0; i < 8; i++) t->h_stat[i] = 0;  // [0..3]: pft_debug_get_host_stat; [4]: exact-NN pool demand
-  {
-    const char* fb = getenv("PFT_FORCE_BUILDER");
-    t->force_builder = fb ? (!strcmp(fb, "single") ? 1 : (!strcmp(fb, "sorted") ? 2 : 0)) : 0;
-  }
   A(dalloc(&t->d_hdr, 1));
   A(dalloc(&t->d_dbg_hdr, 1));
   if (e == hipSuccess) e = hipMemsetAsync(t->d_hdr, 0, sizeof(PftHeader), t->stream);
@@ -786,7 +807,7 @@ extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, s
     // A3's input: the points that can be extreme in some rigidly transformed coordinate (the hull's vertices and what lies
     // within the float evaluation's reach of its facets); PFT_AABB_FULL=1 keeps every point (cross-check, A/B timing)
     std::vector<uint32_t> keep;
-    if (getenv("PFT_AABB_FULL")) {
+    if (t->sw.aabb_full) {
       keep.resize(n);
       for (size_t i = 0; i < n; i++) keep[i] = (uint32_t)i;
     } else {
@@ -867,7 +888,7 @@ static void stage_resample(pft_tracker* t) {
     if (t->prm.kld)
       pftk_resample_kld(t->stream, t->prm, t->dev, t->resample_epoch, out, nullptr, nullptr, nullptr);
     else
-      pftk_resample(t->stream, t->prm, t->dev, t->resample_epoch, out);
+      pftk_resample(t->stream, t->prm, t->dev, t->resample_epoch, out, t->sw.resample_one_lane);
   }
   t->resample_epoch++;
   t->cur = 1 - t->cur;
@@ -884,9 +905,7 @@ static void stage_aabb(pft_tracker* t, const PftDev& d, uint32_t np, bool finali
 // (cross-check -- identical bits --, A/B timing).  The KLD variant, whose resample is a grid-wide loop of its own, and the
 // first iteration after pft_set_particles / init take the separate kernels.
 static void stage_resample_aabb(pft_tracker* t, bool finalize) {
-  // (read per call, not latched: tests/test_gpu_parity.py toggles them inside one process)
-  const bool split = getenv("PFT_SPLIT_RESAMPLE") != nullptr || getenv("PFT_RESAMPLE_ONE_LANE") != nullptr;
-  if (!t->prm.kld && t->changed && !split) {
+  if (!t->prm.kld && t->changed && !t->sw.split_resample) {
     sync_dev(t);
     uint32_t nparts;
     {
@@ -914,7 +933,7 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
   {
     ProfScope ps(t, PFT_K_CROP);
     if (++t->crop_epoch == 0) t->crop_epoch = 1;
-    pftk_crop(t->stream, t->prm, d, bbox_from_partials, t->crop_epoch, t->raw_pending);
+    pftk_crop(t->stream, t->prm, d, bbox_from_partials, t->crop_epoch, t->raw_pending, t->sw.crop_two_pass);
     t->raw_pending = nullptr;
     if (t->inject_error & ~16u) {  // test hook: what a failing crop / builder would leave behind (bit 4 belongs to the
                                    // population launch: pft_compute raises it there)
@@ -994,10 +1013,9 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
       pftk_exact_grid(t->stream, t->prm, dq);  // (dq: the copy that carries the current candidate pool)
     }
     ProfScope ps(t, PFT_K_LIKELIHOOD);
-    pftk_likelihood_exact(t->stream, t->prm, dq, np, debug_nn, t->num_cus);
+    pftk_likelihood_exact(t->stream, t->prm, dq, np, debug_nn, t->num_cus, t->sw.exact_path);
     return;
   }
-  bool leaf_indirect = false;  // (the sorted builder and the rescue launch behind it always write the leaf records)
   {
     ProfScope ps(t, PFT_K_OCTREE);
     PftDev db = d;
@@ -1008,13 +1026,12 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
     const volatile uint32_t* hs = t->h_stat;
     const uint32_t last_n = hs ? hs[0] : 0u, last_depth = hs ? hs[1] : 0u;
     bool sorted = last_n > PFT_SORTED_BUILD_MIN;
-    if (t->force_builder == 1) sorted = false;
-    if (t->force_builder == 2) sorted = true;
+    if (t->sw.builder == 1) sorted = false;
+    if (t->sw.builder == 2) sorted = true;
 #ifdef PFT_DIAG
     // diagnostic build only (results are wrong while set): PFT_DEBUG_SKIP_OCTREE=1 reuses the tree of the
     // previous build after the first 8 builds, to measure the builder's true share of a frame
-    static const bool skip_env = getenv("PFT_DEBUG_SKIP_OCTREE") != nullptr;
-    if (skip_env && ++t->dbg_builds > 8) {
+    if (t->sw.skip_octree && ++t->dbg_builds > 8) {
     } else
 #endif
     if (sorted) {
@@ -1026,16 +1043,19 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
       if (t->force_npass > 0) npass = t->force_npass;
       if (npass > 8) npass = 8;
       pftk_octree_sorted(t->stream, t->prm, db, t->sort, d.N, npass);
-    }
-    else
+      t->leaf_indirect = false;  // (the sorted builder and the rescue launch behind it always write the leaf records)
+    } else {
       // leaf records followed through leaf_order by the likelihood kernel instead of being copied: +0.32 ps per query
       // there (5.4 us at 8 192 x 2 048), -3 us per build and one launch less here: pays below ~9 million queries (the
       // reference's own 400-500 particles: 0.202 -> 0.196 ms per frame)
-      leaf_indirect = pftk_octree(t->stream, t->prm, db, last_n, (unsigned long long)np * t->prm.M <= 8000000ull);
+      t->leaf_indirect = t->sw.leaf_indirect >= 0 ? t->sw.leaf_indirect == 1 : (unsigned long long)np * t->prm.M <= 8000000ull;
+      pftk_octree(t->stream, t->prm, db, last_n, t->leaf_indirect);
+    }
   }
   {
     ProfScope ps(t, PFT_K_LIKELIHOOD);
-    pftk_likelihood(t->stream, t->prm, d, np, debug_nn, t->num_cus, leaf_indirect);
+    const int flags = (t->sw.generic_descent ? 0 : 1) | (t->sw.ablate << 8);
+    pftk_likelihood(t->stream, t->prm, d, np, debug_nn, t->num_cus, t->leaf_indirect, flags);
   }
 }
 

@@ -986,10 +986,9 @@ __global__ __launch_bounds__(256) void k_eq_reduce(PftParams prm, PftDev d, uint
 }
 
 void pftk_likelihood_exact(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
-                           int num_cus) {
-  const int use_lists = getenv("PFT_EXACT_SHELLS_ONLY") ? 0 : 1;  // 0: the per-query shell search alone (cross-check, A/B timing)
-  // 1: a list walk per lane instead of the cell-sorted search (cross-check -- identical bits --, A/B timing)
-  const bool per_query = getenv("PFT_EXACT_PER_QUERY") != nullptr;
+                           int num_cus, PftExactPath path) {
+  const int use_lists = path != PftExactPath::shells;  // 0: the per-query shell search alone (cross-check, A/B timing)
+  const bool per_query = path == PftExactPath::per_query;  // a list walk per lane (identical bits to the cell-sorted search)
   const uint32_t items = n_particles * p.nchunk;
   uint32_t grid = 8u * (uint32_t)num_cus;
   const uint32_t need = (items + 3u) / 4u;

@@ -1059,8 +1059,7 @@ static int run_pipeline(pft_filter* f, const pft_point_xyzrgba* d_in, size_t n) 
     while ((1u << bits) < nb) bits++;
     hipLaunchKernelGGL(k_fa_classify, dim3(ntiles), dim3(F_THREADS), 0, s, p, d, ntiles);
     hipLaunchKernelGGL(k_f_rs_scan, dim3(nb), dim3(F_THREADS), 0, s, d.hist, ntiles, nb);
-    static const bool one_wave_scatter = getenv("PFT_FILTER_SCATTER1") != nullptr;  // A/B timing only
-    if (nb <= FS_MAXB && !one_wave_scatter)
+    if (nb <= FS_MAXB)
       hipLaunchKernelGGL(k_fa_scatter4, dim3(ntiles), dim3(F_THREADS), 0, s, p, d, ntiles, bits);
     else
       hipLaunchKernelGGL(k_fa_scatter, dim3(ntiles), dim3(64), 0, s, p, d, ntiles, bits);

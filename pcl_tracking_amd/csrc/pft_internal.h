@@ -244,6 +244,24 @@ struct PftChangeArgs {
 void pftk_change_detect(hipStream_t s, const PftChangeBufs& b, const float4* pts, const uint32_t* n_ptr, uint32_t n,
                         const PftChangeArgs& a, uint32_t* host_stat);
 
+// The result-neutral path switches (A/B timing and cross-checks; README "Environment switches").  pft_create reads them
+// once, with pft_read_switches, and keeps them on the handle: the launchers take the decisions as plain arguments.
+enum class PftExactPath { sorted, per_query, shells };  // exact-NN search: cell-sorted lists, lists per query, shells only
+struct PftSwitches {
+  bool graph;             // PFT_GRAPH=1: steady-state frames replayed as one hipGraph (handles with their own stream)
+  int builder;            // PFT_FORCE_BUILDER: 0 by the last crop size, 1 single workgroup ("single"), 2 sorted ("sorted")
+  int leaf_indirect;      // PFT_LEAF_INDIRECT: -1 by the launch size, 0 leaf records copied, 1 followed through leaf_order
+  bool aabb_full;         // PFT_AABB_FULL: the box over every reference point instead of the hull shell
+  bool split_resample;    // PFT_SPLIT_RESAMPLE or PFT_RESAMPLE_ONE_LANE: resample and box as separate launches
+  bool resample_one_lane; // PFT_RESAMPLE_ONE_LANE: the one-lane-per-particle resample kernel instead of the four-lane one
+  bool crop_two_pass;     // PFT_CROP_TWO_PASS: the crop as a count + a scatter launch instead of the one-pass kernel
+  bool generic_descent;   // PFT_GENERIC_DESCENT=1: every octree level by the exact 8-way selection
+  PftExactPath exact_path;  // PFT_EXACT_SHELLS_ONLY, else PFT_EXACT_PER_QUERY, else the cell-sorted search
+  int ablate;             // diagnostic build only: PFT_ABLATE, or pft_debug_set_ablate (results are wrong while set)
+  bool skip_octree;       // diagnostic build only: PFT_DEBUG_SKIP_OCTREE (results are wrong while set)
+};
+PftSwitches pft_read_switches();
+
 // launchers
 // the object report (pft_report.hip): one workgroup reads hdr->rep, writes the tracked cloud and the report
 void pftk_report(hipStream_t s, const pft_point_xyzrgba* pts, uint32_t n, const PftHeader* hdr, int sum_order,
@@ -253,7 +271,7 @@ void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t
 void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out);
 void pftk_init_particles(hipStream_t s, const PftParams& p, pft_particle rep, pft_particle* out, float* mats,
                          PftHeader* hdr);
-void pftk_resample(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out);
+void pftk_resample(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out, bool one_lane);
 void pftk_bbox_final(hipStream_t s, const PftDev& d);
 uint32_t pftk_resample_box(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out);
 // debug: resample from an explicit (a, q) table instead of the prefix-sum form
@@ -265,7 +283,7 @@ void pft_aabb_support_subset(const pft_point_xyzrgba* pts, size_t n, std::vector
 // NearestPairPointCloudCoherence mode: uniform grid over the cropped cloud, then the likelihood with the true NN
 void pftk_exact_grid(hipStream_t s, const PftParams& p, const PftDev& d);
 void pftk_likelihood_exact(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
-                           int num_cus);
+                           int num_cus, PftExactPath path);
 // KLD variant: draws up to p.kld_max candidates from d.part_all[0 .. p_active) (alias prefix form, or the explicit
 // table a/q when given), keeps the prefix the KL bound asks for, writes particles + matrices and the new p_active
 void pftk_resample_kld(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out,
@@ -273,9 +291,9 @@ void pftk_resample_kld(hipStream_t s, const PftParams& p, const PftDev& d, uint3
 // epoch: a value that differs from the handle's previous crop launch (non-zero); tags the per-workgroup counts of the one-pass crop
 // raw: the input in PCL's 32-byte layout when its 16-byte records have not been formed yet (first crop of a frame), else null
 void pftk_crop(hipStream_t s, const PftParams& p, const PftDev& d, bool bbox_from_partials, uint32_t epoch,
-               const pft_point_xyzrgba* raw);
-// returns true when the leaf records were left for the likelihood kernel to follow through leaf_order (its INDIRECT form)
-bool pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool allow_indirect = true);
+               const pft_point_xyzrgba* raw, bool two_pass);
+// the single-workgroup builder; indirect: no leaf_pts copies, the likelihood kernel follows leaf_order (its INDIRECT form)
+void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect);
 // no-op launch unless the sorted builder flagged "radix passes too few" (error bit 3): then the single-workgroup build
 void pftk_octree_rescue(hipStream_t s, const PftParams& p, const PftDev& d);
 struct SortBufs {
@@ -289,8 +307,9 @@ struct SortBufs {
 // many-workgroup builder for large cropped clouds (pft_octree_sorted.hip); npass = 4 (depth <= 10) or 8
 void pftk_octree_sorted(hipStream_t s, const PftParams& p, const PftDev& d, const SortBufs& sb, uint32_t n_pad,
                         int npass);
+// flags (k_likelihood's argument): bit 0 fast descent allowed, bits 8+ the stage ablation mask of the diagnostic build
 void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
-                     int num_cus, bool leaf_indirect = false);
+                     int num_cus, bool leaf_indirect, int flags);
 // shard (nullable): sharded handles -- the particles with their raw weights also go into the all-gather's send buffer
 void pftk_finalize_raw(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles,
                        float* raw_out /*nullable*/, pft_particle* shard /*nullable*/);

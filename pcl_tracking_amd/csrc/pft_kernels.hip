@@ -624,8 +624,7 @@ static AliasView alias_view(const PftDev& d, uint32_t n) {
   v.n = n;
   return v;
 }
-void pftk_resample(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out) {
-  const bool one_lane = getenv("PFT_RESAMPLE_ONE_LANE") != nullptr;  // A/B and cross-check: the one-lane-per-particle kernel (read per call)
+void pftk_resample(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out, bool one_lane) {
   if (one_lane)
     hipLaunchKernelGGL(k_resample<false>, dim3(cdiv(p.P_local, 256)), dim3(256), 0, s, p, d.part_all,
                        alias_view(d, p.P_total), (const int32_t*)nullptr, (const double*)nullptr, d.hdr, epoch, out,
@@ -678,9 +677,8 @@ void pftk_bbox_final(hipStream_t s, const PftDev& d) {
   hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(512), 0, s, d.bbox_part, d.bbox_grid, d.bbox6);
 }
 void pftk_crop(hipStream_t s, const PftParams& p, const PftDev& d, bool from_part, uint32_t epoch,
-               const pft_point_xyzrgba* raw) {
+               const pft_point_xyzrgba* raw, bool two_pass) {
   uint32_t nb = cdiv(d.N ? d.N : 1, 1024);
-  const bool two_pass = getenv("PFT_CROP_TWO_PASS") != nullptr;  // A/B timing and cross-check (read per call: tests toggle it)
   float4* packed = const_cast<float4*>(d.in_pts);
   if (!two_pass) {
     if (from_part)

@@ -430,15 +430,8 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
   }
 }
 
-#ifndef PFT_LIK_REFILL
-#define PFT_LIK_REFILL 0  // 1: the while-while work item of pft_likelihood_refill.h (measured experiment, not the product)
-#endif
-#if PFT_LIK_REFILL
-#include "pft_likelihood_refill.h"
-#endif
-
-// INDIRECT is a parameter of the KERNEL (the host launches the instantiation that matches the builder mode it chose:
-// pftk_octree returns it): both forms inside one kernel doubled its code and its scalar-register spills (76 -> 136) and
+// INDIRECT is a parameter of the KERNEL (the host decides the leaf-record form once per build and passes it to the builder
+// and to this launch): both forms inside one kernel doubled its code and its scalar-register spills (76 -> 136) and
 // cost the headline launch 2 %
 #define PFT_LIK_RUN(UT, FA, LF) likelihood_items<UT, FA, DEBUG_NN, LF, INDIRECT>(prm, d, cx, W, n_particles, D, n_crop, omin, abl)
 
@@ -581,11 +574,7 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
   } else if (words_in_lds && leaf16) {  // node words addressed as LDS (ds_read), not through a generic pointer
     const uint32_t* W = lwords;
     if (fast)
-#if PFT_LIK_REFILL
-      likelihood_items_refill<DEBUG_NN>(prm, d, cx, W, n_particles, D, n_crop);
-#else
       PFT_LIK_RUN(true, true, 1);
-#endif
     else if (use_tab)
       PFT_LIK_RUN(true, false, 1);
     else
@@ -612,8 +601,6 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
   }
 }
 
-static int g_allow_fast = -1;
-
 // diagnostic: resident workgroups per CU the runtime reports for the production likelihood kernel
 extern "C" int pft_debug_likelihood_occupancy(void) {
   int nb = -1;
@@ -623,17 +610,8 @@ extern "C" int pft_debug_likelihood_occupancy(void) {
   return nb;
 }
 
-#ifdef PFT_DIAG
-// timing experiments only (tools/lik_microbench.py with the diagnostic variant library): bit0 generic levels, bit1 leaf
-// scan, bit2 coherence.  Not compiled into the product library.
-extern "C" void pft_debug_set_ablate(int mask) {
-  if (g_allow_fast < 0) g_allow_fast = 1;
-  g_allow_fast = (g_allow_fast & 0xff) | (mask << 8);
-}
-#endif
-
 void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
-                     int num_cus, bool leaf_indirect) {
+                     int num_cus, bool leaf_indirect, int flags) {
   static bool attr_set[PFT_MAX_DEVICES];
   // half of the CU's LDS per workgroup: two 1024-thread workgroups (32 waves, 8 per SIMD) are resident per CU
   uint32_t lds = ((uint32_t)pftk_max_lds_bytes() / (uint32_t)PFT_LIK_WGS_PER_CU) & ~255u;
@@ -648,15 +626,6 @@ void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
     for (int k = 0; k < 8; k++) ok = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess && ok;
     attr_set[dev] = ok;
   }
-  {  // PFT_GENERIC_DESCENT=1: all-generic descent (A/B and parity cross-check; read per launch: tools/fuzz_parity.py draws it per case)
-    const char* e = getenv("PFT_GENERIC_DESCENT");
-    if (g_allow_fast < 0) g_allow_fast = 1;
-    g_allow_fast = (g_allow_fast & ~1) | ((e && e[0] == '1') ? 0 : 1);
-#ifdef PFT_DIAG
-    const char* a = getenv("PFT_ABLATE");  // timing experiments only: bit0 generic levels, bit1 leaf scan, bit2 coherence
-    if (a) g_allow_fast |= atoi(a) << 8;
-#endif
-  }
   // (fewer workgroups at small particle counts -- less staging traffic -- was measured: 400 particles 52.2 us per frame with
   // the full grid, 54.9 / 56.2 / 84.2 with 384 / 256 / 128 workgroups)
   uint32_t items = n_particles * p.nchunk;
@@ -669,10 +638,10 @@ void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
   do {                                                                                                                   \
     if (d.gate)                                                                                                          \
       hipLaunchKernelGGL((k_likelihood<DN, IND, true>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
-                         g_allow_fast);                                                                                  \
+                         flags);                                                                                         \
     else                                                                                                                 \
       hipLaunchKernelGGL((k_likelihood<DN, IND, false>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
-                         g_allow_fast);                                                                                  \
+                         flags);                                                                                         \
   } while (0)
   if (debug_nn && leaf_indirect)
     PFT_LIK_LAUNCH(true, true);

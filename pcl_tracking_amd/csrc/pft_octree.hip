@@ -667,19 +667,16 @@ static void pftk_octree_set_attr() {
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
-bool pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool allow_indirect) {
+void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect) {
   // static LDS of the kernel (BuildSh ~2.6 KB, the dense top-level arrays 5 KB): leave 10 KB out of the dynamic request
   const uint32_t lds = ((uint32_t)pftk_max_lds_bytes() - 10240u) & ~15u;
   pftk_octree_set_attr();
   // Who produces the leaf-ordered point records (any choice is correct for any size; the builder records it in the header):
   //   2  nobody: the likelihood kernel reads crop_pts[leaf_order[pos]] -- one more dependent 4-byte load per candidate
   //      (measured +0.32 ps per query: 5.4 us per launch at 8 192 particles x 2 048 points) against a launch of its own
-  //      (4.6 us) or scattered stores by the one builder workgroup; the caller allows it when the launch is small
-  //      (allow_indirect); PFT_LEAF_INDIRECT=0 keeps the copies, =1 forces the indirection (A/B timing, cross-check)
+  //      (4.6 us) or scattered stores by the one builder workgroup; the caller chooses it when the launch is small
   //   1  the builder itself (crops of at most 5 000 points, by the previous iteration's size)
   //   0  k_leaf_gather, a launch of many workgroups
-  const char* e = getenv("PFT_LEAF_INDIRECT");
-  const bool indirect = e ? e[0] == '1' : allow_indirect;
   const int mode = indirect ? 2 : (expected_points <= 5000u ? 1 : 0);
   const dim3 gg((d.N + 255u) / 256u ? (d.N + 255u) / 256u : 1u);
   if (d.gate) {
@@ -690,7 +687,6 @@ bool pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t ex
     // at most PFT_SORTED_BUILD_MIN-ish points reach this builder in practice, but any crop (<= N) is legal
     if (mode == 0) hipLaunchKernelGGL(k_leaf_gather<false>, gg, dim3(256), 0, s, d);
   }
-  return indirect;
 }
 
 // behind the sorted builder: a no-op unless error bit 3 asks for the rebuild (then the whole tree, leaf records included)

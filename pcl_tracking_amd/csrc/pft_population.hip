@@ -674,7 +674,7 @@ __global__ void k_alias_materialize(const pft_particle* __restrict__ P, AliasVie
 #ifndef PFT_POP_WGS
 #define PFT_POP_WGS 128u  // workgroups up to which a thread keeps one particle: at 65 536 particles (the replicated population
                           // of an 8-GPU run) 128 workgroups with two particles per thread take 60.9 us per frame, 256 with one 68.3, 64
-                          // with four 67.1 (tools/diag/pop_wgs.sh; PFT_POP_MAX_WGS overrides)
+                          // with four 67.1 (measured by rebuilding with -DPFT_POP_WGS=64 / 256)
 #endif
 void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n, int from_partials,
                      int do_normalize, int do_mean, int do_alias) {
@@ -692,9 +692,8 @@ void pftk_population(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
   // one particle per thread over G workgroups until G would exceed PFT_POP_WGS (the sums are the same adjacent-pair trees for
   // any K and G).  One workgroup with K particles per thread and no device-scope barrier was tried for the reference's
   // own 400-500 particles: slower (the two workgroups' barriers cost less than a second particle per thread).
-  static const uint32_t max_wgs = getenv("PFT_POP_MAX_WGS") ? (uint32_t)atoi(getenv("PFT_POP_MAX_WGS")) : PFT_POP_WGS;
   uint32_t K = 1;
-  while (K < 16u && (n + PFT_POPC_THREADS * K - 1) / (PFT_POPC_THREADS * K) > max_wgs) K <<= 1;
+  while (K < 16u && (n + PFT_POPC_THREADS * K - 1) / (PFT_POPC_THREADS * K) > PFT_POP_WGS) K <<= 1;
   while ((n + PFT_POPC_THREADS * K - 1) / (PFT_POPC_THREADS * K) > PFT_POPM_MAX_WGS) K <<= 1;  // n <= PFT_MAX_PARTICLES: K <= 16
   uint32_t G = 1;
   while (G * PFT_POPC_THREADS * K < n) G <<= 1;  // a power of two: the workgroups are the upper levels of the sum trees

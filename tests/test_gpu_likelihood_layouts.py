@@ -245,3 +245,25 @@ def test_u16_leaf_start_edges_against_the_oracle(orc, n, indirect, monkeypatch):
     assert len(G["crop_idx"]) == n
     assert (rec["layout"], rec["descent"]) == (EDGES[n], "fast"), rec
     assert len(np.unique(G["nn_idx"])) > 100
+
+
+@pytest.mark.gpu
+def test_switches_are_latched_per_handle(orc, monkeypatch):
+    """a handle keeps the descent and leaf-record form of the environment it was created in: handle A (generic descent,
+    copied records) evaluates again after the switches were cleared and handle B (the defaults) was created"""
+    inputs, res = CASES["u16_fast"][:2]
+    model, cloud, p = inputs()
+    monkeypatch.setenv("PFT_GENERIC_DESCENT", "1")
+    monkeypatch.setenv("PFT_LEAF_INDIRECT", "0")
+    a, _ = make_pair(orc, model, cloud, len(p), res)
+    monkeypatch.delenv("PFT_GENERIC_DESCENT")
+    monkeypatch.delenv("PFT_LEAF_INDIRECT")
+    b, _ = make_pair(orc, model, cloud, len(p), res)
+    runs = [(t, t.evalWeights(p, want_nn=True)) for t in (a, b, a)]
+    for t, G in runs:
+        rec = G["lik_layout"]
+        want = ("table_generic", False) if t is a else ("fast", True)
+        assert rec["valid"] and (rec["descent"], rec["indirect"]) == want, rec
+    raw = [G["raw"].view(np.uint32) for _, G in runs]
+    np.testing.assert_array_equal(raw[0], raw[1])
+    np.testing.assert_array_equal(raw[0], raw[2])

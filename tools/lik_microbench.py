@@ -29,7 +29,7 @@ p = t.getParticles()
 t.profileEnable(True)
 for mask, name in ((0, "full"), (1, "no generic levels"), (2, "no leaf scan"), (4, "no coherence"), (6, "descent only"),
                    (7, "transform+key+fast only")):
-    t._L.pft_debug_set_ablate(mask)
+    t._L.pft_debug_set_ablate(t._h, mask)
     t.evalWeights(p)
     t.profileReset()
     for r in range(reps):
@@ -38,4 +38,4 @@ for mask, name in ((0, "full"), (1, "no generic levels"), (2, "no leaf scan"), (
     print("%-26s likelihood %.1f us   octree %.1f us   aabb %.1f us" % (
         name, pr["likelihood"][0] / pr["likelihood"][1] * 1e3, pr["octree"][0] / pr["octree"][1] * 1e3,
         pr["aabb"][0] / pr["aabb"][1] * 1e3))
-t._L.pft_debug_set_ablate(0)
+t._L.pft_debug_set_ablate(t._h, 0)
