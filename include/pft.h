@@ -259,6 +259,12 @@ int pft_debug_get_hard_steps(pft_tracker* t, uint64_t out5[5]);
  * out4[1] node words held in LDS by the hybrid layout, out4[2] the workgroup's LDS bytes, out4[3] the fast descent's
  * margin in leaf cells (float bits) */
 int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4]);
+/* the ancestor table of the fast descent for the last tree built: info10 = {usable (filled for this tree), level L,
+ * window first cell x, y, z, log2 of the window's cells bx, by, bz (level-L cells), tree build epoch, epoch the table was
+ * filled for}; table (nullable) receives min(cap, 2^(bx+by+bz)) entries, entry [x | y << bx | z << (bx + by)] =
+ * (a << 27) | node: node is the deepest existing ancestor of window cell (x, y, z) at a level a <= L.
+ * PFT_ANCESTOR_TABLE=0 at pft_create: no table, info10[0] = info10[1] = 0 */
+int pft_debug_get_ancestor_table(pft_tracker* t, uint32_t info10[10], uint32_t* table, size_t cap);
 /* host-only (no device needed): the positions of the reference points the bounding box of the particles' transformed
  * clouds is taken over (A3: calcBoundingBox of the tracker that /root/reference/src/auto_tracking.cpp:691-693 runs) -- the
  * convex hull's vertices plus the shell the float evaluation can reach; `keep` has room for n indices (ascending),

@@ -64,6 +64,7 @@ struct pft_tracker {
   uint32_t* d_words = nullptr;
   uint32_t max_words = 0;
   uint16_t* d_jump = nullptr;
+  uint32_t* d_anc = nullptr;    // ancestor table (PFT_ANC_CAP entries; null with PFT_ANCESTOR_TABLE=0)
   uint32_t* d_ref_perm = nullptr;
   float4* d_leaf_pts = nullptr;
   uint32_t *d_leaf_order = nullptr, *d_pt_node = nullptr, *d_pt_key = nullptr, *d_pt_tmp = nullptr;
@@ -368,6 +369,7 @@ static void sync_dev(pft_tracker* t) {
   d.words = t->d_words;
   d.max_words = t->max_words;
   d.jump = t->d_jump;
+  d.anc = t->d_anc;
   d.ref_perm = t->d_ref_perm;
   d.leaf_pts = t->d_leaf_pts;
   d.leaf_order = t->d_leaf_order;
@@ -541,6 +543,7 @@ PftSwitches pft_read_switches() {
   w.split_resample = on("PFT_SPLIT_RESAMPLE") || w.resample_one_lane;  // (the one-lane kernel is a resample of its own)
   w.crop_two_pass = on("PFT_CROP_TWO_PASS");
   w.generic_descent = is1("PFT_GENERIC_DESCENT");
+  w.ancestor_table = !on("PFT_ANCESTOR_TABLE") || is1("PFT_ANCESTOR_TABLE");
   w.exact_path = on("PFT_EXACT_SHELLS_ONLY") ? PftExactPath::shells : on("PFT_EXACT_PER_QUERY") ? PftExactPath::per_query : PftExactPath::sorted;
 #ifdef PFT_DIAG
   if (const char* a = getenv("PFT_ABLATE")) w.ablate = atoi(a);  // bit0 generic levels, bit1 leaf scan, bit2 coherence
@@ -637,6 +640,7 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   A(dalloc(&t->d_bbox_part, t->bbox_part_cap * 6));
   A(dalloc(&t->d_bbox6, 8));
   A(dalloc(&t->d_jump, (size_t)1 << (3 * PFT_JUMP_MAX_LEVEL)));
+  if (t->sw.ancestor_table) A(dalloc(&t->d_anc, PFT_ANC_CAP));  // (node indices < 2^24: the 27 bits of an entry suffice)
   A(dalloc(&t->d_alias_list, 2 * Pt));
   A(dalloc(&t->d_alias_pref, 2 * Pt));
   A(dalloc(&t->d_pop_part, (size_t)PFT_POPM_MAX_WGS * 16));
@@ -700,7 +704,7 @@ extern "C" void pft_destroy(pft_tracker* t) {
   dfree(t->d_ref_raw); dfree(t->d_ref_xyz); dfree(t->d_ref_hsv); dfree(t->d_ref_box);
   dfree(t->d_in_raw); dfree(t->d_in_pts);
   dfree(t->d_part[0]); dfree(t->d_part[1]); dfree(t->d_mats); dfree(t->d_bbox_part); dfree(t->d_bbox6);
-  dfree(t->d_crop_counts); dfree(t->d_crop_slots); dfree(t->d_crop_pts); dfree(t->d_crop_idx); dfree(t->d_words); dfree(t->d_jump); dfree(t->d_ref_perm);
+  dfree(t->d_crop_counts); dfree(t->d_crop_slots); dfree(t->d_crop_pts); dfree(t->d_crop_idx); dfree(t->d_words); dfree(t->d_jump); dfree(t->d_anc); dfree(t->d_ref_perm);
   dfree(t->d_leaf_pts); dfree(t->d_leaf_order); dfree(t->d_pt_node); dfree(t->d_pt_key); dfree(t->d_pt_tmp);
   dfree(t->d_pt_key64); dfree(t->sort.keys[0]); dfree(t->sort.keys[1]); dfree(t->sort.vals[0]); dfree(t->sort.vals[1]);
   dfree(t->sort.hist); dfree(t->sort.tile_cnt); dfree(t->sort.tile_box); if (t->h_stat) hipHostFree(t->h_stat);
@@ -1054,7 +1058,7 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
   }
   {
     ProfScope ps(t, PFT_K_LIKELIHOOD);
-    const int flags = (t->sw.generic_descent ? 0 : 1) | (t->sw.ablate << 8);
+    const int flags = (t->sw.generic_descent ? 0 : 1) | (t->sw.ancestor_table ? 2 : 0) | (t->sw.ablate << 8);
     pftk_likelihood(t->stream, t->prm, d, np, debug_nn, t->num_cus, t->leaf_indirect, flags);
   }
 }
@@ -1577,6 +1581,28 @@ extern "C" int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4])
   int r = read_hdr(t, &h);
   if (r != PFT_OK) return r;
   memcpy(out4, h.lik_layout, sizeof(h.lik_layout));
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_get_ancestor_table(pft_tracker* t, uint32_t info10[10], uint32_t* table, size_t cap) {
+  if (!t || !info10) return PFT_ERR_INVALID_ARG;
+  PftHeader h;
+  int r = read_hdr(t, &h);
+  if (r != PFT_OK) return r;
+  const bool has = t->d_anc != nullptr && h.anc_level > 0;
+  info10[0] = has && h.anc_epoch == h.build_epoch ? 1u : 0u;
+  info10[1] = has ? (uint32_t)h.anc_level : 0u;
+  for (int a = 0; a < 3; a++) {
+    info10[2 + a] = has ? h.anc_lo[a] : 0u;
+    info10[5 + a] = has ? h.anc_bits[a] : 0u;
+  }
+  info10[8] = h.build_epoch;
+  info10[9] = h.anc_epoch;
+  const size_t cells = has ? (size_t)1 << (h.anc_bits[0] + h.anc_bits[1] + h.anc_bits[2]) : 0u;
+  if (table && cells && cap) {
+    HIPCHK(t, hipMemcpyAsync(table, t->d_anc, std::min(cap, cells) * sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+  }
   return PFT_OK;
 }
 

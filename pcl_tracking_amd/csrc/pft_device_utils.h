@@ -328,3 +328,35 @@ __device__ __forceinline__ int32_t alias_a_small(const AliasView& v, uint32_t k)
   const uint32_t kk = lower_bound_ge2(v.E, v.nh, dprev, v.cE, v.sE);
   return kk < v.nh ? v.H[kk] : (int32_t)k;
 }
+
+// Window of the ancestor table (PftHeader::anc_*), written by the builders (one thread) for the tree of depth D and box
+// minimum mn: the level-L cells, L = D - PFT_ANC_UP, of the crop box by the likelihood kernel's key formula, rounded up to a
+// power of two per axis (the kernel's window test and index are shifts and ors) and kept inside the tree's box.  The window
+// only decides which queries may use the table (the others take the jump + loop); it does not decide any result.  No table
+// (anc_level 0) when `on` is false, the handle has no table buffer or the window holds more than PFT_ANC_CAP cells.  Every
+// build bumps build_epoch: a table filled for an earlier tree is not used.
+__device__ inline void pft_anc_window(PftHeader* hdr, const PftDev& d, int D, bool on, const double mn[3], double res) {
+  const int L = D - PFT_ANC_UP;
+  on = on && d.anc != nullptr && L >= 1;
+  const float inv = (float)(1.0 / res);
+  uint32_t lo[3] = {0u, 0u, 0u}, bits[3] = {0u, 0u, 0u};
+  for (int a = 0; a < 3 && on; a++) {
+    const float om = (float)mn[a];
+    const float f0 = fmaxf(floorf((hdr->bbox[2 * a] - om) * inv), 0.0f);
+    const float f1 = fmaxf(floorf((hdr->bbox[2 * a + 1] - om) * inv), 0.0f);
+    const uint32_t top = (1u << L) - 1u;
+    const uint32_t c0 = min(f0 < 2147483648.0f ? (uint32_t)f0 >> PFT_ANC_UP : top, top);
+    const uint32_t c1 = min(f1 < 2147483648.0f ? (uint32_t)f1 >> PFT_ANC_UP : top, top);
+    on = c1 >= c0;
+    const uint32_t n = c1 - c0 + 1u;
+    bits[a] = n > 1u ? 32u - (uint32_t)__clz((int)(n - 1u)) : 0u;  // 2^bits >= n; <= L since n <= 2^L
+    lo[a] = min(c0, (1u << L) - (1u << bits[a]));
+  }
+  on = on && bits[0] + bits[1] + bits[2] <= PFT_ANC_CAP_BITS;
+  hdr->anc_level = on ? L : 0;
+  for (int a = 0; a < 3; a++) {
+    hdr->anc_lo[a] = on ? lo[a] : 0u;
+    hdr->anc_bits[a] = on ? bits[a] : 0u;
+  }
+  hdr->build_epoch = hdr->build_epoch + 1u;
+}

@@ -26,6 +26,13 @@
 #define PFT_TABLE_MAX_DEPTH 10
 #define PFT_MAX_GROW 40
 #define PFT_JUMP_MAX_LEVEL 4     // 2^12 cells x u16 = 8 KiB of LDS in the likelihood kernel
+#ifndef PFT_ANC_CAP_BITS
+#define PFT_ANC_CAP_BITS 18      // ancestor table: log2 of the entries per handle (1 MiB); a larger window has no table
+#endif
+#define PFT_ANC_CAP (1u << PFT_ANC_CAP_BITS)
+#ifndef PFT_ANC_UP
+#define PFT_ANC_UP 2             // ancestor table level L = depth - PFT_ANC_UP (1 measured slower)
+#endif
 #define PFT_REF_CHUNK 256        // reference points per likelihood work item (upper limit; PftParams::ref_chunk)
 #ifndef PFT_BUILD_THREADS
 #define PFT_BUILD_THREADS 1024
@@ -102,6 +109,13 @@ struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (
   float margin_cells;   // a query closer than this (in leaf cells) to a cell face takes the exact generic step
   float ominf[3];       // (float) omin
   float inv_res;        // (float)(1/res)
+  // ancestor table of the fast descent (PftDev::anc): entry (a << 27) | node for every level-anc_level cell c of the window
+  // anc_lo + [0, 2^anc_bits) (index cx | cy << bx | cz << (bx + by)): node is the deepest existing ancestor of c at a level
+  // a <= anc_level.  Written by the builders (window) and the fill (entries); used only while anc_epoch == build_epoch
+  int32_t anc_level;     // L = depth - PFT_ANC_UP (0: no table for this tree)
+  uint32_t anc_lo[3], anc_bits[3];
+  uint32_t build_epoch;  // bumped by every tree build
+  uint32_t anc_epoch;    // the build_epoch the entries were filled for
   // growth history of the box replay (read by the key kernel of the sorted builder)
   uint32_t grow_idx[PFT_MAX_GROW];
   uint32_t grow_shift[PFT_MAX_GROW];      // bit a set: min of axis a lowered by the old side
@@ -160,6 +174,7 @@ struct PftDev {  // device pointers (host-side struct, passed by value)
   uint32_t* words;
   uint32_t max_words;
   uint16_t* jump;           // [2^(3*PFT_JUMP_MAX_LEVEL)]
+  uint32_t* anc;            // [PFT_ANC_CAP] ancestor table (PftHeader::anc_level), or null: no table for this handle
   const uint32_t* ref_perm; // sorted reference position -> index in the caller's reference cloud
   float4* leaf_pts;
   uint32_t* leaf_order;
@@ -256,6 +271,7 @@ struct PftSwitches {
   bool resample_one_lane; // PFT_RESAMPLE_ONE_LANE: the one-lane-per-particle resample kernel instead of the four-lane one
   bool crop_two_pass;     // PFT_CROP_TWO_PASS: the crop as a count + a scatter launch instead of the one-pass kernel
   bool generic_descent;   // PFT_GENERIC_DESCENT=1: every octree level by the exact 8-way selection
+  bool ancestor_table;    // PFT_ANCESTOR_TABLE (default 1): the fast descent starts from the ancestor table
   PftExactPath exact_path;  // PFT_EXACT_SHELLS_ONLY, else PFT_EXACT_PER_QUERY, else the cell-sorted search
   int ablate;             // diagnostic build only: PFT_ABLATE, or pft_debug_set_ablate (results are wrong while set)
   bool skip_octree;       // diagnostic build only: PFT_DEBUG_SKIP_OCTREE (results are wrong while set)
@@ -307,7 +323,8 @@ struct SortBufs {
 // many-workgroup builder for large cropped clouds (pft_octree_sorted.hip); npass = 4 (depth <= 10) or 8
 void pftk_octree_sorted(hipStream_t s, const PftParams& p, const PftDev& d, const SortBufs& sb, uint32_t n_pad,
                         int npass);
-// flags (k_likelihood's argument): bit 0 fast descent allowed, bits 8+ the stage ablation mask of the diagnostic build
+// flags (k_likelihood's argument): bit 0 fast descent allowed, bit 1 ancestor table allowed, bits 8+ the stage ablation
+// mask of the diagnostic build
 void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
                      int num_cus, bool leaf_indirect, int flags);
 // shard (nullable): sharded handles -- the particles with their raw weights also go into the all-gather's send buffer

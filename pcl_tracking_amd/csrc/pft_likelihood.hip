@@ -41,6 +41,10 @@ struct LikCtx {
   const uint16_t* jump;    // LDS, or null
   int J;
   uint32_t lvlJ_start;
+  const uint32_t* anc;     // ancestor table (global memory, L2-resident), or null
+  // its window at level D - PFT_ANC_UP, packed (two scalar registers instead of six: the kernel is at 64 VGPRs, and more
+  // live scalars spill into vector lanes): first cell x | y << 10 | z << 20, log2 of the cells per axis bx | by << 8 | bz << 16
+  uint32_t alo, abits;
   float margin, near_thr, ominx, ominy, ominz, inv_res, ncell;
   uint32_t leaf0;
   const uint16_t* leaf16;  // LDS: start offsets of the leaves (+ sentinel)
@@ -187,13 +191,33 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
           V = max(vx, max(vy, vz));
         }
         V = inside ? V : 31;
-        const int lim = min(D, D - 1 - V);  // fast levels are those with lvl < lim
-        if (cx.J > 0) {  // (wave-uniform) the jump lands on level J: its cell spans 2^(D-J) leaf cells, D-J > V
-          const int sh = D - cx.J;
+        int lim = min(D, D - 1 - V);  // fast levels are those with lvl < lim
+        // Ancestor table: the fast descent's result is the deepest existing ancestor of the query's leaf cell at a level
+        // <= lim, an integer fact about the tree: one 4-byte gather of the entry of the query's level-L cell (a query
+        // outside the window reads entry 0 and does not use it; a query outside the box has key 0 and lim < 0: neither).
+        // (Issued right after the key, its live range pushed the kernel past 64 VGPRs into scratch.)
+        bool inw = false;
+        uint32_t ae = 0u;
+        if (!INDIRECT && LEAF == 1 && cx.anc) {  // (wave-uniform; which instances: see k_likelihood)
+          const uint32_t bx = cx.abits & 0xffu, by = (cx.abits >> 8) & 0xffu, bz = cx.abits >> 16;
+          const uint32_t ux = (kx >> PFT_ANC_UP) - (cx.alo & 1023u), uy = (ky >> PFT_ANC_UP) - ((cx.alo >> 10) & 1023u),
+                         uz = (kz >> PFT_ANC_UP) - (cx.alo >> 20);
+          inw = ((ux >> bx) | (uy >> by) | (uz >> bz)) == 0u;
+          ae = cx.anc[inw ? ux | (uy << bx) | (uz << (bx + by)) : 0u];
+        }
+        // the entry (a, node): a < L -- the descent ends at (node, a), no trip; a == L -- the loop goes on from there
+        // (at most D - L = PFT_ANC_UP trips); a > lim (near a face) or outside the window: the jump + loop below
+        const int a = (int)(ae >> 27);
+        const bool hit = inw & (a <= lim);
+        node = hit ? (ae & 0x7ffffffu) : 0u;
+        lvl = hit ? a : 0;
+        lim = (hit & (a < D - PFT_ANC_UP)) ? a : lim;
+        if (cx.J > 0 && __builtin_amdgcn_ballot_w64(!hit)) {  // (wave-uniform) the jump lands on level J: its cell spans
+          const int sh = D - cx.J;                              // 2^(D-J) leaf cells, D-J > V
           const uint32_t e = cx.jump[(kx >> sh) | ((ky >> sh) << cx.J) | ((kz >> sh) << (2 * cx.J))];
-          const bool take = (cx.J <= lim) & (e != 0u);  // all ancestors of an existing node exist and contain the query
-          node = take ? cx.lvlJ_start + e - 1u : 0u;
-          lvl = take ? cx.J : 0;
+          const bool take = !hit & (cx.J <= lim) & (e != 0u);  // all ancestors of an existing node exist and contain the query
+          node = take ? cx.lvlJ_start + e - 1u : node;
+          lvl = take ? cx.J : lvl;
           if (DEBUG_NN) dbg_jump = take ? 1 : 0;
         }
         // fast levels: follow the key while the child containing the query exists (a divergent loop: a version
@@ -555,6 +579,16 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
   cx.jump = ljump;
   cx.J = J;
   cx.lvlJ_start = J > 0 ? hdr->lvl_start[J] : 0u;
+  // the ancestor table, when it was filled for this tree (anc_epoch: the paths that build without filling fall back by
+  // themselves); global memory, so the LDS layout above does not depend on it.  Compiled into the u16-leaf-start layout of
+  // the direct form only: the trees of the other layouts come from the sorted builder (crops above PFT_SORTED_BUILD_MIN) and
+  // the indirect form from small launches, neither of which fills a table, and every inlined copy costs registers (the
+  // kernel is at 63 of its 64 VGPRs with this one)
+  const bool anc_on = fast && (flags & 2) && d.anc && hdr->anc_level > 0 && hdr->anc_epoch == hdr->build_epoch;
+  cx.anc = anc_on ? d.anc : nullptr;
+  static_assert(PFT_TABLE_MAX_DEPTH <= 10, "ancestor table window coordinates are packed in 10 bits");  // (fast: use_tab)
+  cx.alo = hdr->anc_lo[0] | (hdr->anc_lo[1] << 10) | (hdr->anc_lo[2] << 20);
+  cx.abits = hdr->anc_bits[0] | (hdr->anc_bits[1] << 8) | (hdr->anc_bits[2] << 16);
   cx.margin = hdr->margin_cells;
   // |f - 0.5| above this: the query may be within `margin` of a face of its leaf cell (a little wider than the exact test)
   cx.near_thr = 0.5f - 1.01f * hdr->margin_cells - 1.0e-6f;

@@ -631,6 +631,8 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
     hdr->margin_cells = (float)(mc < 0.25 ? mc : 1.0);  // >= 0.5: fast descent never taken
   }
   if (tid == 128) hdr->inv_res = (float)(1.0 / prm.res);
+  // the ancestor table is filled by k_leaf_gather, i.e. in mode 0 only (the other modes have no launch to carry it: no table)
+  if (tid == 320) pft_anc_window(hdr, d, D, ok && use_table && copy_leaf_pts == 0, S.mn, prm.res);
   if (tid >= 192 && tid < 195) {
     const int a = (int)tid - 192;
     hdr->ominf[a] = (float)S.mn[a];
@@ -640,14 +642,49 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
   if (tid >= 256 && tid < 256 + PFT_MAX_DEPTH + 3 && (int)tid - 256 <= D + 1) hdr->lvl_start[tid - 256] = S.lvl[tid - 256];
 }
 
-// leaf-ordered point records for the likelihood kernel's leaf scan: leaf_pts[pos] = crop_pts[leaf_order[pos]]
+// The ancestor table of the tree just built (PftHeader::anc_*): for every cell of the window, the walk of the likelihood
+// kernel's fast descent along the cell's key down to level L -- from the jump table's level-J node when there is one -- and
+// the deepest node it reaches.  An integer fact about the tree: no float decision is involved.
+__device__ __forceinline__ void anc_fill(const PftDev& d, uint32_t gid, uint32_t stride) {
+  const PftHeader* hdr = d.hdr;
+  const int L = hdr->anc_level;
+  if (L <= 0) return;
+  const uint32_t bx = hdr->anc_bits[0], by = hdr->anc_bits[1], n = 1u << (bx + by + hdr->anc_bits[2]);
+  const uint32_t x0 = hdr->anc_lo[0], y0 = hdr->anc_lo[1], z0 = hdr->anc_lo[2];
+  const int J = hdr->jump_level <= L ? hdr->jump_level : 0;
+  const uint32_t lvlJ = J > 0 ? hdr->lvl_start[J] : 0u;
+  for (uint32_t c = gid; c < n; c += stride) {
+    const uint32_t x = x0 + (c & ((1u << bx) - 1u)), y = y0 + ((c >> bx) & ((1u << by) - 1u)), z = z0 + (c >> (bx + by));
+    uint32_t node = 0;
+    int lvl = 0;
+    if (J > 0) {
+      const int sh = L - J;
+      const uint32_t e = d.jump[(x >> sh) | ((y >> sh) << J) | ((z >> sh) << (2 * J))];
+      node = e ? lvlJ + e - 1u : 0u;
+      lvl = e ? J : 0;
+    }
+    for (; lvl < L; lvl++) {
+      const int sh = L - lvl - 1;
+      const uint32_t ch = (((x >> sh) & 1u) << 2) | (((y >> sh) & 1u) << 1) | ((z >> sh) & 1u);
+      const uint32_t wv = d.words[node];
+      if (!((wv >> ch) & 1u)) break;
+      node = (wv >> 8) + __popc(wv & 0xffu & ((1u << ch) - 1u));
+    }
+    d.anc[c] = ((uint32_t)lvl << 27) | node;
+  }
+  if (gid == 0) d.hdr->anc_epoch = hdr->build_epoch;  // (read by the next launch on the stream: after every entry)
+}
+
+// leaf-ordered point records for the likelihood kernel's leaf scan: leaf_pts[pos] = crop_pts[leaf_order[pos]]; and the
+// ancestor table (a launch of its own would cost more than these few thousand extra threads)
 template <bool GATED>
 __global__ __launch_bounds__(256) void k_leaf_gather(PftDev d) {
   if (GATED && pft_unchanged(d.gate)) return;  // change detection: nothing changed, nothing to build
   const PftHeader* hdr = d.hdr;
   const uint32_t pos = blockIdx.x * 256u + threadIdx.x;
-  if (hdr->error || hdr->depth <= 0 || pos >= hdr->n_crop) return;
-  d.leaf_pts[pos] = d.crop_pts[d.leaf_order[pos]];
+  if (hdr->error || hdr->depth <= 0) return;
+  if (pos < hdr->n_crop) d.leaf_pts[pos] = d.crop_pts[d.leaf_order[pos]];
+  anc_fill(d, pos, gridDim.x * 256u);
 }
 
 #ifndef PFT_OCTREE_GATED_TU
