@@ -17,6 +17,11 @@
  *   6. EuclideanClusterExtraction: clusters of min..max points, by size descending, ties by smallest index
  * The output holds each cluster's indices into the caller's INPUT cloud (ascending) and the input's own points.
  * There is no CPU path.  DESIGN.md section 3.7 states the rules and their confidence.
+ *
+ * Plane rounds (pft_segment_set_plane_rounds) repeat stages 3 and 4 as the reference's cluster_euclid.cpp:59-85 and
+ * cluster_extraction.cpp do: planes are taken out one after the other while more than a fraction of the points is
+ * left, and only then the box and the clustering run.  The refit's summation order is a second switch
+ * (pft_segment_set_refit_order).  Both default to the single plane and PCL's serial sums.
  */
 #ifndef PFT_SEGMENT_H
 #define PFT_SEGMENT_H
@@ -94,9 +99,42 @@ int pft_segment_get_cluster_points(pft_segment* s, pft_point_xyzrgba* host_pts, 
 enum { PFT_SEGMENT_STAGES = 7 }; /* compaction, sample stream, scoring, replay, refit, clustering, output */
 int pft_segment_last_ms(const pft_segment* s, double* ms, double* stage_ms);
 
+/* ---- plane rounds: cluster_euclid.cpp:59-85 / cluster_extraction.cpp ----
+ * With nr the number of points after removeZeroPoints, a round runs while
+ *     (double)remaining > min_remaining_fraction * (double)nr        (the reference's size() > 0.3 * nr_points)
+ * and fewer than max_planes rounds have run.  Every round is a fresh SACSegmentation::segment over the remaining
+ * cloud in ascending input order: the sampler is reseeded, n is the round's cloud size, the refit sums run over the
+ * round's inliers.  A round without a plane, or whose plane has no final inlier, ends the loop and removes nothing
+ * (the reference's break).  max_planes is this library's cap, the reference has none: reaching it while the condition
+ * still holds is reported as PFT_ROUNDS_STOP_MAX_PLANES.  Defaults: max_planes = 1, min_remaining_fraction = 0.0,
+ * which is the single plane of create_model_planar_segmentation.cpp. */
+enum { PFT_SEGMENT_MAX_PLANES = 16 };
+enum { PFT_ROUNDS_STOP_FRACTION = 0, PFT_ROUNDS_STOP_NO_PLANE = 1, PFT_ROUNDS_STOP_MAX_PLANES = 2 };
+int pft_segment_set_plane_rounds(pft_segment* s, int max_planes, double min_remaining_fraction);
+int pft_segment_get_plane_rounds(const pft_segment* s, int* max_planes, double* min_remaining_fraction);
+/* n_planes: planes removed by the last apply; stopped_by: PFT_ROUNDS_STOP_* (either may be NULL) */
+int pft_segment_plane_count(const pft_segment* s, size_t* n_planes, int* stopped_by);
+/* the record of one round that ran (a last round that found no plane included: status PFT_PLANE_NONE); round 0 always
+ * exists and is what pft_segment_get_plane returns.  n_valid is the round's cloud size, sample[3] indexes the round's
+ * cloud, n_survivors is the count after all rounds and the box. */
+int pft_segment_get_plane_round(const pft_segment* s, size_t round, pft_segment_plane* plane);
+/* a round's inliers as indices into the INPUT cloud, ascending; which as in pft_segment_get_plane_inliers */
+int pft_segment_get_plane_round_inliers(pft_segment* s, size_t round, int which, int32_t* host_idx, size_t capacity,
+                                        size_t* n);
+
+/* summation order of the refit's nine moment sums: PFT_SUM_PCL (default) is computeMeanAndCovarianceMatrix's serial
+ * float chain in inlier order; PFT_SUM_TREE is the adjacent-pair tree in float over the inlier list padded with -0.0
+ * to a power of two (products rounded to float first), reduced across many workgroups.  Every level of the tree is an
+ * aligned subtree, so the bits do not depend on the launch shape.  The two orders are two specifications: their
+ * coefficients differ in the last digits and so may the final inliers. */
+int pft_segment_set_refit_order(pft_segment* s, int order);
+
 /* the hypotheses of the last apply in draw order, as far as the RANSAC loop consumed them: 3 sample indices (into
  * the removeZeroPoints output) and the inlier count of each; n = RandomSampleConsensus::iterations_ */
 int pft_debug_segment_hypotheses(pft_segment* s, int32_t* samples, uint32_t* counts, size_t capacity, size_t* n);
+/* the same for one round (sample indices into that round's cloud); round 0 is pft_debug_segment_hypotheses */
+int pft_debug_segment_round_hypotheses(pft_segment* s, size_t round, int32_t* samples, uint32_t* counts,
+                                       size_t capacity, size_t* n);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,8 @@ class SegmentPlane(C.Structure):
 
 
 PLANE_FOUND, PLANE_NONE, PLANE_DISABLED = 0, 1, 2
+SEGMENT_MAX_PLANES = 16
+ROUNDS_STOP_FRACTION, ROUNDS_STOP_NO_PLANE, ROUNDS_STOP_MAX_PLANES = 0, 1, 2
 SEGMENT_STAGES = ("compaction", "sample", "score", "replay", "refit", "cluster", "output")
 
 # every symbol include/*.h declare: (name, restype, argtypes)
@@ -185,6 +187,13 @@ SYMBOLS = [
     ("pft_segment_get_cluster_points", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_segment_last_ms", C.c_int, [_vp, _P(_f64), _vp]),
     ("pft_debug_segment_hypotheses", C.c_int, [_vp, _vp, _vp, _sz, _P(_sz)]),
+    ("pft_segment_set_plane_rounds", C.c_int, [_vp, C.c_int, _f64]),
+    ("pft_segment_get_plane_rounds", C.c_int, [_vp, _P(C.c_int), _P(_f64)]),
+    ("pft_segment_plane_count", C.c_int, [_vp, _P(_sz), _P(C.c_int)]),
+    ("pft_segment_get_plane_round", C.c_int, [_vp, _sz, _P(SegmentPlane)]),
+    ("pft_segment_get_plane_round_inliers", C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _P(_sz)]),
+    ("pft_segment_set_refit_order", C.c_int, [_vp, C.c_int]),
+    ("pft_debug_segment_round_hypotheses", C.c_int, [_vp, _sz, _vp, _vp, _sz, _P(_sz)]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

@@ -9,6 +9,9 @@
 //   replay       k_sg_replay: RandomSampleConsensus::computeModel's loop over the scored batch, in one lane
 //   refit        k_sg_select + compaction of the best hypothesis' inliers, k_sg_refit: the nine sequential float sums
 //                of computeMeanAndCovarianceMatrix (nine lanes) and pcl::eigen33 (one lane)
+//                or, PFT_SUM_TREE: k_sg_refit_tiles + k_sg_refit_top, the sums as adjacent-pair trees over many workgroups
+//   rounds       pft_segment_set_plane_rounds: sample .. refit repeated on what the last plane left (cluster_euclid.cpp:
+//                59-85), k_sg_round_*: a byte per input point tells the round that removed it
 //   clustering   survivors sorted by a grid-cell key (the radix sort of pft_filters.hip), lock-free union-find over
 //                neighbour cells, component sizes, the size filter, the ordering rule, a stable sort by cluster rank
 //
@@ -559,6 +562,27 @@ __device__ void sg_eigen33(const float* mat, float* vec) {
   vec[2] = v[pick][2] / s;
 }
 
+// the refit after the sums, one lane: accu = the nine sums divided by the count
+__device__ void sg_refit_tail(SgHdr* __restrict__ h, const float* accu) {
+  float cov[9];
+  cov[0] = accu[0] - accu[6] * accu[6];
+  cov[1] = accu[1] - accu[6] * accu[7];
+  cov[2] = accu[2] - accu[6] * accu[8];
+  cov[4] = accu[3] - accu[7] * accu[7];
+  cov[5] = accu[4] - accu[7] * accu[8];
+  cov[8] = accu[5] - accu[8] * accu[8];
+  cov[3] = cov[1];
+  cov[6] = cov[2];
+  cov[7] = cov[5];
+  float e[3];
+  sg_eigen33(cov, e);
+  const float dot = (e[0] * accu[6] + e[1] * accu[7]) + (e[2] * accu[8] + 0.0f * 1.0f);
+  h->coef_final[0] = e[0];
+  h->coef_final[1] = e[1];
+  h->coef_final[2] = e[2];
+  h->coef_final[3] = -1.0f * dot;
+}
+
 // RULE refit: optimizeModelCoefficients -- nine float accumulators summed in inlier index order, divided by the
 // count, covariance accu[i] - mean * mean, eigen33, d = -((e0 c0 + e1 c1) + (e2 c2 + 0 * 1)).  Fewer than 4 inliers:
 // the coefficients stay.  One workgroup: the points are staged in LDS, nine lanes of wave 0 run the dependent adds.
@@ -594,25 +618,174 @@ __global__ __launch_bounds__(SG_REFIT_THREADS) void k_sg_refit(SgParams p, SgHdr
   }
   if (tid < 9) accu[tid] = acc / (float)m;
   __syncthreads();
-  if (tid == 0) {
-    float cov[9];
-    cov[0] = accu[0] - accu[6] * accu[6];
-    cov[1] = accu[1] - accu[6] * accu[7];
-    cov[2] = accu[2] - accu[6] * accu[8];
-    cov[4] = accu[3] - accu[7] * accu[7];
-    cov[5] = accu[4] - accu[7] * accu[8];
-    cov[8] = accu[5] - accu[8] * accu[8];
-    cov[3] = cov[1];
-    cov[6] = cov[2];
-    cov[7] = cov[5];
-    float e[3];
-    sg_eigen33(cov, e);
-    const float dot = (e[0] * accu[6] + e[1] * accu[7]) + (e[2] * accu[8] + 0.0f * 1.0f);
-    h->coef_final[0] = e[0];
-    h->coef_final[1] = e[1];
-    h->coef_final[2] = e[2];
-    h->coef_final[3] = -1.0f * dot;
+  if (tid == 0) sg_refit_tail(h, accu);
+}
+
+// RULE refit, PFT_SUM_TREE: the nine sums as adjacent-pair trees in float over the inlier list padded with -0.0 (the
+// exact additive identity, so the padding length does not change a bit) to a power of two; the products are rounded to
+// float first.  T0 = the terms, T(k+1)[i] = Tk[2i] + Tk[2i+1].  Levels 0..3 are a thread's 8 points, 3..9 the wave's xor
+// shuffles (a + b == b + a in IEEE, so both lanes of a pair hold the node), 9..11 the four waves in LDS: a tile of
+// SG_RT_TILE inliers is one aligned subtree, whichever workgroup reduces it, and k_sg_refit_top takes the tile sums as
+// the upper levels of the same tree.  So the bits do not depend on the launch shape.
+#define SG_RT_THREADS 256u
+#define SG_RT_PTS 8u
+#define SG_RT_TILE (SG_RT_THREADS * SG_RT_PTS)
+#define SG_RT_TOP 1024u
+__device__ __forceinline__ float sg_pair_wave(float v) {
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) v = v + __shfl_xor(v, o);
+  return v;
+}
+
+__global__ __launch_bounds__(SG_RT_THREADS) void k_sg_refit_tiles(const SgHdr* __restrict__ h, int optimize,
+                                                                  const float4* __restrict__ pts,
+                                                                  const uint32_t* __restrict__ inl,
+                                                                  float* __restrict__ part) {
+  __shared__ float sw[SG_RT_THREADS / WAVE][9];
+  const uint32_t tid = threadIdx.x, m = h->n_ransac_inl;
+  if (h->best_h < 0 || !optimize || m < 4) return;  // (uniform) k_sg_refit_top copies the coefficients
+  const uint32_t ntile = (m + SG_RT_TILE - 1u) / SG_RT_TILE;
+  for (uint32_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+    const uint32_t base = t * SG_RT_TILE + tid * SG_RT_PTS;
+    float x[SG_RT_PTS], y[SG_RT_PTS], z[SG_RT_PTS];
+    bool ok[SG_RT_PTS];
+#pragma unroll
+    for (uint32_t k = 0; k < SG_RT_PTS; k++) {
+      ok[k] = base + k < m;
+      const float4 q = ok[k] ? pts[inl[base + k]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      x[k] = q.x;
+      y[k] = q.y;
+      z[k] = q.z;
+    }
+    float acc[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+      float tm[SG_RT_PTS];
+#pragma unroll
+      for (uint32_t k = 0; k < SG_RT_PTS; k++) {
+        // (x,x) (x,y) (x,z) (y,y) (y,z) (z,z), then x, y, z (times w = 1.0f, exactly the coordinate)
+        const float a = j < 3 ? x[k] : (j < 5 ? y[k] : (j == 5 ? z[k] : (j == 6 ? x[k] : (j == 7 ? y[k] : z[k]))));
+        const float b = j == 0 ? x[k] : (j == 1 || j == 3 ? y[k] : (j == 2 || j == 4 || j == 5 ? z[k] : 1.0f));
+        tm[k] = ok[k] ? a * b : -0.0f;
+      }
+      acc[j] = sg_pair_wave(((tm[0] + tm[1]) + (tm[2] + tm[3])) + ((tm[4] + tm[5]) + (tm[6] + tm[7])));
+    }
+    if (lane_id() == 0) {
+#pragma unroll
+      for (int j = 0; j < 9; j++) sw[wave_id()][j] = acc[j];
+    }
+    __syncthreads();
+    if (tid < 9) part[(size_t)t * 9u + tid] = (sw[0][tid] + sw[1][tid]) + (sw[2][tid] + sw[3][tid]);
+    __syncthreads();
   }
+}
+
+// pair tree over SG_RT_TOP values per moment, one per thread: the wave's shuffles, then the 16 wave sums; the nine
+// results in threads 0..8
+__device__ float sg_top_tree9(float (&v)[9], float (*sw)[9]) {
+  const uint32_t tid = threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < 9; j++) v[j] = sg_pair_wave(v[j]);
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int j = 0; j < 9; j++) sw[wave_id()][j] = v[j];
+  }
+  __syncthreads();
+  float r = -0.0f;
+  if (tid < 9) {
+    float a[SG_RT_TOP / WAVE];
+#pragma unroll
+    for (uint32_t w = 0; w < SG_RT_TOP / WAVE; w++) a[w] = sw[w][tid];
+#pragma unroll
+    for (uint32_t sz = SG_RT_TOP / WAVE; sz > 1u; sz >>= 1)
+#pragma unroll
+      for (uint32_t i = 0; i < sz / 2u; i++) a[i] = a[2u * i] + a[2u * i + 1u];
+    r = a[0];
+  }
+  __syncthreads();
+  return r;
+}
+
+// one workgroup: the tile sums as the upper levels of the tree (chunks of SG_RT_TOP tiles, then the chunk sums: up to
+// 2^20 tiles = 2^31 inliers), then the one-lane tail of k_sg_refit
+__global__ __launch_bounds__(SG_RT_TOP) void k_sg_refit_top(SgHdr* __restrict__ h, int optimize,
+                                                            const float* __restrict__ part) {
+  __shared__ float sw[SG_RT_TOP / WAVE][9];
+  __shared__ float schunk[9][SG_RT_TOP];
+  __shared__ float accu[9];
+  const uint32_t tid = threadIdx.x, m = h->n_ransac_inl;
+  if (h->best_h < 0) return;  // (uniform)
+  if (!optimize || m < 4) {
+    if (tid < 4) h->coef_final[tid] = h->coef_ransac[tid];
+    return;
+  }
+  const uint32_t ntile = (m + SG_RT_TILE - 1u) / SG_RT_TILE, nchunk = (ntile + SG_RT_TOP - 1u) / SG_RT_TOP;
+  float v[9];
+  for (uint32_t c = 0; c < nchunk; c++) {
+    const uint32_t t = c * SG_RT_TOP + tid;
+#pragma unroll
+    for (int j = 0; j < 9; j++) v[j] = t < ntile ? part[(size_t)t * 9u + j] : -0.0f;
+    const float r = sg_top_tree9(v, sw);
+    if (tid < 9) schunk[tid][c] = r;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 9; j++) v[j] = tid < nchunk ? schunk[j][tid] : -0.0f;
+  const float acc = sg_top_tree9(v, sw);
+  if (tid < 9) accu[tid] = acc / (float)m;
+  __syncthreads();
+  if (tid == 0) sg_refit_tail(h, accu);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// plane rounds (pft_segment_set_plane_rounds).  rnd[i], per INPUT index: SG_RND_INVALID = dropped by removeZeroPoints,
+// SG_RND_KEPT = never removed, r = a final inlier of round r.  The inlier lists of any round are re-derived from it.
+#define SG_RND_INVALID 0xFFu
+#define SG_RND_KEPT 0xFEu
+__global__ __launch_bounds__(SG_THREADS) void k_sg_round_init(uint32_t n, const uint8_t* __restrict__ flag,
+                                                              uint8_t* __restrict__ rnd) {
+  const uint32_t i = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (i < n) rnd[i] = flag[i] ? SG_RND_KEPT : SG_RND_INVALID;
+}
+
+// a fresh SACSegmentation::segment over n_r points: the RANSAC and sampler state of the header, not its error bits
+__global__ void k_sg_round_begin(SgHdr* __restrict__ h, uint32_t n_r) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const uint32_t err = h->err;
+  SgHdr z = {};
+  z.k = 1.0;
+  z.best_count = -INT32_MAX;
+  z.best_h = -1;
+  z.n_valid = n_r;
+  z.err = err;
+  *h = z;
+}
+
+// final inliers of round r (flags over the round's cloud) -> rnd at their input indices
+__global__ __launch_bounds__(SG_THREADS) void k_sg_round_mark(const SgHdr* __restrict__ h,
+                                                              const uint8_t* __restrict__ flag,
+                                                              const uint32_t* __restrict__ map, uint8_t* __restrict__ rnd,
+                                                              uint32_t r) {
+  const uint32_t i = blockIdx.x * SG_THREADS + threadIdx.x;
+  if (i < h->n_valid && flag[i]) rnd[map[i]] = (uint8_t)r;
+}
+
+// flags over the input of round r's inliers: which = 0 the final ones, 1 the points of the round's cloud (valid, not
+// removed before round r) within the distance of the round's best hypothesis c
+__global__ __launch_bounds__(SG_THREADS) void k_sg_round_flags(uint32_t n, const uint8_t* __restrict__ rnd,
+                                                               const float4* __restrict__ tx, uint32_t r, int which,
+                                                               float4 c, float thr, uint8_t* __restrict__ flag,
+                                                               uint32_t* __restrict__ tile) {
+  const uint32_t i0 = blockIdx.x * SG_TILE + threadIdx.x * 4u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t i = i0 + k;
+    if (i >= n) break;
+    const uint32_t v = rnd[i];
+    const bool in = which == 0 ? v == r : (v != SG_RND_INVALID && v >= r && within(c, tx[i], thr));
+    flag[i] = in ? 1 : 0;
+  }
+  sg_tile_count(flag, n, tile);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -926,6 +1099,8 @@ struct SgBufs {
   float* bpart;
   int32_t* out_idx;
   pft_point_xyzrgba* out_pts;
+  uint8_t* rnd;         // plane rounds: per input index, the round that removed the point
+  float* refit_part;    // tree-order refit: nine sums per tile of SG_RT_TILE inliers
 };
 
 struct pft_segment {
@@ -940,9 +1115,19 @@ struct pft_segment {
   SgSampler smp = {};
   SgHyp hyp = {};
   uint32_t hmax = 0;
-  hipEvent_t ev[SG_NEV] = {};
-  int ev_stage[SG_NEV] = {};
+  std::vector<hipEvent_t> ev;  // SG_NEV at creation; plane rounds add more on demand
+  std::vector<int> ev_stage;
   int nev = 0;
+  // plane rounds and the refit's summation order (setters; the defaults are the single plane, PCL's chains)
+  int max_planes = 1;
+  double min_fraction = 0.0;
+  int refit_order = PFT_SUM_PCL;
+  uint32_t refit_grid = 0;     // PFT_SEGMENT_REFIT_GRID, latched at creation: workgroups of the tile launch (0 = by size)
+  uint32_t hyp_rounds = 1;     // rounds the hypothesis buffers hold
+  std::vector<SgHdr> rounds;   // header of every round the last apply ran (one synthetic entry when none ran)
+  bool by_rounds = false;      // the last apply ran the round loop: inlier lists come from b.rnd
+  size_t n_rounds = 0, n_planes = 0;
+  int stopped_by = PFT_ROUNDS_STOP_FRACTION;
   // results of the last apply
   bool have_result = false;
   SgHdr res = {};
@@ -971,7 +1156,7 @@ static void free_buffers(pft_segment* s) {
   }
   sfree(b.hist); sfree(b.sorted); sfree(b.cell_start); sfree(b.cell_key); sfree(b.cell_of); sfree(b.parent);
   sfree(b.label); sfree(b.csize); sfree(b.roots); sfree(b.crank); sfree(b.sizes); sfree(b.bpart); sfree(b.out_idx);
-  sfree(b.out_pts);
+  sfree(b.out_pts); sfree(b.rnd); sfree(b.refit_part);
   s->cap = 0;
 }
 
@@ -1013,6 +1198,8 @@ static int ensure_capacity(pft_segment* s, size_t n) {
   SCHK(s, salloc(&b.bpart, 6 * 1024));
   SCHK(s, salloc(&b.out_idx, cap));
   SCHK(s, salloc(&b.out_pts, cap));
+  SCHK(s, salloc(&b.rnd, cap));
+  SCHK(s, salloc(&b.refit_part, 9 * (cap / SG_RT_TILE + 1)));
   s->cap = cap;
   return PFT_OK;
 }
@@ -1058,7 +1245,10 @@ extern "C" int pft_segment_create(const pft_segment_config* cfg, pft_segment** o
     ok = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess;
     s->own_stream = ok;
   }
+  s->ev.assign(SG_NEV, nullptr);
+  s->ev_stage.assign(SG_NEV, 0);
   for (int k = 0; ok && k < SG_NEV; k++) ok = hipEventCreate(&s->ev[k]) == hipSuccess;
+  if (const char* g = getenv("PFT_SEGMENT_REFIT_GRID")) s->refit_grid = (uint32_t)std::max(0, atoi(g));
   s->hmax = ((uint32_t)cfg->max_iterations + 1u + SG_BATCH - 1u) / SG_BATCH * SG_BATCH;
   if (ok)
     ok = salloc(&s->hdr, 1) == hipSuccess &&
@@ -1083,8 +1273,8 @@ extern "C" void pft_segment_destroy(pft_segment* s) {
   if (s->host_hdr) hipHostFree(s->host_hdr);
   sfree(s->smp.mt); sfree(s->smp.mk); sfree(s->smp.mv);
   sfree(s->hyp.sample); sfree(s->hyp.coef); sfree(s->hyp.count);
-  for (int k = 0; k < SG_NEV; k++)
-    if (s->ev[k]) hipEventDestroy(s->ev[k]);
+  for (hipEvent_t e : s->ev)
+    if (e) hipEventDestroy(e);
   if (s->own_stream && s->stream) hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1094,7 +1284,12 @@ extern "C" const char* pft_segment_last_error_string(const pft_segment* s) { ret
 // an event after the launches of one stage: the time since the previous event is booked to that stage (stage -1: an
 // event right after a host synchronisation, whose gap is host idle time and booked nowhere)
 static int mark(pft_segment* s, int stage) {
-  if (s->nev >= SG_NEV) return PFT_OK;  // (cannot happen: at most 3 per batch + 16)
+  if (s->nev >= (int)s->ev.size()) {  // (plane rounds only: one apply of the single plane needs at most 3 per batch + 16)
+    hipEvent_t e = nullptr;
+    SCHK(s, hipEventCreate(&e));
+    s->ev.push_back(e);
+    s->ev_stage.push_back(0);
+  }
   SCHK(s, hipEventRecord(s->ev[s->nev], s->stream));
   s->ev_stage[s->nev] = stage;
   s->nev++;
@@ -1112,6 +1307,124 @@ static int read_hdr(pft_segment* s) {
   SCHK(s, hipMemcpyAsync(s->host_hdr, s->hdr, sizeof(SgHdr), hipMemcpyDeviceToHost, s->stream));
   SCHK(s, hipStreamSynchronize(s->stream));
   SCHK(s, hipGetLastError());
+  return PFT_OK;
+}
+
+// 3. one SACSegmentation::segment over the cloud `pts` (its size in the header's n_valid, at most n_max): RANSAC in
+// batches, the inliers of the best hypothesis, the refit.  Leaves coef_ransac / coef_final / n_ransac_inl in the header.
+static int plane_stage(pft_segment* s, const SgParams& p, const SgHyp& hyp, const float4* pts, uint32_t n_max,
+                       uint32_t ntiles) {
+  const pft_segment_config& c = s->cfg;
+  hipStream_t st = s->stream;
+  SgBufs& b = s->b;
+  const uint32_t* n_valid = &s->hdr->n_valid;
+  // every launch after the deciding batch returns at once
+  SCHK(s, hipMemsetAsync(hyp.count, 0, s->hmax * sizeof(uint32_t), st));
+  const uint32_t nscore = (n_max + SG_THREADS * SG_SCORE_PTS - 1) / (SG_THREADS * SG_SCORE_PTS);
+  for (uint32_t bt = 0; bt * SG_BATCH < s->hmax; bt++) {
+    hipLaunchKernelGGL(k_sg_sample, dim3(1), dim3(SG_THREADS), 0, st, p, s->hdr, s->smp, hyp, pts, bt);
+    MARK(ST_SAMPLE);
+    hipLaunchKernelGGL(k_sg_score, dim3(nscore), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, hyp, pts, bt);
+    MARK(ST_SCORE);
+    hipLaunchKernelGGL(k_sg_replay, dim3(1), dim3(64), 0, st, p, s->hdr, hyp, bt);
+    MARK(ST_REPLAY);
+  }
+  // inliers of the best hypothesis, refit
+  hipLaunchKernelGGL(k_sg_select, dim3(ntiles), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, 0, pts, b.flag,
+                     b.tile, (uint8_t*)nullptr, (uint32_t*)nullptr);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles, n_valid, &s->hdr->n_ransac_inl);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag, n_max, n_valid, b.tile,
+                     (const uint32_t*)nullptr, b.inl_idx, (const float4*)nullptr, (float4*)nullptr);
+  if (s->refit_order == PFT_SUM_TREE) {
+    // at most one workgroup per tile of the largest inlier list; the tiles are walked grid-stride, so any grid is valid
+    uint32_t grid = std::min<uint32_t>((n_max + SG_RT_TILE - 1) / SG_RT_TILE, 1024u);
+    if (s->refit_grid) grid = s->refit_grid;
+    hipLaunchKernelGGL(k_sg_refit_tiles, dim3(std::max(grid, 1u)), dim3(SG_RT_THREADS), 0, st, (const SgHdr*)s->hdr,
+                       c.optimize_coefficients, pts, (const uint32_t*)b.inl_idx, b.refit_part);
+    hipLaunchKernelGGL(k_sg_refit_top, dim3(1), dim3(SG_RT_TOP), 0, st, s->hdr, c.optimize_coefficients,
+                       (const float*)b.refit_part);
+  } else {
+    hipLaunchKernelGGL(k_sg_refit, dim3(1), dim3(SG_REFIT_THREADS), 0, st, p, s->hdr, c.optimize_coefficients, pts,
+                       (const uint32_t*)b.inl_idx);
+  }
+  MARK(ST_REFIT);
+  return PFT_OK;
+}
+
+// the plane rounds of cluster_euclid.cpp:59-85: RULE rounds.  The remaining cloud ping-pongs between (comp_pts,
+// comp_idx) and two clustering buffers that are idle until stage 6; the host reads the header once per round for the
+// remaining count, which sizes the next round's grids and decides the stop.
+static int plane_rounds(pft_segment* s, const SgParams& p, uint32_t n, const float4** cpts, const uint32_t** cidx,
+                        uint32_t* n_left) {
+  hipStream_t st = s->stream;
+  SgBufs& b = s->b;
+  SgHdr* H = s->host_hdr;
+  SgParams pr = p;  // the rounds remove planes only: the box is stage 5, after the loop
+  for (int a = 0; a < 3; a++) pr.box_enable[a] = 0;
+  hipLaunchKernelGGL(k_sg_round_init, dim3((n + SG_THREADS - 1) / SG_THREADS), dim3(SG_THREADS), 0, st, n,
+                     (const uint8_t*)b.flag, b.rnd);
+  MARK(ST_COMPACT);
+  int r = read_hdr(s);
+  if (r != PFT_OK) return r;
+  MARK(-1);
+  const uint32_t nr = H->n_valid;
+  uint32_t remaining = nr;
+  float4* pts[2] = {b.comp_pts, b.sorted};
+  uint32_t* idx[2] = {b.comp_idx, b.cell_of};
+  int cur = 0;
+  for (;;) {
+    // RULE rounds: the reference's cloud_filtered->points.size() > 0.3 * nr_points, a double product and compare
+    if (!((double)remaining > s->min_fraction * (double)nr)) {
+      s->stopped_by = PFT_ROUNDS_STOP_FRACTION;
+      break;
+    }
+    if ((int)s->n_rounds >= s->max_planes) {  // this library's cap; the reference has none
+      s->stopped_by = PFT_ROUNDS_STOP_MAX_PLANES;
+      break;
+    }
+    const uint32_t rd = (uint32_t)s->n_rounds;
+    const uint32_t nt = (remaining + SG_TILE - 1) / SG_TILE;
+    SgHyp hyp = s->hyp;
+    hyp.sample += 3 * (size_t)rd * s->hmax;
+    hyp.coef += (size_t)rd * s->hmax;
+    hyp.count += (size_t)rd * s->hmax;
+    hipLaunchKernelGGL(k_sg_round_begin, dim3(1), dim3(64), 0, st, s->hdr, remaining);
+    MARK(ST_COMPACT);
+    r = plane_stage(s, pr, hyp, pts[cur], remaining, nt);
+    if (r != PFT_OK) return r;
+    // the round's final inliers leave the cloud (ExtractIndices negative): marked in rnd, the rest compacted
+    hipLaunchKernelGGL(k_sg_select, dim3(nt), dim3(SG_THREADS), 0, st, pr, (const SgHdr*)s->hdr, 1,
+                       (const float4*)pts[cur], b.flag, b.tile, b.flag2, b.tile2);
+    hipLaunchKernelGGL(k_sg_round_mark, dim3((remaining + SG_THREADS - 1) / SG_THREADS), dim3(SG_THREADS), 0, st,
+                       (const SgHdr*)s->hdr, (const uint8_t*)b.flag, (const uint32_t*)idx[cur], b.rnd, rd);
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, nt, &s->hdr->n_valid, &s->hdr->n_fin);
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile2, nt, &s->hdr->n_valid, &s->hdr->n_surv);
+    hipLaunchKernelGGL(k_sg_emit, dim3(nt), dim3(SG_THREADS), 0, st, b.flag2, remaining, &s->hdr->n_valid, b.tile2,
+                       (const uint32_t*)idx[cur], idx[cur ^ 1], (const float4*)pts[cur], pts[cur ^ 1]);
+    MARK(ST_COMPACT);
+    r = read_hdr(s);
+    if (r != PFT_OK) return r;
+    MARK(-1);
+    if (H->err & SG_ERR_MAP) {
+      s->err = "RANSAC: the sparse map of drawIndexSample's swaps is full (too many degenerate samples)";
+      return PFT_ERR_CAPACITY;
+    }
+    s->rounds.push_back(*H);
+    s->n_rounds++;
+    if (H->best_h < 0 || H->n_fin == 0) {  // the reference's break: nothing is removed
+      s->stopped_by = PFT_ROUNDS_STOP_NO_PLANE;
+      break;
+    }
+    s->n_planes++;
+    remaining = H->n_surv;
+    cur ^= 1;
+  }
+  // stages 4 + 5 see the remaining cloud with no plane left to remove
+  hipLaunchKernelGGL(k_sg_round_begin, dim3(1), dim3(64), 0, st, s->hdr, remaining);
+  MARK(ST_COMPACT);
+  *cpts = pts[cur];
+  *cidx = idx[cur];
+  *n_left = remaining;
   return PFT_OK;
 }
 
@@ -1152,39 +1465,31 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
                      (const uint32_t*)nullptr, b.comp_idx, b.tx, b.comp_pts);
   MARK(ST_COMPACT);
   const uint32_t* n_valid = &s->hdr->n_valid;
-  if (c.plane_enable) {
-    // 3. RANSAC in batches; every launch after the deciding batch returns at once
-    SCHK(s, hipMemsetAsync(s->hyp.count, 0, s->hmax * sizeof(uint32_t), st));
-    const uint32_t nscore = (n + SG_THREADS * SG_SCORE_PTS - 1) / (SG_THREADS * SG_SCORE_PTS);
-    for (uint32_t bt = 0; bt * SG_BATCH < s->hmax; bt++) {
-      hipLaunchKernelGGL(k_sg_sample, dim3(1), dim3(SG_THREADS), 0, st, p, s->hdr, s->smp, s->hyp,
-                         (const float4*)b.comp_pts, bt);
-      MARK(ST_SAMPLE);
-      hipLaunchKernelGGL(k_sg_score, dim3(nscore), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, s->hyp,
-                         (const float4*)b.comp_pts, bt);
-      MARK(ST_SCORE);
-      hipLaunchKernelGGL(k_sg_replay, dim3(1), dim3(64), 0, st, p, s->hdr, s->hyp, bt);
-      MARK(ST_REPLAY);
-    }
-    // inliers of the best hypothesis, refit, final inliers + survivors
-    hipLaunchKernelGGL(k_sg_select, dim3(ntiles), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, 0,
-                       (const float4*)b.comp_pts, b.flag, b.tile, (uint8_t*)nullptr, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles, n_valid, &s->hdr->n_ransac_inl);
-    hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag, n, n_valid, b.tile,
-                       (const uint32_t*)nullptr, b.inl_idx, (const float4*)nullptr, (float4*)nullptr);
-    hipLaunchKernelGGL(k_sg_refit, dim3(1), dim3(SG_REFIT_THREADS), 0, st, p, s->hdr, c.optimize_coefficients,
-                       (const float4*)b.comp_pts, (const uint32_t*)b.inl_idx);
-    MARK(ST_REFIT);
+  // the cloud stages 4 + 5 read: the removeZeroPoints output, or what the plane rounds left of it
+  const float4* cpts = b.comp_pts;
+  const uint32_t* cidx = b.comp_idx;
+  uint32_t n45 = n, ntiles45 = ntiles;
+  s->rounds.clear();
+  s->n_rounds = s->n_planes = 0;
+  s->stopped_by = PFT_ROUNDS_STOP_FRACTION;
+  s->by_rounds = c.plane_enable && !(s->max_planes == 1 && s->min_fraction == 0.0);
+  if (c.plane_enable && !s->by_rounds) {
+    int r = plane_stage(s, p, s->hyp, b.comp_pts, n, ntiles);
+    if (r != PFT_OK) return r;
+  } else if (c.plane_enable) {
+    int r = plane_rounds(s, p, n, &cpts, &cidx, &n45);
+    if (r != PFT_OK) return r;
+    ntiles45 = std::max((n45 + SG_TILE - 1) / SG_TILE, 1u);  // (nothing left: the kernels see n_valid = 0)
   }
   // 4 + 5: ExtractIndices negative, PassThrough box (no plane: every point is a non-inlier)
-  hipLaunchKernelGGL(k_sg_select, dim3(ntiles), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, 1,
-                     (const float4*)b.comp_pts, b.flag, b.tile, b.flag2, b.tile2);
-  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles, n_valid, &s->hdr->n_fin);
-  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag, n, n_valid, b.tile,
-                     (const uint32_t*)b.comp_idx, b.fin_idx, (const float4*)nullptr, (float4*)nullptr);
-  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile2, ntiles, n_valid, &s->hdr->n_surv);
-  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, b.flag2, n, n_valid, b.tile2,
-                     (const uint32_t*)b.comp_idx, b.surv_in, (const float4*)b.comp_pts, b.spts);
+  hipLaunchKernelGGL(k_sg_select, dim3(ntiles45), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr, 1, cpts, b.flag,
+                     b.tile, b.flag2, b.tile2);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile, ntiles45, n_valid, &s->hdr->n_fin);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles45), dim3(SG_THREADS), 0, st, b.flag, n45, n_valid, b.tile, cidx, b.fin_idx,
+                     (const float4*)nullptr, (float4*)nullptr);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, b.tile2, ntiles45, n_valid, &s->hdr->n_surv);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles45), dim3(SG_THREADS), 0, st, b.flag2, n45, n_valid, b.tile2, cidx, b.surv_in,
+                     cpts, b.spts);
   const uint32_t nbparts = 1024;
   hipLaunchKernelGGL(k_sg_bounds, dim3(nbparts), dim3(SG_THREADS), 0, st, (const SgHdr*)s->hdr, (const float4*)b.spts,
                      b.bpart);
@@ -1287,6 +1592,21 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
   s->res = *H;
   s->res.n_clusters = nc;
   s->res.n_total = total;
+  if (!s->by_rounds) {  // the single plane: one round, told by the same rule
+    s->rounds.assign(1, s->res);
+    const bool ran = c.plane_enable && H->n_valid > 0;
+    const bool removed = ran && H->best_h >= 0 && H->n_fin > 0;
+    s->n_rounds = ran ? 1 : 0;
+    s->n_planes = removed ? 1 : 0;
+    s->stopped_by = !ran ? PFT_ROUNDS_STOP_FRACTION
+                         : (!removed ? PFT_ROUNDS_STOP_NO_PLANE
+                                     : (H->n_valid > H->n_fin ? PFT_ROUNDS_STOP_MAX_PLANES : PFT_ROUNDS_STOP_FRACTION));
+  } else if (s->rounds.empty()) {  // no round ran: round 0 reports the cloud and no plane
+    SgHdr z = {};
+    z.best_h = -1;
+    z.n_valid = H->n_valid;
+    s->rounds.assign(1, z);
+  }
   s->last_ms = 0.0;
   for (int k = 0; k < PFT_SEGMENT_STAGES; k++) s->stage_ms[k] = 0.0;
   for (int e = 1; e < s->nev; e++) {
@@ -1308,6 +1628,10 @@ static int apply_common(pft_segment* s, const pft_point_xyzrgba* pts, size_t n, 
     s->res = SgHdr();
     s->res.best_h = -1;
     s->sizes.clear();
+    s->rounds.assign(1, s->res);
+    s->by_rounds = false;
+    s->n_rounds = s->n_planes = 0;
+    s->stopped_by = PFT_ROUNDS_STOP_FRACTION;
     s->n_in = 0;
     s->last_ms = 0.0;
     for (int k = 0; k < PFT_SEGMENT_STAGES; k++) s->stage_ms[k] = 0.0;
@@ -1335,13 +1659,19 @@ extern "C" int pft_segment_apply_device(pft_segment* s, const pft_point_xyzrgba*
   return apply_common(s, device_points, n, true);
 }
 
-extern "C" int pft_segment_get_plane(const pft_segment* s, pft_segment_plane* pl) {
+static int bad_round(const pft_segment* s, const char* fn) {
+  const_cast<pft_segment*>(s)->err = std::string(fn) + ": round is not below the number of rounds the last apply ran";
+  return PFT_ERR_INVALID_ARG;
+}
+
+extern "C" int pft_segment_get_plane_round(const pft_segment* s, size_t round, pft_segment_plane* pl) {
   if (!s || !pl) return PFT_ERR_INVALID_ARG;
   if (!s->have_result) return PFT_ERR_STATE;
-  const SgHdr& h = s->res;
+  if (round >= s->rounds.size()) return bad_round(s, "pft_segment_get_plane_round");
+  const SgHdr& h = s->rounds[round];
   memset(pl, 0, sizeof(*pl));
   pl->n_valid = h.n_valid;
-  pl->n_survivors = h.n_surv;
+  pl->n_survivors = s->res.n_surv;
   if (!s->cfg.plane_enable) {
     pl->status = PFT_PLANE_DISABLED;
     return PFT_OK;
@@ -1362,12 +1692,17 @@ extern "C" int pft_segment_get_plane(const pft_segment* s, pft_segment_plane* pl
   pl->inliers = h.n_fin;
   int32_t smp[3];
   pft_segment* sm = const_cast<pft_segment*>(s);
-  if (hipMemcpy(smp, s->hyp.sample + 3 * (size_t)h.best_h, sizeof(smp), hipMemcpyDeviceToHost) != hipSuccess) {
+  if (hipMemcpy(smp, s->hyp.sample + 3 * ((size_t)round * s->hmax + (size_t)h.best_h), sizeof(smp),
+                hipMemcpyDeviceToHost) != hipSuccess) {
     sm->err = "hipMemcpy of the best sample failed";
     return PFT_ERR_HIP;
   }
   for (int k = 0; k < 3; k++) pl->sample[k] = smp[k];
   return PFT_OK;
+}
+
+extern "C" int pft_segment_get_plane(const pft_segment* s, pft_segment_plane* pl) {
+  return pft_segment_get_plane_round(s, 0, pl);
 }
 
 // the best hypothesis' inliers are kept as compacted indices; mapped to the input on the way out
@@ -1377,17 +1712,34 @@ __global__ void k_sg_map_idx(uint32_t n, const uint32_t* __restrict__ idx, const
   if (i < n) out[i] = (int32_t)map[idx[i]];
 }
 
-extern "C" int pft_segment_get_plane_inliers(pft_segment* s, int which, int32_t* host_idx, size_t capacity, size_t* n) {
+extern "C" int pft_segment_get_plane_round_inliers(pft_segment* s, size_t round, int which, int32_t* host_idx,
+                                                   size_t capacity, size_t* n) {
   if (!s || !n || (which != 0 && which != 1)) return PFT_ERR_INVALID_ARG;
   if (!s->have_result) return PFT_ERR_STATE;
-  const bool have = s->cfg.plane_enable && s->res.best_h >= 0;
-  const uint32_t cnt = !have ? 0u : (which == 0 ? s->res.n_fin : s->res.n_ransac_inl);
+  if (round >= s->rounds.size()) return bad_round(s, "pft_segment_get_plane_round_inliers");
+  const SgHdr& h = s->rounds[round];
+  const bool have = s->cfg.plane_enable && h.best_h >= 0;
+  const uint32_t cnt = !have ? 0u : (which == 0 ? h.n_fin : h.n_ransac_inl);
   *n = cnt;
   if (cnt > capacity) return PFT_ERR_CAPACITY;
   if (!cnt) return PFT_OK;
   if (!host_idx) return PFT_ERR_INVALID_ARG;
   const int32_t* src = reinterpret_cast<const int32_t*>(s->b.fin_idx);
-  if (which == 1) {  // crank is scratch once an apply has finished
+  if (s->by_rounds) {  // re-derived from the per-point round byte; flag, tile and crank are scratch after an apply
+    const uint32_t nin = (uint32_t)s->n_in, nt = (nin + SG_TILE - 1) / SG_TILE;
+    int32_t* tmp = reinterpret_cast<int32_t*>(s->b.crank);
+    const float4 cf = make_float4(h.coef_ransac[0], h.coef_ransac[1], h.coef_ransac[2], h.coef_ransac[3]);
+    hipLaunchKernelGGL(k_sg_round_flags, dim3(nt), dim3(SG_THREADS), 0, s->stream, nin, (const uint8_t*)s->b.rnd,
+                       (const float4*)s->b.tx, (uint32_t)round, which, cf, float_bound_below(s->cfg.distance_threshold),
+                       s->b.flag, s->b.tile);
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, s->stream, s->b.tile, nt, (const uint32_t*)nullptr,
+                       &s->hdr->n_total);
+    hipLaunchKernelGGL(k_sg_emit, dim3(nt), dim3(SG_THREADS), 0, s->stream, (const uint8_t*)s->b.flag, nin,
+                       (const uint32_t*)nullptr, (const uint32_t*)s->b.tile, (const uint32_t*)nullptr,
+                       reinterpret_cast<uint32_t*>(tmp), (const float4*)nullptr, (float4*)nullptr);
+    SCHK(s, hipGetLastError());
+    src = tmp;
+  } else if (which == 1) {  // crank is scratch once an apply has finished
     int32_t* tmp = reinterpret_cast<int32_t*>(s->b.crank);
     hipLaunchKernelGGL(k_sg_map_idx, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, cnt,
                        (const uint32_t*)s->b.inl_idx, (const uint32_t*)s->b.comp_idx, tmp);
@@ -1396,6 +1748,66 @@ extern "C" int pft_segment_get_plane_inliers(pft_segment* s, int which, int32_t*
   }
   SCHK(s, hipMemcpyAsync(host_idx, src, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
   SCHK(s, hipStreamSynchronize(s->stream));
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_get_plane_inliers(pft_segment* s, int which, int32_t* host_idx, size_t capacity, size_t* n) {
+  return pft_segment_get_plane_round_inliers(s, 0, which, host_idx, capacity, n);
+}
+
+extern "C" int pft_segment_set_plane_rounds(pft_segment* s, int max_planes, double min_remaining_fraction) {
+  if (!s) return PFT_ERR_INVALID_ARG;
+  if (max_planes < 1 || max_planes > PFT_SEGMENT_MAX_PLANES) {
+    s->err = "pft_segment_set_plane_rounds: max_planes must be 1 .. PFT_SEGMENT_MAX_PLANES (16)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (!(min_remaining_fraction >= 0.0 && min_remaining_fraction <= 1.0)) {
+    s->err = "pft_segment_set_plane_rounds: min_remaining_fraction must be within [0, 1]";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if ((uint32_t)max_planes > s->hyp_rounds) {  // one set of hypothesis buffers per round
+    SCHK(s, hipSetDevice(s->cfg.device_id));
+    SCHK(s, hipStreamSynchronize(s->stream));
+    SgHyp nh = {};
+    const size_t cnt = (size_t)s->hmax * (size_t)max_planes;
+    if (salloc(&nh.sample, 3 * cnt) != hipSuccess || salloc(&nh.coef, cnt) != hipSuccess ||
+        salloc(&nh.count, cnt) != hipSuccess) {
+      sfree(nh.sample); sfree(nh.coef); sfree(nh.count);
+      s->err = "pft_segment_set_plane_rounds: hipMalloc of the rounds' hypothesis buffers failed";
+      return PFT_ERR_HIP;
+    }
+    sfree(s->hyp.sample); sfree(s->hyp.coef); sfree(s->hyp.count);
+    s->hyp = nh;
+    s->hyp_rounds = (uint32_t)max_planes;
+    s->have_result = false;  // the last apply's hypotheses went with the old buffers
+  }
+  s->max_planes = max_planes;
+  s->min_fraction = min_remaining_fraction;
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_get_plane_rounds(const pft_segment* s, int* max_planes, double* min_remaining_fraction) {
+  if (!s) return PFT_ERR_INVALID_ARG;
+  if (max_planes) *max_planes = s->max_planes;
+  if (min_remaining_fraction) *min_remaining_fraction = s->min_fraction;
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_set_refit_order(pft_segment* s, int order) {
+  if (!s) return PFT_ERR_INVALID_ARG;
+  if (order != PFT_SUM_PCL && order != PFT_SUM_TREE) {
+    s->err = "pft_segment_set_refit_order: order must be PFT_SUM_PCL or PFT_SUM_TREE";
+    return PFT_ERR_INVALID_ARG;
+  }
+  s->refit_order = order;
+  return PFT_OK;
+}
+
+extern "C" int pft_segment_plane_count(const pft_segment* s, size_t* n_planes, int* stopped_by) {
+  if (!s) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  if (n_planes) *n_planes = s->n_planes;
+  if (stopped_by) *stopped_by = s->stopped_by;
   return PFT_OK;
 }
 
@@ -1454,14 +1866,20 @@ extern "C" int pft_segment_last_ms(const pft_segment* s, double* ms, double* sta
 
 extern "C" int pft_debug_segment_hypotheses(pft_segment* s, int32_t* samples, uint32_t* counts, size_t capacity,
                                             size_t* n) {
+  return pft_debug_segment_round_hypotheses(s, 0, samples, counts, capacity, n);
+}
+
+extern "C" int pft_debug_segment_round_hypotheses(pft_segment* s, size_t round, int32_t* samples, uint32_t* counts,
+                                                  size_t capacity, size_t* n) {
   if (!s || !n) return PFT_ERR_INVALID_ARG;
   if (!s->have_result) return PFT_ERR_STATE;
-  const size_t cnt = s->cfg.plane_enable ? s->res.iterations : 0;
+  if (round >= s->rounds.size()) return bad_round(s, "pft_debug_segment_round_hypotheses");
+  const size_t cnt = s->cfg.plane_enable ? s->rounds[round].iterations : 0, off = round * (size_t)s->hmax;
   *n = cnt;
   if (cnt > capacity) return PFT_ERR_CAPACITY;
   if (!cnt) return PFT_OK;
   if (!samples || !counts) return PFT_ERR_INVALID_ARG;
-  SCHK(s, hipMemcpy(samples, s->hyp.sample, 3 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
-  SCHK(s, hipMemcpy(counts, s->hyp.count, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  SCHK(s, hipMemcpy(samples, s->hyp.sample + 3 * off, 3 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  SCHK(s, hipMemcpy(counts, s->hyp.count + off, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return PFT_OK;
 }

@@ -6,6 +6,8 @@
 //
 // pft::ModelSegmenter is the fused pipeline (transform, removeZeroPoints, plane, ExtractIndices negative, PassThrough
 // box, clustering) of one device handle.  All compute happens in the HIP library; failures throw std::runtime_error.
+// setPlaneRounds makes it the loop of test/cluster_euclid.cpp:59-85 and test/cluster_extraction.cpp: planes are removed
+// one after the other while more than a fraction of the points is left.
 #pragma once
 #include <stdexcept>
 #include <string>
@@ -55,6 +57,22 @@ class ModelSegmenter {
     cfg_.box_max[axis] = hi;
   }
 
+  // planes are removed one after the other while (double)remaining > min_remaining_fraction * (double)n_valid and
+  // fewer than max_planes (1 .. PFT_SEGMENT_MAX_PLANES) rounds ran: cluster_euclid.cpp runs (no cap, 0.3)
+  void setPlaneRounds(int max_planes, double min_remaining_fraction) {
+    if (max_planes < 1 || max_planes > PFT_SEGMENT_MAX_PLANES || !(min_remaining_fraction >= 0.0 && min_remaining_fraction <= 1.0))
+      throw std::invalid_argument("setPlaneRounds: max_planes 1 .. 16, min_remaining_fraction within [0, 1]");
+    max_planes_ = max_planes;
+    min_fraction_ = min_remaining_fraction;
+    if (h_) check(pft_segment_set_plane_rounds(h_, max_planes_, min_fraction_), "pft_segment_set_plane_rounds");
+  }
+  // PFT_SUM_PCL (default): the refit's serial float sums; PFT_SUM_TREE: pair trees over many workgroups
+  void setRefitOrder(int order) {
+    if (order != PFT_SUM_PCL && order != PFT_SUM_TREE) throw std::invalid_argument("setRefitOrder: PFT_SUM_PCL or PFT_SUM_TREE");
+    refit_order_ = order;
+    if (h_) check(pft_segment_set_refit_order(h_, refit_order_), "pft_segment_set_refit_order");
+  }
+
   void setInputCloud(const PointCloud<PointXYZRGBA>::ConstPtr& cloud) {
     input_ = cloud;
     dev_in_ = nullptr;
@@ -66,7 +84,11 @@ class ModelSegmenter {
   }
 
   void apply() {
-    if (!h_) check(pft_segment_create(&cfg_, &h_), "pft_segment_create");
+    if (!h_) {
+      check(pft_segment_create(&cfg_, &h_), "pft_segment_create");
+      check(pft_segment_set_plane_rounds(h_, max_planes_, min_fraction_), "pft_segment_set_plane_rounds");
+      check(pft_segment_set_refit_order(h_, refit_order_), "pft_segment_set_refit_order");
+    }
     if (dev_in_)
       check(pft_segment_apply_device(h_, dev_in_, dev_n_), "pft_segment_apply_device");
     else if (input_)
@@ -79,6 +101,32 @@ class ModelSegmenter {
     pft_segment_plane p;
     check(pft_segment_get_plane(h_, &p), "pft_segment_get_plane");
     return p;
+  }
+  // planes the last apply removed / why the rounds ended (PFT_ROUNDS_STOP_*)
+  size_t planeCount() {
+    size_t n = 0;
+    check(pft_segment_plane_count(h_, &n, nullptr), "pft_segment_plane_count");
+    return n;
+  }
+  int stoppedBy() {
+    int why = 0;
+    check(pft_segment_plane_count(h_, nullptr, &why), "pft_segment_plane_count");
+    return why;
+  }
+  // the record of one round: n_valid is the round's cloud size, sample indexes the round's cloud
+  pft_segment_plane plane(size_t round) {
+    pft_segment_plane p;
+    check(pft_segment_get_plane_round(h_, round, &p), "pft_segment_get_plane_round");
+    return p;
+  }
+  // a round's inliers, indices into the input cloud: which = 0 the final ones, 1 those of the best hypothesis
+  void planeInliers(size_t round, PointIndices& inliers, int which = 0) {
+    const pft_segment_plane p = plane(round);
+    std::vector<int32_t> idx(p.status == PFT_PLANE_FOUND ? (which == 0 ? p.inliers : p.ransac_inliers) : 0);
+    size_t n = 0;
+    check(pft_segment_get_plane_round_inliers(h_, round, which, idx.data(), idx.size(), &n),
+          "pft_segment_get_plane_round_inliers");
+    inliers.indices.assign(idx.begin(), idx.begin() + n);
   }
   // the final plane inliers, indices into the input cloud
   void planeInliers(PointIndices& inliers) {
@@ -131,6 +179,9 @@ class ModelSegmenter {
 
  private:
   pft_segment* h_ = nullptr;
+  int max_planes_ = 1;  // handle settings: applied to every handle apply() creates
+  double min_fraction_ = 0.0;
+  int refit_order_ = PFT_SUM_PCL;
   PointCloud<PointXYZRGBA>::ConstPtr input_;
   const pft_point_xyzrgba* dev_in_ = nullptr;
   size_t dev_n_ = 0;

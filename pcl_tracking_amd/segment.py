@@ -7,7 +7,8 @@ create_model.cpp:131-179), over the C ABI of include/pft_segment.h.  All compute
     ec.setMaxClusterSize(25000); ec.setInputCloud(cloud); clusters = ec.extract()
 
 ModelSegmenter is the fused pipeline (transform, removeZeroPoints, plane, ExtractIndices negative, PassThrough box,
-clustering) of one handle; `make_planar_segmenter` / `make_box_segmenter` configure it as the two reference nodes."""
+clustering) of one handle; `make_planar_segmenter` / `make_box_segmenter` configure it as the two reference nodes,
+`make_scene_segmenter` as the plane-after-plane loop of test/cluster_euclid.cpp:59-85 and test/cluster_extraction.cpp."""
 import ctypes as C
 
 import numpy as np
@@ -35,13 +36,27 @@ class ModelSegmenter:
         self._h = None
         self._cloud = None
         self._dev = None
+        self._rounds = (1, 0.0)  # pft_segment_set_plane_rounds / _set_refit_order: applied to every handle created
+        self._refit_order = _lib.PFT_SUM_PCL
         self.configure(**cfg)
 
     def configure(self, transform=None, plane=None, max_iterations=None, distance_threshold=None, probability=None,
-                  optimize=None, box=None, box_enable=None, tolerance=None, min_size=None, max_size=None):
+                  optimize=None, box=None, box_enable=None, tolerance=None, min_size=None, max_size=None,
+                  plane_rounds=None, refit_order=None):
         """transform: 4x4 camera->base (None keeps, False disables); box: (xmin, xmax, ymin, ymax, zmin, zmax);
-        box_enable: three flags"""
+        box_enable: three flags; plane_rounds: (max_planes, min_remaining_fraction), planes are removed one after the
+        other while more than the fraction of the points is left; refit_order: "pcl" (serial float sums) or "tree"
+        (adjacent-pair trees over many workgroups)"""
         c = self._cfg
+        if plane_rounds is not None:
+            mx, frac = plane_rounds
+            if not 1 <= int(mx) <= _lib.SEGMENT_MAX_PLANES or not 0.0 <= float(frac) <= 1.0:
+                raise PftError(1, "plane_rounds: max_planes 1 .. %d, fraction within [0, 1]" % _lib.SEGMENT_MAX_PLANES)
+            self._rounds = (int(mx), float(frac))
+        if refit_order is not None:
+            if refit_order not in ("pcl", "tree"):
+                raise PftError(1, "refit_order: 'pcl' or 'tree'")
+            self._refit_order = _lib.PFT_SUM_TREE if refit_order == "tree" else _lib.PFT_SUM_PCL
         if transform is not None:
             if transform is False:
                 c.transform_enable = 0
@@ -89,6 +104,8 @@ class ModelSegmenter:
             if st != 0:
                 raise PftError(st, "pft_segment_create")
             self._h = h
+            self._check(self._L.pft_segment_set_plane_rounds(h, self._rounds[0], self._rounds[1]))
+            self._check(self._L.pft_segment_set_refit_order(h, self._refit_order))
 
     def close(self):
         if getattr(self, "_h", None) is not None:
@@ -120,9 +137,22 @@ class ModelSegmenter:
             raise PftError(2, "apply() without an input cloud")
 
     # -- results of the last apply --
-    def plane(self):
+    def planeCount(self):
+        """planes the last apply removed"""
+        n = C.c_size_t()
+        self._check(self._L.pft_segment_plane_count(self._h, C.byref(n), None))
+        return n.value
+
+    def stoppedBy(self):
+        """why the plane rounds ended: _lib.ROUNDS_STOP_FRACTION / _NO_PLANE / _MAX_PLANES"""
+        why = C.c_int()
+        self._check(self._L.pft_segment_plane_count(self._h, None, C.byref(why)))
+        return why.value
+
+    def plane(self, round=0):
+        """the record of one round (n_valid = the round's cloud size, sample indexes the round's cloud)"""
         pl = SegmentPlane()
-        self._check(self._L.pft_segment_get_plane(self._h, C.byref(pl)))
+        self._check(self._L.pft_segment_get_plane_round(self._h, round, C.byref(pl)))
         return {
             "status": pl.status, "n_valid": pl.n_valid, "coefficients": np.array(pl.coefficients, np.float32),
             "ransac_coefficients": np.array(pl.ransac_coefficients, np.float32), "sample": list(pl.sample),
@@ -130,15 +160,15 @@ class ModelSegmenter:
             "hypotheses_scored": pl.hypotheses_scored, "n_survivors": pl.n_survivors,
         }
 
-    def planeInliers(self, which=0):
+    def planeInliers(self, which=0, round=0):
         """indices into the input cloud: which = 0 final inliers, 1 the best RANSAC hypothesis' inliers"""
         n = C.c_size_t()
-        pl = self.plane()
+        pl = self.plane(round)
         cnt = pl["inliers"] if which == 0 else pl["ransac_inliers"]
         if pl["status"] != _lib.PLANE_FOUND:
             cnt = 0
         idx = np.zeros(cnt, np.int32)
-        self._check(self._L.pft_segment_get_plane_inliers(self._h, which, _ptr(idx), cnt, C.byref(n)))
+        self._check(self._L.pft_segment_get_plane_round_inliers(self._h, round, which, _ptr(idx), cnt, C.byref(n)))
         return idx[: n.value]
 
     def clusterSizes(self):
@@ -163,15 +193,16 @@ class ModelSegmenter:
             o += int(s)
         return out
 
-    def hypotheses(self):
-        """(samples int32[n, 3], counts uint32[n]) in draw order, n = RANSAC iterations"""
+    def hypotheses(self, round=0):
+        """(samples int32[n, 3], counts uint32[n]) in draw order, n = RANSAC iterations of the round"""
         n = C.c_size_t()
-        st = self._L.pft_debug_segment_hypotheses(self._h, None, None, 0, C.byref(n))
+        st = self._L.pft_debug_segment_round_hypotheses(self._h, round, None, None, 0, C.byref(n))
         if st not in (0, 6):
             self._check(st)
         smp = np.zeros((n.value, 3), np.int32)
         cnt = np.zeros(n.value, np.uint32)
-        self._check(self._L.pft_debug_segment_hypotheses(self._h, _ptr(smp), _ptr(cnt), n.value, C.byref(n)))
+        self._check(self._L.pft_debug_segment_round_hypotheses(self._h, round, _ptr(smp), _ptr(cnt), n.value,
+                                                               C.byref(n)))
         return smp, cnt
 
     def lastMilliseconds(self):
@@ -193,6 +224,16 @@ def make_box_segmenter(**kw):
     """create_model.cpp: no plane, PassThrough z, y, x"""
     s = ModelSegmenter(**kw)
     s.configure(plane=False, box_enable=(1, 1, 1))
+    return s
+
+
+def make_scene_segmenter(**kw):
+    """test/cluster_euclid.cpp:59-85 and test/cluster_extraction.cpp: planes (100 iterations, 0.02 m) are removed until
+    at most 30 % of the points are left, no box, then clusters at 0.02 m with 10 .. 2 500 points.  The reference's loop
+    has no cap on the rounds; here it is PFT_SEGMENT_MAX_PLANES, and stoppedBy() tells when it was reached."""
+    s = ModelSegmenter(**kw)
+    s.configure(plane=True, max_iterations=100, distance_threshold=0.02, plane_rounds=(_lib.SEGMENT_MAX_PLANES, 0.3),
+                box_enable=(0, 0, 0), tolerance=0.02, min_size=10, max_size=2500)
     return s
 
 
