@@ -119,13 +119,31 @@ int pft_set_input(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n);
 /* same, for a cloud already resident in HBM (device pointer, PCL layout; borrowed until the next
  * pft_set_input* call) */
 int pft_set_input_device(pft_tracker* t, const void* device_pts, size_t n);
+/* same, for the output of an input filter (pft_filters.h) whose apply may still be running: the tracker borrows the
+ * filter's output cloud and the DEVICE word that holds its count, and its stream waits for the apply with an event --
+ * no host count, no host wait.  Works after pft_filter_apply* and pft_filter_apply*_async alike.
+ *   max_points bounds the count: buffers and the grids of the launches that follow the input size (the crop, the
+ *   leaf gather of the octree builder, the exact-NN grid, the sorted builder) are sized by it.  0 = the size of the
+ *   apply's input, which the output can never exceed.
+ *   A device count above the bound: the first crop reads max_points points only, and the next call that synchronises
+ *   returns PFT_ERR_CAPACITY (pft_last_error_string names pft_set_input_from_filter).  A device count of zero: the
+ *   iterations run as with an empty crop, and the next call that synchronises returns PFT_ERR_NO_INPUT.
+ *   The filter's output is read by the first crop of the frame only (pft_compute or pft_eval_weights), which copies what
+ *   later crops need; the filter's next apply waits (on the device) for that crop of every tracker that borrowed the
+ *   output.  An apply issued BEFORE that crop was enqueued invalidates the hand-off: the compute then returns
+ *   PFT_ERR_NO_INPUT.  Either handle may be destroyed first.
+ *   PFT_ERR_INVALID_ARG with a text: a sharded handle (world_size > 1), a filter on another device.  PFT_ERR_STATE: the
+ *   filter has not been applied yet.  With PFT_GRAPH=1 such a frame is launched directly. */
+struct pft_filter;
+int pft_set_input_from_filter(pft_tracker* t, struct pft_filter* f, size_t max_points);
 /* tracker_->compute() :693 -- first call runs initParticles; then iteration_num x
  * [resample, weight, update].  Asynchronous on the handle's stream. */
 int pft_compute(pft_tracker* t);
 /* tracker_->getResult() :309 -- synchronises the stream.  Like every call that synchronises (pft_get_particles,
  * pft_get_fit_ratio, pft_synchronize, pft_eval_weights) it also reports device-side failures of the iterations run
  * since the last such call: PFT_ERR_CAPACITY (octree node capacity, depth or bounding-box growth steps exceeded) or
- * PFT_ERR_HIP (the one-pass crop gave up waiting), pft_last_error_string naming the flag.  The affected iteration ran
+ * PFT_ERR_HIP (the one-pass crop gave up waiting), pft_last_error_string naming the flag; after
+ * pft_set_input_from_filter also PFT_ERR_CAPACITY / PFT_ERR_NO_INPUT for a device-side input count above its bound / of zero.  The affected iteration ran
  * without a target cloud (all likelihoods zero), so the pose returned with the error is the unweighted particle mean;
  * the flags are per iteration and the next pft_compute starts clean.  (PCL's compute() is void; the reference's caller
  * wraps it in try / catch, auto_tracking.cpp:692-696.) */
@@ -221,6 +239,9 @@ int pft_eval_weights(pft_tracker* t, const pft_particle* particles, size_t P, fl
                      float* nn_d2);
 int pft_debug_get_bbox(pft_tracker* t, float bbox[6]); /* x_min,x_max,y_min,y_max,z_min,z_max */
 int pft_debug_get_crop(pft_tracker* t, int32_t* idx, size_t cap, size_t* n);
+/* test hook: the handle's 16-byte input records [first, first + n) (x, y, z, rgba bits), as the first crop of a frame
+ * forms them; PFT_ERR_CAPACITY past the handle's input capacity */
+int pft_debug_get_input_records(pft_tracker* t, void* out, size_t first, size_t n);
 int pft_debug_get_octree(pft_tracker* t, int32_t* depth, double min_xyz[3], double max_xyz[3], uint32_t* n_leaves,
                          uint32_t* n_nodes);
 int pft_debug_get_point_keys(pft_tracker* t, uint32_t* keys3, size_t cap_points);

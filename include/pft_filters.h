@@ -55,6 +55,14 @@ const char* pft_filter_last_error_string(const pft_filter* f);
  * output count is known (one stream synchronisation); the output cloud is then valid in HBM. */
 int pft_filter_apply(pft_filter* f, const pft_point_xyzrgba* host_points, size_t n);
 int pft_filter_apply_device(pft_filter* f, const pft_point_xyzrgba* device_points, size_t n);
+/* The same pipeline (the same launches: the calls above are these followed by the wait), enqueued on the handle's stream
+ * without waiting for it.  The host cloud may be reused as soon as the call returns (its upload is the one thing waited
+ * for); the device cloud is borrowed until the apply has finished on the device.  The accessors below wait for a pending
+ * apply the first time one of them is called after it; pft_set_input_from_filter (pft.h) hands the output to a tracker
+ * without any wait.  A VoxelGrid leaf too small for the cloud hands the input through, decided on the device.  n == 0
+ * is the empty result, on the host, at once. */
+int pft_filter_apply_async(pft_filter* f, const pft_point_xyzrgba* host_points, size_t n);
+int pft_filter_apply_device_async(pft_filter* f, const pft_point_xyzrgba* device_points, size_t n);
 
 /* n_pass: points that survived PassThrough (all finite-or-not points when it is disabled);
  * n_out: points of the output cloud */

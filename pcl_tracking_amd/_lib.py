@@ -108,6 +108,7 @@ SYMBOLS = [
     ("pft_set_trans", C.c_int, [_vp, _vp]),
     ("pft_set_input", C.c_int, [_vp, _vp, _sz]),
     ("pft_set_input_device", C.c_int, [_vp, _vp, _sz]),
+    ("pft_set_input_from_filter", C.c_int, [_vp, _vp, _sz]),
     ("pft_compute", C.c_int, [_vp]),
     ("pft_get_result", C.c_int, [_vp, _vp]),
     ("pft_get_particles", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
@@ -124,6 +125,7 @@ SYMBOLS = [
     ("pft_eval_weights", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
     ("pft_debug_get_bbox", C.c_int, [_vp, _vp]),
     ("pft_debug_get_crop", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_debug_get_input_records", C.c_int, [_vp, _vp, _sz, _sz]),
     ("pft_debug_get_octree", C.c_int, [_vp, _P(_i32), _vp, _vp, _P(_u32), _P(_u32)]),
     ("pft_debug_get_point_keys", C.c_int, [_vp, _vp, _sz]),
     ("pft_debug_get_scan_stats", C.c_int, [_vp, _P(_u64), _P(_u64)]),
@@ -167,6 +169,8 @@ SYMBOLS = [
     ("pft_filter_last_error_string", C.c_char_p, [_vp]),
     ("pft_filter_apply", C.c_int, [_vp, _vp, _sz]),
     ("pft_filter_apply_device", C.c_int, [_vp, _vp, _sz]),
+    ("pft_filter_apply_async", C.c_int, [_vp, _vp, _sz]),
+    ("pft_filter_apply_device_async", C.c_int, [_vp, _vp, _sz]),
     ("pft_filter_counts", C.c_int, [_vp, _P(_sz), _P(_sz)]),
     ("pft_filter_output_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
     ("pft_filter_get_output", C.c_int, [_vp, _vp, _sz, _P(_sz)]),

@@ -51,6 +51,13 @@ struct pft_tracker {
   float4* d_in_pts = nullptr;
   uint32_t in_cap = 0, N = 0;
   const pft_point_xyzrgba* raw_pending = nullptr;  // input handed over but not yet packed: the next crop does it
+  // pft_set_input_from_filter: the frame's input count lives on the device.  N is then its bound; the first crop reads
+  // the count from n_src (the filter's word), latches it into d_n_in for the later crops and records borrow->ev
+  bool n_on_device = false;
+  const uint32_t* n_src = nullptr;
+  uint32_t* d_n_in = nullptr;
+  PftBorrow* borrow = nullptr;  // the link to the filter last borrowed from (shared with it)
+  const pft_filter* borrow_of = nullptr;
   pft_particle* d_part[2] = {nullptr, nullptr};
   int cur = 0;
   float* d_mats = nullptr;
@@ -355,6 +362,7 @@ static void sync_dev(pft_tracker* t) {
   d.ref_hsv = t->d_ref_hsv;
   d.in_pts = t->d_in_pts;
   d.N = t->N;
+  d.n_dev = t->n_on_device ? t->d_n_in : nullptr;
   d.part_cur = t->d_part[t->cur];
   d.part_all = t->bound_gathered ? static_cast<pft_particle*>(t->bound_gathered) : t->d_part[t->cur];
   d.mats = t->d_mats;
@@ -437,7 +445,13 @@ static int check_device_error(pft_tracker* t) {
     m += " [bit5] the change detector's octree outgrew 21-bit keys or its growth steps per test (PFT_MAX_GROW 40): that "
          "iteration evaluated as if the scene had changed, and the detector forgot its previous crop (its box is never reset: "
          "once deeper than 21 levels, every later test does the same);";
-  if (e & ~55u) m += " [other] " + std::to_string(e & ~55u) + ";";
+  if (e & 64u)
+    m += " [bit6] pft_set_input_from_filter: the filter's output count on the device exceeded max_points; the crop read "
+         "max_points points only;";
+  if (e & 128u)
+    m += " [bit7] pft_set_input_from_filter: the filter's output count on the device was zero (no input cloud): the "
+         "iterations ran with an empty crop;";
+  if (e & ~247u) m += " [other] " + std::to_string(e & ~247u) + ";";
   if (e & 7u) m += " the iteration(s) with bit0-2 ran without a target cloud (all likelihoods zero)";
   if (e & 16u) {  // the barrier counters of an interrupted launch are cleared before the next one (the launch resets them itself
                   // when all its workgroups get through; this covers a launch that did not)
@@ -445,7 +459,8 @@ static int check_device_error(pft_tracker* t) {
     hipMemsetAsync(reinterpret_cast<char*>(t->d_hdr) + offsetof(PftHeader, pop_bar), 0, sizeof(((PftHeader*)nullptr)->pop_bar), t->stream);
   }
   t->err = m;
-  return (e & (4u | 16u)) ? PFT_ERR_HIP : PFT_ERR_CAPACITY;
+  if (e & (4u | 16u)) return PFT_ERR_HIP;
+  return (e & 128u) && !(e & ~128u) ? PFT_ERR_NO_INPUT : PFT_ERR_CAPACITY;
 }
 
 static int ensure_input_capacity(pft_tracker* t, uint32_t n) {
@@ -688,9 +703,25 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   return PFT_OK;
 }
 
+// gives up the link to a filter (the stream has drained, or the link's event has been waited for, when this is called
+// for good); the filter frees a link it finds abandoned, an abandoned filter's link is freed here
+static void release_borrow(pft_tracker* t) {
+  PftBorrow* b = t->borrow;
+  t->borrow = nullptr;
+  if (!b) return;
+  b->tracker_alive = false;
+  b->armed = false;
+  if (!b->filter_alive) {
+    hipEventDestroy(b->ev);
+    delete b;
+  }
+}
+
 extern "C" void pft_destroy(pft_tracker* t) {
   if (!t) return;
   if (t->stream) hipStreamSynchronize(t->stream);
+  release_borrow(t);
+  dfree(t->d_n_in);
   if (t->graph_exec) hipGraphExecDestroy(t->graph_exec);
   for (int k = 0; k < PFT_K_COUNT; k++)
     for (auto& p : t->ev[k]) {
@@ -848,6 +879,9 @@ static int set_input_common(pft_tracker* t, const void* src, size_t n, bool devi
     if (r != PFT_OK) return r;
   }
   t->N = (uint32_t)n;
+  t->n_on_device = false;
+  t->n_src = nullptr;
+  if (t->borrow) t->borrow->armed = false;
   if (n) {
     const pft_point_xyzrgba* dsrc = static_cast<const pft_point_xyzrgba*>(src);
     if (!device) {
@@ -869,6 +903,60 @@ extern "C" int pft_set_input(pft_tracker* t, const pft_point_xyzrgba* pts, size_
 }
 extern "C" int pft_set_input_device(pft_tracker* t, const void* device_pts, size_t n) {
   return set_input_common(t, device_pts, n, true);
+}
+
+extern "C" int pft_set_input_from_filter(pft_tracker* t, pft_filter* f, size_t max_points) {
+  if (!t || !f) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size > 1) {
+    t->err = "pft_set_input_from_filter on a sharded handle (world_size > 1): every rank needs the same host-side count";
+    return PFT_ERR_INVALID_ARG;
+  }
+  PftFilterView v;
+  if (pftf_view(f, &v) != PFT_OK) {
+    t->err = "pft_set_input_from_filter: the filter has not been applied yet";
+    return PFT_ERR_STATE;
+  }
+  if (v.device_id != t->cfg.device_id) {
+    t->err = "pft_set_input_from_filter: the filter lives on device " + std::to_string(v.device_id) + ", the tracker on device " +
+             std::to_string(t->cfg.device_id) + " (a filter on another device)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  const size_t bound = max_points ? max_points : v.n_in;
+  if (bound == 0) return set_input_common(t, nullptr, 0, true);  // an apply over no points: no input cloud
+  if (bound > 0x7fffffffu) return PFT_ERR_CAPACITY;
+  hipSetDevice(t->cfg.device_id);
+  int r = ensure_input_capacity(t, (uint32_t)bound);
+  if (r != PFT_OK) return r;
+  if (t->cd_ever && t->cd.b.cap < t->in_cap) {
+    r = cd_reserve(t, t->cd, t->in_cap, false);
+    if (r != PFT_OK) return r;
+  }
+  if (!t->d_n_in) {
+    HIPCHK(t, dalloc(&t->d_n_in, 1));
+    HIPCHK(t, hipMemsetAsync(t->d_n_in, 0, sizeof(uint32_t), t->stream));
+  }
+  if (!t->borrow || !t->borrow->filter_alive || t->borrow_of != f) {
+    release_borrow(t);
+    PftBorrow* b = new PftBorrow();
+    if (hipEventCreateWithFlags(&b->ev, hipEventDisableTiming) != hipSuccess) {
+      delete b;
+      t->err = "pft_set_input_from_filter: hipEventCreateWithFlags failed";
+      return PFT_ERR_HIP;
+    }
+    t->borrow = b;
+    t->borrow_of = f;
+    pftf_attach(f, b);
+  }
+  t->borrow->armed = true;
+  t->borrow->valid = true;
+  HIPCHK(t, hipStreamWaitEvent(t->stream, v.done, 0));  // the apply, however far it has got
+  t->N = (uint32_t)bound;
+  t->n_on_device = true;
+  t->n_src = v.n_out_dev;
+  t->raw_pending = v.out;
+  t->has_input = true;
+  sync_dev(t);
+  return PFT_OK;
 }
 
 // ---- the stages ----
@@ -937,8 +1025,15 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
   {
     ProfScope ps(t, PFT_K_CROP);
     if (++t->crop_epoch == 0) t->crop_epoch = 1;
-    pftk_crop(t->stream, t->prm, d, bbox_from_partials, t->crop_epoch, t->raw_pending, t->sw.crop_two_pass);
+    const bool from_filter = t->n_on_device && t->raw_pending;
+    pftk_crop(t->stream, t->prm, d, bbox_from_partials, t->crop_epoch, t->raw_pending, t->sw.crop_two_pass,
+              from_filter ? t->n_src : nullptr);
     t->raw_pending = nullptr;
+    if (from_filter && t->borrow) {  // the filter's output and count word have been read: its next apply waits for this
+      hipEventRecord(t->borrow->ev, t->stream);
+      t->borrow->recorded = true;
+      t->borrow->armed = false;
+    }
     if (t->inject_error & ~16u) {  // test hook: what a failing crop / builder would leave behind (bit 4 belongs to the
                                    // population launch: pft_compute raises it there)
       hipLaunchKernelGGL(k_inject_error, dim3(1), dim3(1), 0, t->stream, t->d_hdr, t->inject_error & ~16u);
@@ -1067,6 +1162,13 @@ static int check_ready(pft_tracker* t) {
   if (!t) return PFT_ERR_INVALID_ARG;
   hipSetDevice(t->cfg.device_id);
   if (!t->has_input || t->N == 0) return PFT_ERR_NO_INPUT;  // PCL: PCL_ERROR + early return
+  if (t->n_on_device && t->raw_pending && !(t->borrow && t->borrow->valid)) {
+    // the filter was applied again, grew or was destroyed before this frame's first crop: its output is not this frame's
+    t->err = "the filter handed over by pft_set_input_from_filter was applied again or destroyed before the frame's first crop";
+    t->has_input = false;
+    t->raw_pending = nullptr;
+    return PFT_ERR_NO_INPUT;
+  }
   if (!t->has_ref) return PFT_ERR_NO_REFERENCE;
   return PFT_OK;
 }
@@ -1113,7 +1215,10 @@ extern "C" int pft_compute(pft_tracker* t) {
       if (!t->cd_ever) t->cd_counter = t->cd_counter == 0u ? t->cd_interval : t->cd_counter - 1u;
     }
   };
-  const bool graphed = t->use_graph && !t->cfg.exact_nearest && t->changed && !t->prof && t->graph_frames++ >= 2u;
+  // (a frame whose input count lives on the device is launched directly: its first crop carries the filter's pointers
+  // and is followed by an event record, neither of which belongs into the replayed graph)
+  const bool graphed = t->use_graph && !t->cfg.exact_nearest && t->changed && !t->prof && !t->n_on_device &&
+                       t->graph_frames++ >= 2u;
   if (!graphed) {
     run_iterations();
   } else {
@@ -1507,6 +1612,15 @@ extern "C" int pft_debug_get_crop(pft_tracker* t, int32_t* idx, size_t cap, size
   if (idx && c) {
     HIPCHK(t, hipMemcpy(idx, t->d_crop_idx, c * sizeof(int32_t), hipMemcpyDeviceToHost));
   }
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_get_input_records(pft_tracker* t, void* out, size_t first, size_t n) {
+  if (!t || (!out && n)) return PFT_ERR_INVALID_ARG;
+  if (first + n > t->in_cap) return PFT_ERR_CAPACITY;
+  hipSetDevice(t->cfg.device_id);
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  if (n) HIPCHK(t, hipMemcpy(out, t->d_in_pts + first, n * sizeof(float4), hipMemcpyDeviceToHost));
   return PFT_OK;
 }
 

@@ -22,6 +22,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "pft_device_utils.h"
 #include "../../include/pft_filters.h"
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(1024) void k_f_scan_small(FParams p, FDev d, uint32
   uint32_t n_out = n_pass, n_trig = 0, n_present = 0;
   if (p.mode == PFT_VOXEL_EXACT) {
     n_out = scan_array(d.tile_head, ntiles, scr);
-    if (d.hdr->leaf_too_small) n_out = 0;
+    if (d.hdr->leaf_too_small) n_out = p.n;  // the input is handed through (k_f_emit_exact copies it)
   }
   if (threadIdx.x == 0) {
     d.hdr->n_pass = n_pass;
@@ -759,7 +760,21 @@ __global__ __launch_bounds__(FE_THREADS) void k_f_emit_exact(FParams p, FDev d, 
   __shared__ uint32_t sfirst[2];
   const uint32_t t = blockIdx.x, base = t * FE_TILE, tid = threadIdx.x;
   const uint32_t nv = d.hdr->n_pass;
-  if (base >= nv || d.hdr->leaf_too_small) return;
+  if (d.hdr->leaf_too_small) {
+    // PCL warns "Leaf size is too small for the input dataset" and hands the input cloud through unchanged: decided
+    // here, on the device, so that an apply nobody waits for ends with the same output and count
+    for (uint32_t k = 0; k < FE_TILE / FE_THREADS; k++) {
+      const uint32_t i = base + k * FE_THREADS + tid;
+      if (i < p.n) {
+        const float4* q = reinterpret_cast<const float4*>(d.in + i);
+        float4* o = reinterpret_cast<float4*>(d.out + i);
+        o[0] = q[0];
+        o[1] = q[1];
+      }
+    }
+    return;
+  }
+  if (base >= nv) return;
   const uint32_t cnt_tile = min(FE_TILE, nv - base);
 #pragma unroll
   for (uint32_t k = 0; k < FE_TILE / FE_THREADS; k++) {
@@ -910,9 +925,13 @@ struct pft_filter {
   pft_point_xyzrgba* d_in_own = nullptr;
   FDev d = {};
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_copy = nullptr;  // end of the upload of a host cloud
   size_t n_in = 0, n_pass = 0, n_out = 0;
   int leaf_too_small = 0;
   bool have_result = false;
+  bool pending = false;  // an apply is enqueued and its counts have not been read yet (wait_pending)
+  bool applied = false;  // the device-side output and count word belong to an apply (pft_set_input_from_filter)
+  std::vector<PftBorrow*> borrows;  // trackers that read the output on the device (pft_internal.h)
   bool tile_pass_scanned = false;
   double last_ms = 0.0;
 };
@@ -935,9 +954,34 @@ static void free_buffers(pft_filter* f) {
   f->cap = 0;
 }
 
+// The trackers that borrowed the output (pft_set_input_from_filter) read it in the first crop of their frame and record
+// an event behind that launch.  Before the output is overwritten the filter's stream waits for those events; before it
+// is freed the host does (host_wait).  A tracker that has not enqueued that crop yet loses the frame: its hand-off is
+// invalidated and its next compute reports it.  Links whose tracker is gone are dropped here.
+static void settle_borrows(pft_filter* f, bool host_wait) {
+  size_t keep = 0;
+  for (PftBorrow* b : f->borrows) {
+    if (b->armed) b->valid = false;
+    if (b->recorded) {
+      if (host_wait)
+        hipEventSynchronize(b->ev);
+      else
+        hipStreamWaitEvent(f->stream, b->ev, 0);
+    }
+    if (b->tracker_alive) {
+      f->borrows[keep++] = b;
+    } else {  // (a wait already enqueued on the stream keeps what it needs of a destroyed event)
+      hipEventDestroy(b->ev);
+      delete b;
+    }
+  }
+  f->borrows.resize(keep);
+}
+
 static int ensure_capacity(pft_filter* f, size_t n) {
   if (n <= f->cap) return PFT_OK;
   if (f->stream) FCHK(f, hipStreamSynchronize(f->stream));
+  settle_borrows(f, true);
   free_buffers(f);
   size_t cap = n < 1024 ? 1024 : n;
   cap = (cap + 1023) / 1024 * 1024;
@@ -1006,6 +1050,7 @@ extern "C" int pft_filter_create(const pft_filter_config* cfg, pft_filter** out)
     f->own_stream = true;
   }
   bool ok = hipEventCreate(&f->ev0) == hipSuccess && hipEventCreate(&f->ev1) == hipSuccess &&
+            hipEventCreateWithFlags(&f->ev_copy, hipEventDisableTiming) == hipSuccess &&
             falloc(&f->d.bucket, F_MAX_HIST + 1) == hipSuccess && falloc(&f->d.hdr, 1) == hipSuccess &&
             hipHostMalloc(reinterpret_cast<void**>(&f->d.host_stat), 4 * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess;
   if (ok) ok = hipMemset(f->d.hdr, 0, sizeof(FHdr)) == hipSuccess;
@@ -1020,13 +1065,21 @@ extern "C" int pft_filter_create(const pft_filter_config* cfg, pft_filter** out)
 
 extern "C" void pft_filter_destroy(pft_filter* f) {
   if (!f) return;
+  hipSetDevice(f->cfg.device_id);
   if (f->stream) hipStreamSynchronize(f->stream);
+  settle_borrows(f, true);  // no tracker is still reading the output; hand-offs not yet consumed are invalidated
+  for (PftBorrow* b : f->borrows) {
+    b->filter_alive = false;
+    b->valid = false;
+  }
+  f->borrows.clear();
   free_buffers(f);
   ffree(f->d.bucket);
   ffree(f->d.hdr);
   if (f->d.host_stat) hipHostFree(f->d.host_stat);
   if (f->ev0) hipEventDestroy(f->ev0);
   if (f->ev1) hipEventDestroy(f->ev1);
+  if (f->ev_copy) hipEventDestroy(f->ev_copy);
   if (f->own_stream && f->stream) hipStreamDestroy(f->stream);
   delete f;
 }
@@ -1090,56 +1143,99 @@ static int run_pipeline(pft_filter* f, const pft_point_xyzrgba* d_in, size_t n) 
   }
   FCHK(f, hipEventRecord(f->ev1, s));
   FCHK(f, hipGetLastError());
-  FCHK(f, hipStreamSynchronize(s));
-  float ms = 0.0f;
-  FCHK(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
-  f->last_ms = ms;
   f->n_in = n;
-  f->n_pass = f->d.host_stat[0];
-  f->n_out = f->d.host_stat[1];
-  f->leaf_too_small = (int)f->d.host_stat[2];
-  f->have_result = true;
-  if (f->leaf_too_small) {
-    // PCL warns "Leaf size is too small for the input dataset" and hands the input cloud through unchanged
-    FCHK(f, hipMemcpyAsync(f->d.out, d_in, n * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToDevice, s));
-    FCHK(f, hipStreamSynchronize(s));
-    f->n_out = n;
-  }
+  f->pending = true;
+  f->applied = true;
   return PFT_OK;
 }
 
-static int apply_common(pft_filter* f, const pft_point_xyzrgba* pts, size_t n, bool on_device) {
+// the one host wait of an apply: the stream drains, the counts come out of the pinned status words
+static int wait_pending(pft_filter* f) {
+  if (!f->pending) return PFT_OK;
+  FCHK(f, hipSetDevice(f->cfg.device_id));
+  FCHK(f, hipStreamSynchronize(f->stream));
+  f->pending = false;
+  float ms = 0.0f;
+  FCHK(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+  f->last_ms = ms;
+  f->n_pass = f->d.host_stat[0];
+  f->n_out = f->d.host_stat[1];  // (a leaf size too small for the cloud: the input's count, decided by k_f_scan_small)
+  f->leaf_too_small = (int)f->d.host_stat[2];
+  f->have_result = true;
+  return PFT_OK;
+}
+static int wait_pending(const pft_filter* f) { return wait_pending(const_cast<pft_filter*>(f)); }
+
+// enqueue only: the upload (host clouds), the pipeline and the end event.  wait == false returns as soon as a host
+// cloud has been read (its upload is the only thing waited for); wait == true is the same call followed by wait_pending
+static int apply_common(pft_filter* f, const pft_point_xyzrgba* pts, size_t n, bool on_device, bool wait) {
   if (!f || (!pts && n)) return PFT_ERR_INVALID_ARG;
   if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
   f->have_result = false;
+  f->pending = false;  // (a pending apply nobody asked about is superseded in stream order)
   FCHK(f, hipSetDevice(f->cfg.device_id));
   if (n == 0) {  // empty input cloud: empty output
+    settle_borrows(f, false);
+    FCHK(f, hipMemsetAsync(&f->d.hdr->n_out, 0, sizeof(uint32_t), f->stream));  // the count a tracker would read on the device
+    FCHK(f, hipEventRecord(f->ev1, f->stream));
     f->n_in = f->n_pass = f->n_out = 0;
     f->leaf_too_small = 0;
     f->last_ms = 0.0;
     f->have_result = true;
+    f->applied = true;
     return PFT_OK;
   }
   int r = ensure_capacity(f, n);
   if (r != PFT_OK) return r;
+  settle_borrows(f, false);  // the output is about to be overwritten
   const pft_point_xyzrgba* d_in = pts;
   if (!on_device) {
     FCHK(f, hipMemcpyAsync(f->d_in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, f->stream));
+    FCHK(f, hipEventRecord(f->ev_copy, f->stream));
     d_in = f->d_in_own;
   }
-  return run_pipeline(f, d_in, n);
+  r = run_pipeline(f, d_in, n);
+  if (r != PFT_OK) return r;
+  if (wait) return wait_pending(f);
+  if (!on_device) FCHK(f, hipEventSynchronize(f->ev_copy));  // the caller's buffer is only borrowed for this call
+  return PFT_OK;
 }
 
 extern "C" int pft_filter_apply(pft_filter* f, const pft_point_xyzrgba* host_points, size_t n) {
-  return apply_common(f, host_points, n, false);
+  return apply_common(f, host_points, n, false, true);
 }
 
 extern "C" int pft_filter_apply_device(pft_filter* f, const pft_point_xyzrgba* device_points, size_t n) {
-  return apply_common(f, device_points, n, true);
+  return apply_common(f, device_points, n, true, true);
+}
+
+extern "C" int pft_filter_apply_async(pft_filter* f, const pft_point_xyzrgba* host_points, size_t n) {
+  return apply_common(f, host_points, n, false, false);
+}
+
+extern "C" int pft_filter_apply_device_async(pft_filter* f, const pft_point_xyzrgba* device_points, size_t n) {
+  return apply_common(f, device_points, n, true, false);
+}
+
+int pftf_view(pft_filter* f, PftFilterView* v) {
+  if (!f->applied) return PFT_ERR_STATE;
+  v->out = f->d.out;
+  v->n_out_dev = &f->d.hdr->n_out;
+  v->n_in = f->n_in;
+  v->device_id = f->cfg.device_id;
+  v->done = f->ev1;
+  return PFT_OK;
+}
+void pftf_attach(pft_filter* f, PftBorrow* b) {
+  for (PftBorrow* q : f->borrows)
+    if (q == b) return;
+  f->borrows.push_back(b);
 }
 
 extern "C" int pft_filter_counts(const pft_filter* f, size_t* n_pass, size_t* n_out) {
   if (!f) return PFT_ERR_INVALID_ARG;
+  int r = wait_pending(f);
+  if (r != PFT_OK) return r;
   if (!f->have_result) return PFT_ERR_STATE;
   if (n_pass) *n_pass = f->n_pass;
   if (n_out) *n_out = f->n_out;
@@ -1148,6 +1244,8 @@ extern "C" int pft_filter_counts(const pft_filter* f, size_t* n_pass, size_t* n_
 
 extern "C" int pft_filter_output_device(const pft_filter* f, const pft_point_xyzrgba** device_points, size_t* n_out) {
   if (!f || !device_points || !n_out) return PFT_ERR_INVALID_ARG;
+  int r = wait_pending(f);
+  if (r != PFT_OK) return r;
   if (!f->have_result) return PFT_ERR_STATE;
   *device_points = f->d.out;
   *n_out = f->n_out;
@@ -1156,6 +1254,8 @@ extern "C" int pft_filter_output_device(const pft_filter* f, const pft_point_xyz
 
 extern "C" int pft_filter_get_output(pft_filter* f, pft_point_xyzrgba* host_out, size_t capacity, size_t* n_out) {
   if (!f || !n_out) return PFT_ERR_INVALID_ARG;
+  int r = wait_pending(f);
+  if (r != PFT_OK) return r;
   if (!f->have_result) return PFT_ERR_STATE;
   *n_out = f->n_out;
   if (f->n_out > capacity) return PFT_ERR_CAPACITY;
@@ -1169,6 +1269,8 @@ extern "C" int pft_filter_get_output(pft_filter* f, pft_point_xyzrgba* host_out,
 
 extern "C" int pft_filter_get_pass_indices(pft_filter* f, int32_t* host_idx, size_t capacity, size_t* n_pass) {
   if (!f || !n_pass) return PFT_ERR_INVALID_ARG;
+  int r = wait_pending(f);
+  if (r != PFT_OK) return r;
   if (!f->have_result) return PFT_ERR_STATE;
   *n_pass = f->n_pass;
   if (f->n_pass > capacity) return PFT_ERR_CAPACITY;
@@ -1189,6 +1291,8 @@ extern "C" int pft_filter_get_pass_indices(pft_filter* f, int32_t* host_idx, siz
 
 extern "C" int pft_filter_last_ms(const pft_filter* f, double* ms) {
   if (!f || !ms) return PFT_ERR_INVALID_ARG;
+  int r = wait_pending(f);
+  if (r != PFT_OK) return r;
   if (!f->have_result) return PFT_ERR_STATE;
   *ms = f->last_ms;
   return PFT_OK;

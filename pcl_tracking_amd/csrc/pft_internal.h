@@ -93,7 +93,8 @@ struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (
                     // too few -> the rescue launch rebuilds, bit4 a device-scope barrier of the population kernel timed out,
                     // bit5 the change detector's depth (21) or growth steps exceeded -- raised in the pinned status block
                     // only (host_stat[2..3]): every stage reads a non-zero word here as "no target", and that iteration
-                    // evaluates
+                    // evaluates; bit6 / bit7 a device-side input count above its bound / of zero (first crop of a frame),
+                    // in the pinned status block only as well
   double omin[3], omax[3];
   int32_t depth;
   int32_t use_table;
@@ -159,7 +160,9 @@ struct PftDev {  // device pointers (host-side struct, passed by value)
   const float4* ref_hsv;
   const float4* ref_box;    // [M_box] {x, y, z, .} of the box's support subset
   const float4* in_pts;
-  uint32_t N;
+  uint32_t N;               // input points; with n_dev an upper bound on them (grids and buffers are sized by it)
+  const uint32_t* n_dev;    // the input count lives on the device (pft_set_input_from_filter): the handle's own copy of it,
+                            // latched by the first crop of the frame; else null
   pft_particle* part_cur;   // shard being evaluated
   pft_particle* part_all;   // all P particles (== part_cur when world_size == 1)
   float* mats;
@@ -259,6 +262,28 @@ struct PftChangeArgs {
 void pftk_change_detect(hipStream_t s, const PftChangeBufs& b, const float4* pts, const uint32_t* n_ptr, uint32_t n,
                         const PftChangeArgs& a, uint32_t* host_stat);
 
+// ---- device-side hand-off from an input filter to a tracker (pft_set_input_from_filter) ----
+// One link per tracker and filter, shared by the two handles; the handle that finds the other one gone frees it.
+struct PftBorrow {
+  hipEvent_t ev = nullptr;   // recorded by the tracker right behind the first crop of a frame: the only launch that reads the
+                             // filter's output and count word
+  bool recorded = false;     // ev has been recorded at least once
+  bool armed = false;        // handed over, that crop not enqueued yet
+  bool valid = false;        // cleared when the filter overwrites or frees its output while the link is armed
+  bool tracker_alive = true, filter_alive = true;
+};
+struct pft_filter;
+struct PftFilterView {
+  const pft_point_xyzrgba* out;  // the output cloud in HBM
+  const uint32_t* n_out_dev;     // the device word that holds its count
+  size_t n_in;                   // points the apply ran over: the count can never exceed it
+  int device_id;
+  hipEvent_t done;               // recorded on the filter's stream behind the apply
+};
+// pft_filters.hip: PFT_ERR_STATE before the first apply
+int pftf_view(pft_filter* f, PftFilterView* v);
+void pftf_attach(pft_filter* f, PftBorrow* b);
+
 // The result-neutral path switches (A/B timing and cross-checks; README "Environment switches").  pft_create reads them
 // once, with pft_read_switches, and keeps them on the handle: the launchers take the decisions as plain arguments.
 enum class PftExactPath { sorted, per_query, shells };  // exact-NN search: cell-sorted lists, lists per query, shells only
@@ -284,7 +309,8 @@ void pftk_report(hipStream_t s, const pft_point_xyzrgba* pts, uint32_t n, const 
                  pft_point_xyzrgba* tracked, pft_object_report* out);
 void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, int argorder, float4* xyz,
                          float4* hsv);
-void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out);
+void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out,
+                     const uint32_t* n_dev = nullptr);
 void pftk_init_particles(hipStream_t s, const PftParams& p, pft_particle rep, pft_particle* out, float* mats,
                          PftHeader* hdr);
 void pftk_resample(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t epoch, pft_particle* out, bool one_lane);
@@ -306,8 +332,11 @@ void pftk_resample_kld(hipStream_t s, const PftParams& p, const PftDev& d, uint3
                        const int32_t* table_a, const double* table_q, int32_t* bins_out);
 // epoch: a value that differs from the handle's previous crop launch (non-zero); tags the per-workgroup counts of the one-pass crop
 // raw: the input in PCL's 32-byte layout when its 16-byte records have not been formed yet (first crop of a frame), else null
+// n_src (with d.n_dev, first crop of a frame): the device word the live input count is read from; the crop latches
+// min(count, d.N) into d.n_dev for the frame's later crops and raises bit 6 (count above d.N) or bit 7 (count zero) in
+// the pinned status block.  Null: the count is d.n_dev's (or, without one, d.N)
 void pftk_crop(hipStream_t s, const PftParams& p, const PftDev& d, bool bbox_from_partials, uint32_t epoch,
-               const pft_point_xyzrgba* raw, bool two_pass);
+               const pft_point_xyzrgba* raw, bool two_pass, const uint32_t* n_src = nullptr);
 // the single-workgroup builder; indirect: no leaf_pts copies, the likelihood kernel follows leaf_order (its INDIRECT form)
 void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect);
 // no-op launch unless the sorted builder flagged "radix passes too few" (error bit 3): then the single-workgroup build

@@ -14,8 +14,10 @@ __global__ void k_pack_reference(const pft_point_xyzrgba* __restrict__ pts, uint
                        (float)((k >> 16) & 0xff) / 255.0f, 0.0f);
 }
 
-__global__ void k_pack_input(const pft_point_xyzrgba* __restrict__ pts, uint32_t n, float4* __restrict__ out) {
+__global__ void k_pack_input(const pft_point_xyzrgba* __restrict__ pts, uint32_t n, float4* __restrict__ out,
+                             const uint32_t* __restrict__ n_dev) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n_dev) n = min(*n_dev, n);  // the input count lives on the device; n bounds it (the grid's size)
   if (i >= n) return;
   // 32-byte PCL point -> 16-byte record; two dwordx4 loads per lane, one dwordx4 store
   const float4* src = reinterpret_cast<const float4*>(pts + i);
@@ -388,13 +390,28 @@ __device__ __forceinline__ bool crop_keep(float4 p, const float* b6) {
   return fin && !(p.x < xmin || p.x > b6[3]) && !(p.y < ymin || p.y > b6[4]) && !(p.z < zmin || p.z > b6[5]);
 }
 
+// First crop of a frame whose input count lives on the device: the count the frame's later crops read (the source word
+// belongs to the filter, which may overwrite it once this launch is through), and the two conditions the host cannot
+// see beforehand, raised in the pinned status block only (the iteration itself is well defined in both cases)
+__device__ __forceinline__ void crop_latch_count(const uint32_t* n_dev, uint32_t n_bound, uint32_t* n_latch,
+                                                 uint32_t* host_stat) {
+  const uint32_t c = *n_dev;
+  *n_latch = min(c, n_bound);
+  const uint32_t e = (c > n_bound ? 64u : 0u) | (c == 0u ? 128u : 0u);
+  if (e && host_stat) {
+    host_stat[2] = e;
+    host_stat[3] |= e;
+  }
+}
+
 template <bool FROM_PART>
 __global__ __launch_bounds__(1024) void k_crop_count(const float4* __restrict__ in, uint32_t N,
                                                      const float* __restrict__ bbox6,
                                                      const float* __restrict__ part, uint32_t nparts,
-                                                     uint32_t* __restrict__ counts) {
+                                                     uint32_t* __restrict__ counts, const uint32_t* __restrict__ n_dev) {
   __shared__ uint32_t s_cnt[16];
   __shared__ float s6[6];
+  if (n_dev) N = min(*n_dev, N);  // the input count lives on the device; N bounds it (workgroups past it count zero)
   if (FROM_PART) {
     reduce_partials(part, nparts, s6);
   } else if (threadIdx.x < 6) {
@@ -420,10 +437,13 @@ __global__ __launch_bounds__(1024) void k_crop_scatter(const float4* __restrict_
                                                        const float* __restrict__ part, uint32_t nparts,
                                                        const uint32_t* __restrict__ counts, int argorder,
                                                        float4* __restrict__ out, int32_t* __restrict__ out_idx,
-                                                       PftHeader* __restrict__ hdr, uint32_t* host_stat) {
+                                                       PftHeader* __restrict__ hdr, uint32_t* host_stat,
+                                                       const uint32_t* __restrict__ n_dev, uint32_t* __restrict__ n_latch) {
   __shared__ uint32_t s_scan[20];
   __shared__ uint32_t s_base;
   __shared__ float s6[6];
+  const uint32_t n_bound = N;
+  if (n_dev) N = min(*n_dev, N);
   if (FROM_PART) {
     reduce_partials(part, nparts, s6);
   } else if (threadIdx.x < 6) {
@@ -454,6 +474,7 @@ __global__ __launch_bounds__(1024) void k_crop_scatter(const float4* __restrict_
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x < PFT_LIK_GROUPS) hdr->lik_ctr[threadIdx.x * PFT_LIK_CTR_STRIDE] = 0u;
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    if (n_latch) crop_latch_count(n_dev, n_bound, n_latch, host_stat);
     hdr->n_crop = s_base + total;
     if (host_stat) host_stat[0] = s_base + total;
     hdr->bbox[0] = -s6[0]; hdr->bbox[1] = s6[3];
@@ -476,10 +497,20 @@ __global__ __launch_bounds__(1024) void k_crop_onepass(const float4* __restrict_
                                                        uint32_t epoch, int argorder, float4* __restrict__ out,
                                                        int32_t* __restrict__ out_idx, PftHeader* __restrict__ hdr,
                                                        uint32_t* host_stat, const pft_point_xyzrgba* __restrict__ raw,
-                                                       float4* __restrict__ packed) {
+                                                       float4* __restrict__ packed, const uint32_t* __restrict__ n_dev,
+                                                       uint32_t* __restrict__ n_latch) {
   __shared__ uint32_t s_scan[20];
   __shared__ uint32_t s_base, s_b;
   __shared__ float s6[6];
+  // n_dev != null: the input count lives on the device and N only bounds it.  The grid follows the bound; the workgroups
+  // whose ticket lies past the live count take it and leave (they neither publish a slot nor wait for one), the last LIVE
+  // one writes the results, the holder of the last ticket of the GRID resets the counter
+  const uint32_t n_bound = N;
+  uint32_t nl = gridDim.x;
+  if (n_dev) {
+    N = min(*n_dev, N);
+    nl = max((N + 1023u) >> 10, 1u);
+  }
   if (threadIdx.x == 0) {
     s_b = atomicAdd(&hdr->crop_ticket, 1u);
     // error flags are per iteration: the first workgroup of the launch clears them (a later workgroup raises bit 2 only
@@ -493,6 +524,10 @@ __global__ __launch_bounds__(1024) void k_crop_onepass(const float4* __restrict_
   }
   __syncthreads();
   const uint32_t b = s_b, nb = gridDim.x;
+  if (b >= nl) {  // (only with a device count)
+    if (b == nb - 1 && threadIdx.x == 0) atomicExch(&hdr->crop_ticket, 0u);
+    return;
+  }
   const uint32_t i = b * blockDim.x + threadIdx.x;
   bool keep = false;
   float4 p = make_float4(0, 0, 0, 0);
@@ -537,9 +572,10 @@ __global__ __launch_bounds__(1024) void k_crop_onepass(const float4* __restrict_
     out[s_base + pos] = make_float4(p.x, p.y, p.z, __uint_as_float(kk));
     out_idx[s_base + pos] = (int32_t)i;
   }
-  if (b == nb - 1 && threadIdx.x < PFT_LIK_GROUPS) hdr->lik_ctr[threadIdx.x * PFT_LIK_CTR_STRIDE] = 0u;
-  if (b == nb - 1 && threadIdx.x == 0) {
-    atomicExch(&hdr->crop_ticket, 0u);  // every workgroup of this launch has taken its ticket by now
+  if (b == nl - 1 && threadIdx.x < PFT_LIK_GROUPS) hdr->lik_ctr[threadIdx.x * PFT_LIK_CTR_STRIDE] = 0u;
+  if (b == nl - 1 && threadIdx.x == 0) {
+    if (b == nb - 1) atomicExch(&hdr->crop_ticket, 0u);  // every workgroup of this launch has taken its ticket by now
+    if (n_latch) crop_latch_count(n_dev, n_bound, n_latch, host_stat);
     hdr->n_crop = s_base + total;
     if (host_stat) host_stat[0] = s_base + total;
     hdr->bbox[0] = -s6[0]; hdr->bbox[1] = s6[3];
@@ -603,9 +639,9 @@ void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t
   if (!n) return;
   hipLaunchKernelGGL(k_pack_reference, dim3(cdiv(n, 256)), dim3(256), 0, s, d_pts, n, argorder, xyz, hsv);
 }
-void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out) {
+void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out, const uint32_t* n_dev) {
   if (!n) return;
-  hipLaunchKernelGGL(k_pack_input, dim3(cdiv(n, 256)), dim3(256), 0, s, d_pts, n, out);
+  hipLaunchKernelGGL(k_pack_input, dim3(cdiv(n, 256)), dim3(256), 0, s, d_pts, n, out, n_dev);
 }
 void pftk_init_particles(hipStream_t s, const PftParams& p, pft_particle rep, pft_particle* out, float* mats,
                          PftHeader* hdr) {
@@ -677,29 +713,34 @@ void pftk_bbox_final(hipStream_t s, const PftDev& d) {
   hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(512), 0, s, d.bbox_part, d.bbox_grid, d.bbox6);
 }
 void pftk_crop(hipStream_t s, const PftParams& p, const PftDev& d, bool from_part, uint32_t epoch,
-               const pft_point_xyzrgba* raw, bool two_pass) {
+               const pft_point_xyzrgba* raw, bool two_pass, const uint32_t* n_src) {
   uint32_t nb = cdiv(d.N ? d.N : 1, 1024);
   float4* packed = const_cast<float4*>(d.in_pts);
+  // a device-side input count: read from n_src and latched into d.n_dev by the frame's first crop, from d.n_dev after it
+  const uint32_t* n_dev = d.n_dev ? (n_src ? n_src : d.n_dev) : nullptr;
+  uint32_t* n_latch = d.n_dev && n_src ? const_cast<uint32_t*>(d.n_dev) : nullptr;
   if (!two_pass) {
     if (from_part)
       hipLaunchKernelGGL(k_crop_onepass<true>, dim3(nb), dim3(1024), 0, s, d.in_pts, d.N, d.bbox6, d.bbox_part, d.bbox_grid,
-                         d.crop_slots, epoch, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat, raw, packed);
+                         d.crop_slots, epoch, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat, raw, packed, n_dev,
+                         n_latch);
     else
       hipLaunchKernelGGL(k_crop_onepass<false>, dim3(nb), dim3(1024), 0, s, d.in_pts, d.N, d.bbox6, d.bbox_part, d.bbox_grid,
-                         d.crop_slots, epoch, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat, raw, packed);
+                         d.crop_slots, epoch, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat, raw, packed, n_dev,
+                         n_latch);
     return;
   }
-  if (raw) pftk_pack_input(s, raw, d.N, packed);  // the two-pass kernels read the 16-byte records
+  if (raw) pftk_pack_input(s, raw, d.N, packed, n_dev);  // the two-pass kernels read the 16-byte records
   if (from_part) {
     hipLaunchKernelGGL(k_crop_count<true>, dim3(nb), dim3(1024), 0, s, d.in_pts, d.N, d.bbox6, d.bbox_part,
-                       d.bbox_grid, d.crop_counts);
+                       d.bbox_grid, d.crop_counts, n_dev);
     hipLaunchKernelGGL(k_crop_scatter<true>, dim3(nb), dim3(1024), 0, s, d.in_pts, d.N, d.bbox6, d.bbox_part,
-                       d.bbox_grid, d.crop_counts, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat);
+                       d.bbox_grid, d.crop_counts, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat, n_dev, n_latch);
   } else {
     hipLaunchKernelGGL(k_crop_count<false>, dim3(nb), dim3(1024), 0, s, d.in_pts, d.N, d.bbox6, d.bbox_part,
-                       d.bbox_grid, d.crop_counts);
+                       d.bbox_grid, d.crop_counts, n_dev);
     hipLaunchKernelGGL(k_crop_scatter<false>, dim3(nb), dim3(1024), 0, s, d.in_pts, d.N, d.bbox6, d.bbox_part,
-                       d.bbox_grid, d.crop_counts, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat);
+                       d.bbox_grid, d.crop_counts, p.hsv_argorder, d.crop_pts, d.crop_idx, d.hdr, d.host_stat, n_dev, n_latch);
   }
 }
 void pftk_finalize_raw(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, float* raw_out,

@@ -4,7 +4,7 @@
 // drawResult / viz_cb do with each pose (:300-326, :432-466).  The shared steps live in tracking_app.hpp.
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
-//                     [--model-leaf L] [--device-report]
+//                     [--model-leaf L] [--device-report] [--async]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
 // *.pcd = PCD v0.7 ascii / binary / binary_compressed with fields x y z rgba (what create_model.cpp:219-222 writes);
@@ -14,7 +14,10 @@
 // staying in HBM for all the trackers.  Every object is an independent handle on its own HIP stream: the loop below
 // enqueues all of them before it reads any result, so they overlap on the GPU.  --device-report moves drawResult / viz_cb to
 // the device as well (pft_report after each compute, still before any result is read): the object line then takes its
-// centroid from the report, and a `box` line follows with viz_cb's principal-axis box.
+// centroid from the report, and a `box` line follows with viz_cb's principal-axis box.  --async (with --raw): the front end
+// is enqueued without waiting for it and every tracker takes its output AND its point count on the device
+// (setInputCloudFromFilter), so the whole frame -- front end, hand-off, compute, report -- is in flight before the host waits
+// for anything; the "before / after downsampled" line then follows the results.  The poses are the same either way.
 #include <cstdlib>
 
 #include "tracking_app.hpp"
@@ -24,9 +27,10 @@ using namespace app;
 int main(int argc, char** argv) {
   std::vector<const char*> models, frames;
   Options opt;
-  bool raw = false, in_frames = false;
+  bool raw = false, in_frames = false, async = false;
   for (int i = 1; i < argc; i++) {
     if (!std::strcmp(argv[i], "--raw")) raw = true;
+    else if (!std::strcmp(argv[i], "--async")) async = true;
     else if (!std::strcmp(argv[i], "--kld")) opt.use_fixed = false;
     else if (!std::strcmp(argv[i], "--pcl-sums")) opt.pcl_sums = true;
     else if (!std::strcmp(argv[i], "--device-report")) opt.device_report = true;
@@ -55,7 +59,11 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async]\n", argv[0]);
+    return 2;
+  }
+  if (async && !raw) {
+    std::fprintf(stderr, "--async needs --raw: it is the front end that is not waited for\n");
     return 2;
   }
 
@@ -70,14 +78,18 @@ int main(int argc, char** argv) {
     Cloud::Ptr cloud = loadCloud(frames[f]);
     const pft_point_xyzrgba* d_cloud = nullptr;
     size_t n_down = 0;
-    if (raw) {
+    if (async) {
+      front_end.setInputCloud(cloud);
+      front_end.filterAsync();
+    } else if (raw) {
       front_end.setInputCloud(cloud);
       front_end.filterDevice(&d_cloud, &n_down);
       std::fprintf(stderr, "PointCloud before downsampled: %zu data points.\nPointCloud after downsampled: %zu data points.\n",
                    front_end.passedPoints(), n_down);  // auto_tracking.cpp:682, 684
     }
     for (auto& kv : v.tracker_dict) {  // :688-697 -- asynchronous: all objects are in flight before a result is read
-      if (raw) kv.second->setInputCloudDevice(d_cloud, n_down);
+      if (async) kv.second->setInputCloudFromFilter(front_end);
+      else if (raw) kv.second->setInputCloudDevice(d_cloud, n_down);
       else kv.second->setInputCloud(cloud);
       try {
         kv.second->compute();
@@ -98,6 +110,9 @@ int main(int argc, char** argv) {
       v.objectPosition(kv.first, result, centroid);
       printObjectLine(f + 1, kv.first, result, centroid);
     }
+    if (async)  // the counts, now that the frame's results are on the host
+      std::fprintf(stderr, "PointCloud before downsampled: %zu data points.\nPointCloud after downsampled: %zu data points.\n",
+                   front_end.passedPoints(), front_end.outputPoints());
   }
   return 0;
 }

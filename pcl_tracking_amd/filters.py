@@ -90,14 +90,37 @@ class InputFilter:
     def setInputCloudDevice(self, device_ptr, n, keepalive=None):
         self._cloud, self._dev = None, (int(device_ptr), int(n), keepalive)
 
-    def _apply(self):
+    def _apply(self, wait=True):
         self._ensure()
+        L = self._L
         if self._dev is not None:
-            self._check(self._L.pft_filter_apply_device(self._h, C.c_void_p(self._dev[0]), self._dev[1]))
+            f = L.pft_filter_apply_device if wait else L.pft_filter_apply_device_async
+            self._check(f(self._h, C.c_void_p(self._dev[0]), self._dev[1]))
         elif self._cloud is not None:
-            self._check(self._L.pft_filter_apply(self._h, _ptr(self._cloud), len(self._cloud)))
+            f = L.pft_filter_apply if wait else L.pft_filter_apply_async
+            self._check(f(self._h, _ptr(self._cloud), len(self._cloud)))
         else:
             raise PftError(2, "filter() without an input cloud")
+
+    def filterAsync(self):
+        """enqueue the pipeline and return without waiting for it.  counts(), passIndices(), lastMilliseconds() and
+        output() wait for it when first asked; ParticleFilterTracker.setInputCloudFromFilter hands the output on
+        without any wait.  A device input cloud is borrowed until the pipeline has run."""
+        self._apply(wait=False)
+
+    def output(self):
+        """the output cloud of the last filter() / filterAsync() on the host"""
+        _, n_out = self.counts()
+        out = np.zeros(n_out, POINT_DTYPE)
+        n = C.c_size_t()
+        self._check(self._L.pft_filter_get_output(self._h, _ptr(out), n_out, C.byref(n)))
+        return out
+
+    def outputDevice(self):
+        """(device pointer, n) of the output cloud of the last filter() / filterAsync() (waits for a pending one)"""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.pft_filter_output_device(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def counts(self):
         a, b = C.c_size_t(), C.c_size_t()

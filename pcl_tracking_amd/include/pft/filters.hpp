@@ -84,6 +84,16 @@ class InputFilter {
     apply();
     check(pft_filter_output_device(h_, device_points, n_out), "pft_filter_output_device");
   }
+  // the same pipeline, enqueued without waiting for it: the host cloud may be reused at once, a device cloud is borrowed
+  // until the pipeline has run.  passedPoints / outputPoints / lastMilliseconds wait for it when first asked;
+  // ParticleFilterTracker::setInputCloudFromFilter hands the output on without any wait
+  void filterAsync() { apply(false); }
+  pft_filter* nativeHandle() { return h_; }
+  size_t outputPoints() const {
+    size_t n_pass = 0, n_out = 0;
+    if (h_) pft_filter_counts(h_, &n_pass, &n_out);
+    return n_out;
+  }
   size_t passedPoints() const {
     size_t n_pass = 0, n_out = 0;
     if (h_) pft_filter_counts(h_, &n_pass, &n_out);
@@ -114,12 +124,13 @@ class InputFilter {
       throw std::runtime_error(std::string(what) + ": " + pft_status_string(st) + " " +
                                (h_ ? pft_filter_last_error_string(h_) : ""));
   }
-  void apply() {
+  void apply(bool wait = true) {
     if (!h_) check(pft_filter_create(&cfg_, &h_), "pft_filter_create");
     if (dev_in_)
-      check(pft_filter_apply_device(h_, dev_in_, dev_n_), "pft_filter_apply_device");
+      check((wait ? pft_filter_apply_device : pft_filter_apply_device_async)(h_, dev_in_, dev_n_), "pft_filter_apply_device");
     else if (input_)
-      check(pft_filter_apply(h_, input_->points.data(), input_->points.size()), "pft_filter_apply");
+      check((wait ? pft_filter_apply : pft_filter_apply_async)(h_, input_->points.data(), input_->points.size()),
+            "pft_filter_apply");
     else
       throw std::runtime_error("filter() without an input cloud");
   }

@@ -256,16 +256,34 @@ class ParticleFilterTracker {
   void setInputCloud(const PointCloudInConstPtr& cloud) {
     input_ = cloud;
     dev_input_ = nullptr;
+    filter_input_ = nullptr;
   }
   // a cloud already in HBM (n 32-byte points), e.g. the output of pft::InputFilter::filterDevice
   void setInputCloudDevice(const pft_point_xyzrgba* device_points, size_t n) {
     input_.reset();
     dev_input_ = device_points;
     dev_n_ = n;
+    filter_input_ = nullptr;
+  }
+  // the output of a pft::InputFilter whose filter() / filterAsync() may still be running: cloud and count are read on the
+  // device, nothing waits on the host.  max_points bounds the count (0: the size of the filter's input).  The filter object
+  // must have been applied, and must not be applied again before this tracker's compute()
+  template <class Filter>
+  void setInputCloudFromFilter(Filter& f, size_t max_points = 0) {
+    input_.reset();
+    dev_input_ = nullptr;
+    filter_input_ = f.nativeHandle();
+    filter_max_ = max_points;
   }
 
   // ---- auto_tracking.cpp:693 ----
   void compute() {
+    if (filter_input_) {
+      if (!ensure()) return;
+      if (check(pft_set_input_from_filter(handle_, filter_input_, filter_max_), "setInputCloudFromFilter") != PFT_OK) return;
+      finish(check(pft_compute(handle_), "compute"));
+      return;
+    }
     if (dev_input_ && dev_n_) {
       if (!ensure()) return;
       if (check(pft_set_input_device(handle_, dev_input_, dev_n_), "setInputCloudDevice") != PFT_OK) return;
@@ -403,6 +421,8 @@ class ParticleFilterTracker {
   PointCloudInConstPtr ref_, input_, report_cloud_;
   const pft_point_xyzrgba* dev_input_ = nullptr;
   size_t dev_n_ = 0;
+  pft_filter* filter_input_ = nullptr;  // setInputCloudFromFilter
+  size_t filter_max_ = 0;
   bool throw_on_failure_ = false;
   CoherencePtr coherence_;
   bool use_cd_ = false;

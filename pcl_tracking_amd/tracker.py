@@ -306,6 +306,22 @@ class ParticleFilterTracker:
         self._keep = keepalive
         self._check(self._L.pft_set_input_device(self._h, C.c_void_p(device_ptr), n))
 
+    def setInputCloudFromFilter(self, f, max_points=0):
+        """input cloud = the output of the InputFilter `f`, whose filter() / filterAsync() may still be running: the
+        cloud and its count are read on the device, nothing waits on the host.  max_points bounds the count (0: the
+        size of the filter's input).  `f` is kept alive by this object until the next setInputCloud*."""
+        self._ensure()
+        if f._h is None:
+            raise PftError(7, "setInputCloudFromFilter: the filter has not been applied yet")
+        self._keep = f
+        self._check(self._L.pft_set_input_from_filter(self._h, f._h, int(max_points)))
+
+    def debugInputRecords(self, first, n):
+        """the handle's 16-byte input records [first, first + n) as (n, 4) uint32 (test hook)"""
+        out = np.zeros((n, 4), np.uint32)
+        self._check(self._L.pft_debug_get_input_records(self._h, _ptr(out), first, n))
+        return out
+
     def compute(self):
         self._ensure()
         self._check(self._L.pft_compute(self._h))
