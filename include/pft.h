@@ -209,6 +209,13 @@ typedef struct pft_object_report {
 /* reference_dict[obj] (:675): host pointer, copied; may be called again at any time.  PFT_ERR_INVALID_ARG for n == 0, a
  * non-finite coordinate, or a sharded handle (world_size > 1) */
 int pft_set_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n);
+/* :673-675 from a model-preparation handle (pft_model.h) whose last prepare succeeded: pft_set_reference with its
+ * downsampled cloud and pft_set_trans with its trans; with set_report_cloud != 0 also pft_set_report_cloud with its
+ * re-centred cloud, copied device to device.  The tracker is left exactly as those calls leave it when given the same
+ * clouds from the host.  The refusals of pft_set_report_cloud hold, with its texts, and are decided before anything is
+ * applied; PFT_ERR_STATE for a model not prepared, PFT_ERR_INVALID_ARG for a model on another device */
+struct pft_model;
+int pft_set_object_from_model(pft_tracker* t, struct pft_model* m, int set_report_cloud);
 /* enqueues the report on the handle's stream (never synchronises); it reads the representative state on the device, so
  * it follows the pft_compute calls before it in stream order.  PFT_ERR_STATE before the first pft_compute or without a
  * report cloud */

@@ -94,6 +94,9 @@ int pft_segment_cluster_sizes(const pft_segment* s, uint32_t* sizes, size_t capa
 /* all clusters one after the other, in cluster order: indices into the input cloud / the input's points */
 int pft_segment_get_cluster_indices(pft_segment* s, int32_t* host_idx, size_t capacity, size_t* n_total);
 int pft_segment_get_cluster_points(pft_segment* s, pft_point_xyzrgba* host_pts, size_t capacity, size_t* n_total);
+/* the same points where they are, in HBM: cluster j starts at the sum of the sizes of the clusters before it
+ * (pft_segment_cluster_sizes).  Valid until the handle's next apply; NULL when there is no cluster */
+int pft_segment_clusters_device(const pft_segment* s, const pft_point_xyzrgba** device_pts, size_t* n_total);
 /* GPU time of the last apply, milliseconds, without the host's header reads between stages; stage_ms (may be NULL)
  * receives PFT_SEGMENT_STAGES values */
 enum { PFT_SEGMENT_STAGES = 7 }; /* compaction, sample stream, scoring, replay, refit, clustering, output */

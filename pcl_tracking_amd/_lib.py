@@ -94,6 +94,7 @@ PLANE_FOUND, PLANE_NONE, PLANE_DISABLED = 0, 1, 2
 SEGMENT_MAX_PLANES = 16
 ROUNDS_STOP_FRACTION, ROUNDS_STOP_NO_PLANE, ROUNDS_STOP_MAX_PLANES = 0, 1, 2
 SEGMENT_STAGES = ("compaction", "sample", "score", "replay", "refit", "cluster", "output")
+MODEL_STAGES = ("remove_zero_points", "centroid", "recentre", "grid_sample")
 
 # every symbol include/*.h declare: (name, restype, argtypes)
 _vp, _sz, _i32, _u32, _u64, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint64, C.c_double
@@ -198,6 +199,21 @@ SYMBOLS = [
     ("pft_segment_get_plane_round_inliers", C.c_int, [_vp, _sz, C.c_int, _vp, _sz, _P(_sz)]),
     ("pft_segment_set_refit_order", C.c_int, [_vp, C.c_int]),
     ("pft_debug_segment_round_hypotheses", C.c_int, [_vp, _sz, _vp, _vp, _sz, _P(_sz)]),
+    ("pft_segment_clusters_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
+    # include/pft_model.h
+    ("pft_model_create", C.c_int, [C.c_int, _P(_vp)]),
+    ("pft_model_destroy", None, [_vp]),
+    ("pft_model_last_error_string", C.c_char_p, [_vp]),
+    ("pft_model_prepare", C.c_int, [_vp, _vp, _sz, C.c_float]),
+    ("pft_model_prepare_device", C.c_int, [_vp, _vp, _sz, C.c_float]),
+    ("pft_model_prepare_from_segment", C.c_int, [_vp, _vp, _sz, C.c_float]),
+    ("pft_model_counts", C.c_int, [_vp, _P(_sz), _P(_sz), _P(_sz)]),
+    ("pft_model_get_trans", C.c_int, [_vp, _vp]),
+    ("pft_model_get_recentred", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_model_get_reference", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_model_output_device", C.c_int, [_vp, _P(_vp), _P(_sz), _P(_vp), _P(_sz)]),
+    ("pft_model_last_ms", C.c_int, [_vp, _P(_f64), _vp]),
+    ("pft_set_object_from_model", C.c_int, [_vp, _vp, C.c_int]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

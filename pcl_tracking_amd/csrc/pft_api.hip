@@ -2035,22 +2035,40 @@ extern "C" int pft_debug_change_detect(pft_tracker* t, const pft_point_xyzrgba* 
 }
 
 // ---- object report (pft_report.hip) ----
-extern "C" int pft_set_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n) {
-  if (!t) return PFT_ERR_INVALID_ARG;
+// the refusals of a report cloud that do not depend on where the cloud lies; first_bad: the first point with a non-finite
+// coordinate, SIZE_MAX = none
+static int report_cloud_refusal(pft_tracker* t, bool empty, size_t n, size_t first_bad) {
   if (t->cfg.world_size != 1) {
     t->err = "the object report is not supported on a sharded handle (world_size > 1)";
     return PFT_ERR_INVALID_ARG;
   }
-  if (!pts || n == 0) {
+  if (empty) {
     t->err = "pft_set_report_cloud: empty report cloud";
     return PFT_ERR_INVALID_ARG;
   }
   if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
-  for (size_t i = 0; i < n; i++)  // the reference's cloud went through removeZeroPoints
-    if (!std::isfinite(pts[i].x) || !std::isfinite(pts[i].y) || !std::isfinite(pts[i].z)) {
-      t->err = "pft_set_report_cloud: point " + std::to_string(i) + " has a non-finite coordinate";
-      return PFT_ERR_INVALID_ARG;
-    }
+  if (first_bad != SIZE_MAX) {  // the reference's cloud went through removeZeroPoints
+    t->err = "pft_set_report_cloud: point " + std::to_string(first_bad) + " has a non-finite coordinate";
+    return PFT_ERR_INVALID_ARG;
+  }
+  return PFT_OK;
+}
+
+static int store_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, hipMemcpyKind kind);
+
+extern "C" int pft_set_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  size_t first_bad = SIZE_MAX;
+  if (t->cfg.world_size == 1 && pts && n <= 0x7fffffffu)
+    for (size_t i = 0; i < n && first_bad == SIZE_MAX; i++)
+      if (!std::isfinite(pts[i].x) || !std::isfinite(pts[i].y) || !std::isfinite(pts[i].z)) first_bad = i;
+  const int r = report_cloud_refusal(t, !pts || n == 0, n, first_bad);
+  if (r != PFT_OK) return r;
+  return store_report_cloud(t, pts, n, hipMemcpyHostToDevice);
+}
+
+// pts: a host cloud, or one in this handle's HBM (kind), already accepted by report_cloud_refusal
+static int store_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, hipMemcpyKind kind) {
   hipSetDevice(t->cfg.device_id);
   HIPCHK(t, hipStreamSynchronize(t->stream));  // a report in flight may still read the previous cloud
   if (!t->d_report) HIPCHK(t, dalloc(&t->d_report, 1));
@@ -2063,10 +2081,42 @@ extern "C" int pft_set_report_cloud(pft_tracker* t, const pft_point_xyzrgba* pts
     HIPCHK(t, dalloc(&t->d_rep_tracked, n));
     t->rep_cap = (uint32_t)n;
   }
-  HIPCHK(t, hipMemcpyAsync(t->d_rep_pts, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, t->stream));
+  HIPCHK(t, hipMemcpyAsync(t->d_rep_pts, pts, n * sizeof(pft_point_xyzrgba), kind, t->stream));
   HIPCHK(t, hipStreamSynchronize(t->stream));
   t->rep_n = (uint32_t)n;
   return PFT_OK;
+}
+
+// setReferenceCloud + setTrans (+ setReportCloud) from a model-preparation handle (pft_model.hip).  Every refusal is
+// decided before anything is applied.  The downsampled reference goes through the host (pft_set_reference orders it and
+// takes its hull subset there); the full-resolution report cloud is copied device to device.
+extern "C" int pft_set_object_from_model(pft_tracker* t, pft_model* m, int set_report_cloud) {
+  if (!t || !m) return PFT_ERR_INVALID_ARG;
+  PftModelView v;
+  if (pftm_view(m, &v) != PFT_OK) {
+    t->err = "pft_set_object_from_model: the model has not been prepared";
+    return PFT_ERR_STATE;
+  }
+  if (v.device_id != t->cfg.device_id) {
+    t->err = "pft_set_object_from_model: the model lives on device " + std::to_string(v.device_id) +
+             ", the tracker on device " + std::to_string(t->cfg.device_id);
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (set_report_cloud) {
+    const int r = report_cloud_refusal(t, v.n_recentred == 0, v.n_recentred,
+                                       v.first_nonfinite == 0xFFFFFFFFu ? SIZE_MAX : (size_t)v.first_nonfinite);
+    if (r != PFT_OK) return r;
+  }
+  hipSetDevice(t->cfg.device_id);
+  std::vector<pft_point_xyzrgba> ref(v.n_reference);
+  if (v.n_reference)  // (the model's prepare has returned: its stream is idle)
+    HIPCHK(t, hipMemcpy(ref.data(), v.reference, v.n_reference * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost));
+  int r = pft_set_reference(t, ref.data(), ref.size());
+  if (r != PFT_OK) return r;
+  r = pft_set_trans(t, v.trans);
+  if (r != PFT_OK) return r;
+  if (set_report_cloud) r = store_report_cloud(t, v.recentred, v.n_recentred, hipMemcpyDeviceToDevice);
+  return r;
 }
 
 extern "C" int pft_report(pft_tracker* t) {

@@ -284,6 +284,26 @@ struct PftFilterView {
 int pftf_view(pft_filter* f, PftFilterView* v);
 void pftf_attach(pft_filter* f, PftBorrow* b);
 
+// ---- model preparation (pft_model.hip) and its hand-off to a tracker (pft_set_object_from_model) ----
+// pft_segment.hip: removeZeroPoints (RULE zero, no transform) as the ordered compaction of the segmenter.  keep_idx[0 ..
+// *n_keep) = the kept input indices, ascending, keep_xyz their {x, y, z, 1}; xyz [n], flag [n], tile [ceil(n / 1024)] scratch
+void pftk_remove_zero_points(hipStream_t s, const pft_point_xyzrgba* in, uint32_t n, float4* xyz, uint8_t* flag,
+                             uint32_t* tile, uint32_t* keep_idx, float4* keep_xyz, uint32_t* n_keep);
+struct pft_segment;
+int pftsg_device_id(const pft_segment* s);
+struct pft_model;
+struct PftModelView {
+  const pft_point_xyzrgba* recentred;  // transed_ref, in HBM
+  size_t n_recentred;
+  const pft_point_xyzrgba* reference;  // transed_ref_downsampled, in HBM
+  size_t n_reference;
+  float trans[16];
+  uint32_t first_nonfinite;            // first re-centred point with a non-finite coordinate, 0xFFFFFFFF: none
+  int device_id;
+};
+// PFT_ERR_STATE unless the last prepare succeeded
+int pftm_view(const pft_model* m, PftModelView* v);
+
 // The result-neutral path switches (A/B timing and cross-checks; README "Environment switches").  pft_create reads them
 // once, with pft_read_switches, and keeps them on the handle: the launchers take the decisions as plain arguments.
 enum class PftExactPath { sorted, per_query, shells };  // exact-NN search: cell-sorted lists, lists per query, shells only

@@ -168,6 +168,21 @@ __global__ __launch_bounds__(SG_THREADS) void k_sg_zero(SgParams p, const pft_po
   sg_tile_count(flag, p.n, tile);
 }
 
+// removeZeroPoints alone, for the model preparation (pft_model.hip): RULE zero without a transform and the compaction
+// above.  keep_idx[0 .. *n_keep) = the kept input indices, ascending; keep_xyz = their {x, y, z, 1}.  xyz [n], flag [n]
+// and tile [ceil(n / SG_TILE)] are scratch.
+void pftk_remove_zero_points(hipStream_t st, const pft_point_xyzrgba* in, uint32_t n, float4* xyz, uint8_t* flag,
+                             uint32_t* tile, uint32_t* keep_idx, float4* keep_xyz, uint32_t* n_keep) {
+  SgParams p = {};
+  p.n = n;
+  p.zero_thr = float_bound_below(0.01);
+  const uint32_t ntiles = (n + SG_TILE - 1) / SG_TILE;
+  hipLaunchKernelGGL(k_sg_zero, dim3(ntiles), dim3(SG_THREADS), 0, st, p, in, xyz, flag, tile);
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, tile, ntiles, (const uint32_t*)nullptr, n_keep);
+  hipLaunchKernelGGL(k_sg_emit, dim3(ntiles), dim3(SG_THREADS), 0, st, (const uint8_t*)flag, n, (const uint32_t*)nullptr,
+                     (const uint32_t*)tile, (const uint32_t*)nullptr, keep_idx, (const float4*)xyz, keep_xyz);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // 3. RANSAC.  RULE rng: boost::uniform_int<>(0, INT_MAX) over boost::mt19937 reduces to engine() >> 1 (bucket size 2).
 #define MT_N 624
@@ -1854,6 +1869,16 @@ extern "C" int pft_segment_get_cluster_points(pft_segment* s, pft_point_xyzrgba*
   SCHK(s, hipStreamSynchronize(s->stream));
   return PFT_OK;
 }
+
+extern "C" int pft_segment_clusters_device(const pft_segment* s, const pft_point_xyzrgba** device_pts, size_t* n_total) {
+  if (!s || !device_pts || !n_total) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) return PFT_ERR_STATE;
+  *device_pts = s->res.n_total ? s->b.out_pts : nullptr;
+  *n_total = s->res.n_total;
+  return PFT_OK;
+}
+
+int pftsg_device_id(const pft_segment* s) { return s->cfg.device_id; }
 
 extern "C" int pft_segment_last_ms(const pft_segment* s, double* ms, double* stage_ms) {
   if (!s || !ms) return PFT_ERR_INVALID_ARG;

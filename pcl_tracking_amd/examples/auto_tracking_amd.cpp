@@ -4,7 +4,8 @@
 // drawResult / viz_cb do with each pose (:300-326, :432-466).  The shared steps live in tracking_app.hpp.
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
-//                     [--model-leaf L] [--device-report] [--async]
+//                     [--model-leaf L] [--device-report] [--async] [--device-models]
+//   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
 // *.pcd = PCD v0.7 ascii / binary / binary_compressed with fields x y z rgba (what create_model.cpp:219-222 writes);
@@ -18,8 +19,13 @@
 // is enqueued without waiting for it and every tracker takes its output AND its point count on the device
 // (setInputCloudFromFilter), so the whole frame -- front end, hand-off, compute, report -- is in flight before the host waits
 // for anything; the "before / after downsampled" line then follows the results.  The poses are the same either way.
+// --device-models runs the "set object to track" step as one device pipeline per object (pft::ModelPreparation) instead of
+// on the host.  --segment <scene> takes no model files: the scene goes through the pipeline of create_model_amd, with
+// its flags and their meaning (segment_options.hpp), and every cluster becomes an object, in cluster order, prepared on
+// the device from where it lies in HBM -- the reference's service call (:749-772) without files in between.
 #include <cstdlib>
 
+#include "segment_options.hpp"
 #include "tracking_app.hpp"
 
 using namespace app;
@@ -27,9 +33,16 @@ using namespace app;
 int main(int argc, char** argv) {
   std::vector<const char*> models, frames;
   Options opt;
-  bool raw = false, in_frames = false, async = false;
+  bool raw = false, in_frames = false, async = false, device_models = false;
+  const char* segment_scene = nullptr;
+  SegmentOptions so;
   for (int i = 1; i < argc; i++) {
     if (!std::strcmp(argv[i], "--raw")) raw = true;
+    else if (!std::strcmp(argv[i], "--device-models")) device_models = true;
+    else if (!std::strcmp(argv[i], "--segment") && i + 1 < argc) segment_scene = argv[++i];
+    else if (const int got = parseSegmentFlag(so, argc, argv, i)) {
+      if (got < 0) return 2;
+    }
     else if (!std::strcmp(argv[i], "--async")) async = true;
     else if (!std::strcmp(argv[i], "--kld")) opt.use_fixed = false;
     else if (!std::strcmp(argv[i], "--pcl-sums")) opt.pcl_sums = true;
@@ -58,8 +71,9 @@ int main(int argc, char** argv) {
     frames.assign(models.begin() + 1, models.end());
     models.resize(1);
   }
-  if (models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async]\n", argv[0]);
+  if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models]\n"
+                         "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
   if (async && !raw) {
@@ -68,10 +82,36 @@ int main(int argc, char** argv) {
   }
 
   TrackingApp v(opt);
-  const int nb_objects = (int)models.size();
-  for (int obj_id = 0; obj_id < nb_objects; obj_id++) v.ref_cloud_dict[obj_id] = loadCloud(models[obj_id]);
-  v.buildTrackers(nb_objects, [](ParticleFilter& tr, int) { tr.setThrowOnFailure(false); });
-  if (!v.setObjectsToTrack()) return 1;
+  if (segment_scene) {  // model creation and model preparation in this process, the clusters never leaving HBM
+    Cloud::Ptr scene = loadCloud(segment_scene);
+    if (scene->points.empty()) {
+      std::fprintf(stderr, "no points in %s\n", segment_scene);
+      return 1;
+    }
+    pft::ModelSegmenter seg;
+    pft::VoxelGrid grid;  // its output cloud stays on the device for as long as the segmentation reads it
+    try {
+      segmentScene(so, scene, grid, seg);
+      const std::vector<uint32_t> sizes = seg.clusterSizes();
+      std::fprintf(stderr, "clusters %zu\n", sizes.size());
+      if (sizes.empty()) return 1;
+      v.buildTrackers((int)sizes.size(), [](ParticleFilter& tr, int) { tr.setThrowOnFailure(false); });
+      if (!v.setObjectsToTrackOnDevice(seg)) return 1;
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "%s\n", e.what());
+      return 1;
+    }
+  } else {
+    const int nb_objects = (int)models.size();
+    for (int obj_id = 0; obj_id < nb_objects; obj_id++) v.ref_cloud_dict[obj_id] = loadCloud(models[obj_id]);
+    v.buildTrackers(nb_objects, [](ParticleFilter& tr, int) { tr.setThrowOnFailure(false); });
+    try {
+      if (!(device_models ? v.setObjectsToTrackOnDevice() : v.setObjectsToTrack())) return 1;
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "%s\n", e.what());
+      return 1;
+    }
+  }
 
   InputFilter front_end;  // filterPassThrough (z in [0, 10]) + gridSampleApprox (0.01), fused on the device
   for (size_t f = 0; f < frames.size(); f++) {

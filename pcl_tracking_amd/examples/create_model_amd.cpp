@@ -26,50 +26,19 @@
 #include "pft/filters.hpp"
 #include "pft/pcd_io.hpp"
 #include "pft/segmentation.hpp"
+#include "segment_options.hpp"
 #include "tracking_app.hpp"
 
 int main(int argc, char** argv) {
   const char* scene = nullptr;
   std::string out_dir;
-  bool plane = true, ascii = false;
-  bool have_transform = false, have_box = false;
-  float T[16];
-  float box[6];
-  double tol = -1.0;
-  int min_size = -1, max_size = -1;
-  int max_planes = 0, sac_iter = -1;
-  double fraction = 0.3, sac_thr = -1.0;
-  float leaf = 0.0f;
-  bool tree_refit = false;
+  bool ascii = false;
+  app::SegmentOptions so;  // the flags shared with auto_tracking_amd --segment (segment_options.hpp)
   for (int i = 1; i < argc; i++) {
     if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out_dir = argv[++i];
-    else if (!std::strcmp(argv[i], "--no-plane")) plane = false;
     else if (!std::strcmp(argv[i], "--ascii")) ascii = true;
-    else if (!std::strcmp(argv[i], "--transform") && i + 16 < argc) {
-      for (int k = 0; k < 16; k++) T[k] = std::strtof(argv[++i], nullptr);
-      have_transform = true;
-    } else if (!std::strcmp(argv[i], "--box") && i + 1 < argc) {
-      if (std::sscanf(argv[++i], "%f,%f,%f,%f,%f,%f", &box[0], &box[1], &box[2], &box[3], &box[4], &box[5]) != 6) {
-        std::fprintf(stderr, "--box xmin,xmax,ymin,ymax,zmin,zmax\n");
-        return 2;
-      }
-      have_box = true;
-    } else if (!std::strcmp(argv[i], "--tolerance") && i + 1 < argc) tol = std::atof(argv[++i]);
-    else if (!std::strcmp(argv[i], "--min-size") && i + 1 < argc) min_size = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--max-size") && i + 1 < argc) max_size = std::atoi(argv[++i]);
-    else if (!std::strcmp(argv[i], "--tree-refit")) tree_refit = true;
-    else if (!std::strcmp(argv[i], "--voxel") && i + 1 < argc) leaf = std::strtof(argv[++i], nullptr);
-    else if (!std::strcmp(argv[i], "--planes") && i + 1 < argc) {
-      const int got = std::sscanf(argv[++i], "%d,%lf", &max_planes, &fraction);
-      if (got < 1 || max_planes < 1 || max_planes > PFT_SEGMENT_MAX_PLANES || !(fraction >= 0.0 && fraction <= 1.0)) {
-        std::fprintf(stderr, "--planes MAX[,FRACTION]: MAX 1 .. %d, FRACTION within [0, 1]\n", (int)PFT_SEGMENT_MAX_PLANES);
-        return 2;
-      }
-    } else if (!std::strcmp(argv[i], "--sac") && i + 1 < argc) {
-      if (std::sscanf(argv[++i], "%d,%lf", &sac_iter, &sac_thr) != 2 || sac_iter < 0 || !(sac_thr >= 0.0)) {
-        std::fprintf(stderr, "--sac ITER,THRESHOLD\n");
-        return 2;
-      }
+    else if (const int got = app::parseSegmentFlag(so, argc, argv, i)) {
+      if (got < 0) return 2;
     }
     else if (!scene) scene = argv[i];
     else {
@@ -78,10 +47,7 @@ int main(int argc, char** argv) {
     }
   }
   if (!scene || out_dir.empty()) {
-    std::fprintf(stderr, "usage: %s <scene> --out DIR [--no-plane] [--transform 16 floats] "
-                         "[--box xmin,xmax,ymin,ymax,zmin,zmax] [--tolerance T] [--min-size N] [--max-size N] [--ascii] "
-                         "[--planes MAX[,FRACTION]] [--tree-refit] [--sac ITER,THRESHOLD] [--voxel LEAF]\n",
-                 argv[0]);
+    std::fprintf(stderr, "usage: %s <scene> --out DIR " APP_SEGMENT_USAGE_1 " [--ascii] " APP_SEGMENT_USAGE_2 "\n", argv[0]);
     return 2;
   }
   app::Cloud::Ptr cloud = app::loadCloud(scene);
@@ -89,41 +55,13 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "no points in %s\n", scene);
     return 1;
   }
+  const int max_planes = so.max_planes;
   pft::ModelSegmenter seg;
-  seg.setPlane(plane);
-  pft_segment_config& c = seg.config();
-  if (!plane) c.box_enable[2] = 1;  // create_model.cpp: PassThrough z as well
-  if (have_box)
-    for (int a = 0; a < 3; a++) {
-      c.box_min[a] = box[2 * a];
-      c.box_max[a] = box[2 * a + 1];
-    }
-  if (have_transform) seg.setTransform(T);
-  if (tol > 0.0) seg.config().cluster_tolerance = tol;
-  if (min_size >= 0) seg.config().min_cluster_size = min_size;
-  if (max_size >= 0) seg.config().max_cluster_size = max_size;
-  if (sac_iter >= 0) {
-    seg.config().max_iterations = sac_iter;
-    seg.config().distance_threshold = sac_thr;
-  }
   std::vector<pft::PointIndices> cluster_indices;
   std::vector<pft::PointCloud<pft::PointXYZRGBA>> clouds;
   pft::VoxelGrid grid;  // its output cloud stays on the device for as long as the segmentation reads it
   try {
-    if (max_planes > 0) seg.setPlaneRounds(max_planes, fraction);
-    if (tree_refit) seg.setRefitOrder(PFT_SUM_TREE);
-    if (leaf > 0.0f) {  // cluster_euclid.cpp:40-44: VoxelGrid, then everything else on its output
-      grid.setLeafSize(leaf, leaf, leaf);
-      grid.setInputCloud(cloud);
-      const pft_point_xyzrgba* d_pts = nullptr;
-      size_t n_out = 0;
-      grid.filterDevice(&d_pts, &n_out);
-      std::fprintf(stderr, "PointCloud after VoxelGrid: %zu data points.\n", n_out);
-      seg.setInputCloudDevice(d_pts, n_out);
-    } else {
-      seg.setInputCloud(cloud);
-    }
-    seg.apply();
+    app::segmentScene(so, cloud, grid, seg);
     seg.clusters(cluster_indices, &clouds);
   } catch (const std::exception& e) {
     std::fprintf(stderr, "%s\n", e.what());

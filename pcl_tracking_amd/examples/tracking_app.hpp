@@ -7,6 +7,8 @@
 //   objectPosition()     drawResult + viz_cb: the full-resolution model moved by the result pose
 //                        (5 mm towards the camera "for better visualization") and its centroid,
 //                        which the node publishes as the object's position                       :300-326, :432-466
+//   setObjectsToTrackOnDevice()  the same step as one device pipeline per object (pft::ModelPreparation), from the model
+//                        clouds or straight from a segmenter's clusters in HBM                  :646-677, :749-772
 //   --device-report      the same on the device (pft_report), with viz_cb's principal-axis box       :432-466
 #pragma once
 #include <cmath>
@@ -20,6 +22,7 @@
 
 #include "pft/common.hpp"
 #include "pft/filters.hpp"
+#include "pft/model_preparation.hpp"
 #include "pft/pcd_io.hpp"
 #include "pft/particle_filter_tracker.hpp"
 
@@ -184,12 +187,32 @@ class TrackingApp {
     return true;
   }
 
+  // setObjectsToTrack() on the device: every object's model goes through one pft::ModelPreparation pipeline
+  // (removeZeroPoints, centroid, re-centring, gridSample) and reaches its tracker with setObjectFromModel, the
+  // full-resolution cloud device to device.  Same prints, same return value.  reference_dict is filled only when the
+  // host-side consumer asks for it (referenceCloud).
+  bool setObjectsToTrackOnDevice() { return prepareOnDevice(nullptr); }
+  // the same with the clusters of a segmenter's last apply as ref_cloud_dict, read where they lie in HBM: cluster j is
+  // object j (the reference's service call, :749-772)
+  bool setObjectsToTrackOnDevice(pft::ModelSegmenter& seg) { return prepareOnDevice(&seg); }
+
+  // reference_dict[obj_id], fetched from the object's model preparation the first time it is asked for
+  Cloud::Ptr referenceCloud(int obj_id) {
+    auto it = reference_dict.find(obj_id);
+    if (it != reference_dict.end() && it->second) return it->second;
+    Cloud::Ptr c(new Cloud());
+    auto mp = model_dict_.find(obj_id);
+    if (mp != model_dict_.end()) mp->second->getRecentred(*c);
+    reference_dict[obj_id] = c;
+    return c;
+  }
+
   // the tracked cloud of an object (drawResult) and its centroid (viz_cb), from a result pose
   void objectPosition(int obj_id, const ParticleT& result, float centroid[4]) {
     Affine3f transformation = tracker_dict[obj_id]->toEigenMatrix(result);
     transformation(2, 3) += -0.005f;  // "move a little bit for better visualization": the published centroid carries it
     Cloud::Ptr result_cloud(new Cloud());
-    transformPointCloud(*reference_dict[obj_id], *result_cloud, transformation);
+    transformPointCloud(*referenceCloud(obj_id), *result_cloud, transformation);
     tracked_cloud_dict[obj_id] = result_cloud;
     centroid[0] = centroid[1] = centroid[2] = 0.0f;
     centroid[3] = 1.0f;
@@ -200,6 +223,28 @@ class TrackingApp {
 
  private:
   Options opt_;
+  std::map<int, std::shared_ptr<pft::ModelPreparation>> model_dict_;  // the device-side models, one handle per object
+
+  bool prepareOnDevice(pft::ModelSegmenter* seg) {
+    for (auto& kv : tracker_dict) {
+      const int obj_id = kv.first;
+      std::shared_ptr<pft::ModelPreparation> mp(new pft::ModelPreparation());
+      if (seg) mp->setInputFromSegmenter(*seg, (size_t)obj_id);
+      else mp->setInputCloud(ref_cloud_dict[obj_id]);
+      mp->setLeafSize(opt_.downsampling_grid_size > 0 ? (float)opt_.downsampling_grid_size : 0.0f);
+      if (!mp->prepare()) {
+        std::fprintf(stderr, "object %d: empty model\n", obj_id);
+        return false;
+      }
+      std::fprintf(stderr, "object %d ref_cloud: %zu data points, nonzero_ref: %zu, downsampled: %zu\n", obj_id,
+                   mp->inputPoints(), mp->nonzeroPoints(), mp->referencePoints());
+      if (kv.second->setObjectFromModel(*mp, opt_.device_report) != PFT_OK) return false;
+      model_dict_[obj_id] = mp;
+      reference_dict.erase(obj_id);
+      kv.second->setMinIndices((int)mp->inputPoints() / 2);
+    }
+    return true;
+  }
 };
 
 // pose and published position of one object for one frame; %.9g round-trips a float, so a test can feed the pose back to the oracle

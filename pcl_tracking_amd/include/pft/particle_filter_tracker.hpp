@@ -332,6 +332,20 @@ class ParticleFilterTracker {
     if (!handle_ || !report_cloud_) return PFT_OK;
     return check(pft_set_report_cloud(handle_, report_cloud_->points.data(), report_cloud_->points.size()), "setReportCloud");
   }
+  // setReferenceCloud + setTrans (+ setReportCloud) from a pft::ModelPreparation that has been prepared (:673-675): the
+  // report cloud goes device to device.  The handle is created first, as compute() would.
+  template <class Model>
+  int setObjectFromModel(Model& mp, bool with_report_cloud = false) {
+    if (!ensure()) return PFT_ERR_NO_DEVICE;
+    const int st = check(pft_set_object_from_model(handle_, mp.nativeHandle(), with_report_cloud ? 1 : 0), "setObjectFromModel");
+    if (st != PFT_OK) return st;
+    trans_ = mp.getTrans();
+    std::shared_ptr<PointCloudIn> ref(new PointCloudIn());
+    mp.getReference(*ref);
+    ref_ = ref;
+    if (with_report_cloud) report_cloud_.reset();  // the handle holds it; the host copy is not needed again
+    return PFT_OK;
+  }
   // enqueues the report of the last compute() on the tracker's stream; nothing waits
   int computeReport() {
     if (!handle_) return check(PFT_ERR_STATE, "computeReport");

@@ -164,6 +164,19 @@ class ModelSegmenter {
       o += sizes[c];
     }
   }
+  // the clusters' sizes in cluster order, and all their points one after the other where they lie in HBM (valid until
+  // the next apply): what pft::ModelPreparation::setInputFromSegmenter reads
+  std::vector<uint32_t> clusterSizes() {
+    size_t nc = 0;
+    check(pft_segment_cluster_count(h_, &nc), "pft_segment_cluster_count");
+    std::vector<uint32_t> sizes(nc);
+    check(pft_segment_cluster_sizes(h_, sizes.data(), nc), "pft_segment_cluster_sizes");
+    return sizes;
+  }
+  void clustersDevice(const pft_point_xyzrgba** device_points, size_t* n_total) {
+    check(pft_segment_clusters_device(h_, device_points, n_total), "pft_segment_clusters_device");
+  }
+  pft_segment* nativeHandle() { return h_; }
   double lastMilliseconds() const {
     double ms = 0.0;
     if (h_) pft_segment_last_ms(h_, &ms, nullptr);

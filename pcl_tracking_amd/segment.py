@@ -193,6 +193,13 @@ class ModelSegmenter:
             o += int(s)
         return out
 
+    def clustersDevice(self):
+        """(device pointer, sizes): all cluster points one after the other in HBM, in cluster order -- cluster j starts
+        32 * sizes[:j].sum() bytes in.  Valid until the next apply(); the pointer is 0 without clusters."""
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.pft_segment_clusters_device(self._h, C.byref(p), C.byref(n)))
+        return p.value or 0, self.clusterSizes()
+
     def hypotheses(self, round=0):
         """(samples int32[n, 3], counts uint32[n]) in draw order, n = RANSAC iterations of the round"""
         n = C.c_size_t()

@@ -295,6 +295,20 @@ class ParticleFilterTracker:
         if self._h is not None:
             self._check(self._L.pft_set_reference(self._h, _ptr(self._ref), len(self._ref)))
 
+    def setObjectFromModel(self, mp, report_cloud=False):
+        """setReferenceCloud + setTrans from the ModelPreparation `mp` (auto_tracking.cpp:673-675); report_cloud=True is
+        also setReportCloud with its re-centred cloud, copied device to device.  The handle is created first, as
+        setInputCloud does; a refusal leaves the tracker as it was."""
+        if mp._h is None:
+            raise PftError(7, "setObjectFromModel: the model has not been prepared")
+        self._ensure()
+        self._check(self._L.pft_set_object_from_model(self._h, mp._h, 1 if report_cloud else 0))
+        # what a later close() and re-creation hands to the new handle
+        self._ref = mp.reference()
+        self._trans = mp.trans()
+        if report_cloud:
+            self._report_cloud = mp.recentred()
+
     def setInputCloud(self, cloud):
         self._ensure()
         cloud = np.ascontiguousarray(cloud, POINT_DTYPE)
