@@ -49,7 +49,9 @@ typedef enum pft_status {
   PFT_ERR_NO_DEVICE = 4,    /* no gfx950 GPU / HIP runtime unusable: there is no CPU fallback */
   PFT_ERR_HIP = 5,          /* a HIP call failed; see pft_last_error_string */
   PFT_ERR_CAPACITY = 6,     /* a size exceeds what the handle was created for */
-  PFT_ERR_STATE = 7         /* call not valid in the current state */
+  PFT_ERR_STATE = 7,        /* call not valid in the current state */
+  PFT_ERR_LOST = 8          /* "object not recognized": the lost rule of pft_match fired (thrown by the C++ mirror's compute()
+                               for the reference's catch (int), auto_tracking.cpp:692-696; no C entry point returns it) */
 } pft_status;
 
 /* One POD holding every parameter the reference sets (auto_tracking.cpp:187-253) plus PCL's
@@ -224,6 +226,54 @@ int pft_report(pft_tracker* t);
 int pft_get_report(pft_tracker* t, pft_object_report* out);
 /* tracked_cloud_dict[obj] (:325): the report cloud moved by the last report's transform; *n = its size, up to cap copied */
 int pft_get_tracked_cloud(pft_tracker* t, pft_point_xyzrgba* out, size_t cap, size_t* n);
+
+/* ---- match statistics of the result pose, the lost rule, resetTracking ----
+ * What a caller cannot learn from pft_get_fit_ratio (PCL's w_min of the best PARTICLE): how much of the model, moved by the
+ * frame's RESULT, finds a partner in the frame.  Opt-in, one extra launch on the handle's stream after pft_compute; it reads
+ * the representative state and the last iteration's tree on the device, so nothing synchronises.  For every reference point
+ * p_j:  q = T p_j with T = pose_to_matrix(result) on the device (double cos / sin rounded to float, no -5 mm offset) and the
+ * likelihood's float expression; (partner, d2) = approxNearestSearch of q in the tree the frame's last iteration built;
+ * matched_j = (double)d2 < max_distance^2, the likelihood's gate; the pair's value DistanceCoherence x HSVColorCoherence.
+ *   n_matched    sum of matched_j
+ *   coherence    sum of matched_j x pair value   } adjacent-pair trees in double over the handle's stored order of the
+ *   sum_sq_dist  sum of matched_j x (double)d2   } reference points, padded with +0.0: independent of the launch shape
+ *   n_crop       points of the crop searched;  evaluated  1, or 0 when there was nothing to evaluate: the last iteration was
+ *                skipped by the change detector or raised a device-side failure ("no target").  The other fields then keep
+ *                the values of the last evaluated frame, the streak included.  An empty crop is evaluated: 0 matched.
+ *   below        (double)n_matched < min_ratio * (double)n_reference
+ *   streak       below ? streak + 1 : 0;   lost  streak >= lost_after;   calls  pft_match launches so far
+ * The streak is cleared by pft_reset_tracking and pft_set_reference. */
+typedef struct pft_match_stats {
+  float    transform[12];                        /* row-major 3x4, the T used */
+  double   coherence, sum_sq_dist;
+  uint32_t n_reference, n_matched, n_crop, evaluated;
+  uint32_t below, streak, lost, calls;
+} pft_match_stats;                               /* 96 B */
+
+/* min_ratio in [0, 1] (default 0: never below), lost_after >= 1 (default 1); read by the pft_match calls that follow */
+int pft_set_match_threshold(pft_tracker* t, double min_ratio, int lost_after);
+int pft_get_match_threshold(pft_tracker* t, double* min_ratio, int* lost_after);
+/* enqueues the match of the last pft_compute (never synchronises).  PFT_ERR_INVALID_ARG with a text: a sharded handle
+ * (world_size > 1), an exact-NN handle (that mode builds no octree).  PFT_ERR_STATE: before the first pft_compute, or after
+ * anything that rebuilt the handle's tree for other particles since (pft_eval_weights, pft_set_particles,
+ * pft_debug_state_restore, pft_set_reference, an input cloud that made the buffers grow) */
+int pft_match(pft_tracker* t);
+/* synchronises and copies the last match out; device-side failures are reported as by pft_get_result */
+int pft_get_match(pft_tracker* t, pft_match_stats* out);
+/* the pairs of the last match, per reference point in the CALLER's order: input_idx = index in the frame's input cloud of
+ * the partner if matched, else -1; sq_dist = the neighbour's d2 whether matched or not (INFINITY for an empty crop).
+ * Either array may be null; *n = the reference size, up to cap copied.  After an unevaluated match: the last evaluated one's
+ * for this reference cloud (pft_set_reference forgets the pairs and the result fields of the block: until a match is
+ * evaluated for the new cloud they read -1 / INFINITY and n_reference = its size, n_matched = 0).  PFT_ERR_STATE without a
+ * pft_match since the reference cloud was last set */
+int pft_get_match_pairs(pft_tracker* t, int32_t* input_idx, float* sq_dist, size_t cap, size_t* n);
+/* ParticleFilterTracker::resetTracking(): the handle forgets its population.  The next pft_compute (pft_dist_begin_frame on
+ * a sharded handle) is a first frame in every respect -- initParticles(true) around the trans in force then, the
+ * first-frame schedule, motion zero, resample epoch 0, builder hints reset -- and the tracker then runs bit for bit like a
+ * fresh handle with the same configuration, reference and trans on the same frames.  The change detector keeps its state,
+ * as PCL keeps its detector.  One deliberate difference: PCL keeps changed_ and the stale motion_, and would resample the
+ * fresh uniform population once before the first weight() */
+int pft_reset_tracking(pft_tracker* t);
 
 /* ---- multi-GPU phase API (one handle per rank; the collectives between the phases are issued by
  *      the host layer on the same stream, see pcl_tracking_amd/dist.py and DESIGN.md) ----

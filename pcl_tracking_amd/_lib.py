@@ -13,7 +13,7 @@ PFT_CD_RING = 32  # decisions kept by the change detector (pft_debug_change_stat
 K_RESAMPLE, K_AABB, K_CROP, K_OCTREE, K_LIKELIHOOD, K_POPULATION, K_PACK, K_COUNT = range(8)
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no input cloud", 3: "no reference cloud", 4: "no usable HIP device",
-          5: "HIP error", 6: "capacity exceeded", 7: "invalid state"}
+          5: "HIP error", 6: "capacity exceeded", 7: "invalid state", 8: "object not recognized"}
 
 
 class PftError(RuntimeError):
@@ -48,6 +48,15 @@ class ObjectReport(C.Structure):
         ("eigenvalues", C.c_float * 3), ("axes", C.c_float * 9), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
         ("box_centre", C.c_float * 3), ("box_quat", C.c_float * 4), ("box_size", C.c_float * 3),
         ("n_points", C.c_uint32), ("info", C.c_uint32), ("pad", C.c_uint32 * 1),
+    ]
+
+
+class MatchStatsStruct(C.Structure):
+    """pft_match_stats (include/pft.h): match statistics of one result pose and the lost rule's state, 96 bytes"""
+    _fields_ = [
+        ("transform", C.c_float * 12), ("coherence", C.c_double), ("sum_sq_dist", C.c_double),
+        ("n_reference", C.c_uint32), ("n_matched", C.c_uint32), ("n_crop", C.c_uint32), ("evaluated", C.c_uint32),
+        ("below", C.c_uint32), ("streak", C.c_uint32), ("lost", C.c_uint32), ("calls", C.c_uint32),
     ]
 
 
@@ -157,6 +166,12 @@ SYMBOLS = [
     ("pft_report", C.c_int, [_vp]),
     ("pft_get_report", C.c_int, [_vp, _P(ObjectReport)]),
     ("pft_get_tracked_cloud", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_set_match_threshold", C.c_int, [_vp, _f64, C.c_int]),
+    ("pft_get_match_threshold", C.c_int, [_vp, _P(_f64), _P(C.c_int)]),
+    ("pft_match", C.c_int, [_vp]),
+    ("pft_get_match", C.c_int, [_vp, _P(MatchStatsStruct)]),
+    ("pft_get_match_pairs", C.c_int, [_vp, _vp, _vp, _sz, _P(_sz)]),
+    ("pft_reset_tracking", C.c_int, [_vp]),
     ("pft_kld_normal_quantile", _f64, [_f64]),
     ("pft_kld_bound", _f64, [C.c_int, _f64, _f64]),
     ("pft_profile_enable", C.c_int, [_vp, C.c_int]),

@@ -150,6 +150,17 @@ struct pft_tracker {
   uint32_t rep_tracked_n = 0;  // points of the tracked cloud the last pft_report wrote (0: none, or the buffer was replaced)
   bool rep_issued = false;     // a pft_report has been enqueued: d_report holds (or will hold) its result
 
+  // match statistics (pft_match): the result block with the lost rule's state, and the pairs in the caller's order
+  pft_match_stats* d_match = nullptr;
+  int32_t* d_match_idx = nullptr;
+  float* d_match_d2 = nullptr;
+  uint32_t match_cap = 0;        // reference points the pair arrays have room for
+  uint32_t match_n = 0;          // reference points of the last pft_match (0: none since the reference was last set)
+  bool match_issued = false;     // a pft_match has been enqueued: d_match holds (or will hold) its result
+  bool tree_of_compute = false;  // the tree, crop and result on the device are those of the last pft_compute
+  double match_min_ratio = 0.0;
+  int match_lost_after = 1;
+
   // state
   bool has_ref = false, has_input = false, initialized = false, changed = false;
   uint32_t resample_epoch = 0;
@@ -183,6 +194,7 @@ extern "C" const char* pft_status_string(int s) {
     case PFT_ERR_HIP: return "HIP error";
     case PFT_ERR_CAPACITY: return "capacity exceeded";
     case PFT_ERR_STATE: return "invalid state";
+    case PFT_ERR_LOST: return "object not recognized";
   }
   return "unknown";
 }
@@ -471,6 +483,7 @@ static int ensure_input_capacity(pft_tracker* t, uint32_t n) {
   }
   hipStreamSynchronize(t->stream);
   t->in_cap = 0;  // a failing allocation below leaves null buffers: they must not look usable
+  t->tree_of_compute = false;  // (the tree goes with them)
   dfree(t->d_in_raw); dfree(t->d_in_pts); dfree(t->d_crop_counts); dfree(t->d_crop_slots); dfree(t->d_crop_pts); dfree(t->d_crop_idx);
   dfree(t->d_words); dfree(t->d_leaf_pts); dfree(t->d_leaf_order); dfree(t->d_pt_node); dfree(t->d_pt_key);
   dfree(t->d_pt_tmp); dfree(t->d_pt_key64);
@@ -745,6 +758,7 @@ extern "C" void pft_destroy(pft_tracker* t) {
   dfree(t->sv_part); dfree(t->sv_alias_list); dfree(t->sv_alias_pref); dfree(t->sv_alias_pos); dfree(t->sv_hdr);
   cd_free(t->cd); cd_free(t->cd_dbg);
   dfree(t->d_rep_pts); dfree(t->d_rep_tracked); dfree(t->d_report);
+  dfree(t->d_match); dfree(t->d_match_idx); dfree(t->d_match_d2);
   dfree(t->sv_cd); dfree(t->sv_cd_key[0]); dfree(t->sv_cd_key[1]); dfree(t->sv_cd_cnt[0]); dfree(t->sv_cd_cnt[1]);
   if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
   delete t;
@@ -756,6 +770,13 @@ extern "C" int pft_synchronize(pft_tracker* t) {
   if (!t) return PFT_ERR_INVALID_ARG;
   HIPCHK(t, hipStreamSynchronize(t->stream));
   return check_device_error(t);
+}
+
+// the lost rule's state {below, streak, lost} back to zero, in stream order
+static int match_clear_streak(pft_tracker* t) {
+  if (!t->d_match) return PFT_OK;
+  HIPCHK(t, hipMemsetAsync(&t->d_match->below, 0, 3 * sizeof(uint32_t), t->stream));
+  return PFT_OK;
 }
 
 extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n) {
@@ -858,6 +879,12 @@ extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, s
   }
   t->has_ref = true;
   if (t->h_stat) t->h_stat[0] = t->h_stat[1] = 0;  // new scene: forget the builder hints (unknown depth = all radix passes)
+  t->tree_of_compute = false;  // the tree on the device was searched for another model
+  t->match_n = 0;
+  {
+    const int r = match_clear_streak(t);  // a new object: the lost rule starts over
+    if (r != PFT_OK) return r;
+  }
   sync_dev(t);
   return PFT_OK;
 }
@@ -1180,6 +1207,7 @@ extern "C" int pft_compute(pft_tracker* t) {
     t->err = "pft_compute on a sharded handle: drive the pft_dist_* phases instead";
     return PFT_ERR_STATE;
   }
+  t->tree_of_compute = false;
   if (!t->initialized) stage_init_particles(t);
   if (!t->cd_latched) {  // initCompute() creates the change detector at the resolution in force now
     t->cd_res_latched = t->cd_res;
@@ -1278,6 +1306,7 @@ extern "C" int pft_compute(pft_tracker* t) {
     t->err = std::string("kernel launch: ") + hipGetErrorString(e);
     return PFT_ERR_HIP;
   }
+  t->tree_of_compute = true;  // (pft_match: cleared by whatever rebuilds the tree for other particles)
   return PFT_OK;
 }
 
@@ -1387,6 +1416,7 @@ extern "C" int pft_set_particles(pft_tracker* t, const pft_particle* p, size_t n
   HIPCHK(t, hipStreamSynchronize(t->stream));
   t->initialized = true;
   t->changed = false;
+  t->tree_of_compute = false;  // the representative state was replaced: the tree is not its frame's any more
   if (t->h_stat) t->h_stat[0] = t->h_stat[1] = 0;  // the spread of the particles decides the crop: forget the builder hints
   return PFT_OK;
 }
@@ -1492,6 +1522,7 @@ extern "C" int pft_debug_state_restore(pft_tracker* t) {
     return PFT_ERR_STATE;
   }
   hipSetDevice(t->cfg.device_id);
+  t->tree_of_compute = false;  // the header goes back to the checkpoint's, the tree does not
   t->cur = t->sv_cur;
   t->resample_epoch = t->sv_epoch;
   t->changed = t->sv_changed;
@@ -1565,6 +1596,7 @@ extern "C" int pft_eval_weights(pft_tracker* t, const pft_particle* particles, s
     t->nn_cap = pairs;
   }
   sync_dev(t);
+  t->tree_of_compute = false;  // the crop and the tree are rebuilt for these particles
   PftDev d = t->dev;
   d.p_active = nullptr;  // explicit particle count (a KLD handle's device-side count does not apply here)
   d.part_cur = t->d_dbg_part;
@@ -2160,4 +2192,131 @@ extern "C" int pft_get_tracked_cloud(pft_tracker* t, pft_point_xyzrgba* out, siz
   HIPCHK(t, hipMemcpyAsync(out, t->d_rep_tracked, c * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(t, hipStreamSynchronize(t->stream));
   return check_device_error(t);
+}
+
+// ---- match statistics of the result pose, the lost rule, resetTracking (pft_match.hip) ----
+extern "C" int pft_set_match_threshold(pft_tracker* t, double min_ratio, int lost_after) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!(min_ratio >= 0.0 && min_ratio <= 1.0) || lost_after < 1) {
+    t->err = "pft_set_match_threshold: min_ratio must lie in [0, 1] and lost_after must be at least 1";
+    return PFT_ERR_INVALID_ARG;
+  }
+  t->match_min_ratio = min_ratio;
+  t->match_lost_after = lost_after;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_match_threshold(pft_tracker* t, double* min_ratio, int* lost_after) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (min_ratio) *min_ratio = t->match_min_ratio;
+  if (lost_after) *lost_after = t->match_lost_after;
+  return PFT_OK;
+}
+
+// the first match for a reference cloud: the block's result fields and the pairs start as "nothing matched" (a match that
+// is not evaluated leaves them so); the lost rule's state and the call count stay
+__global__ __launch_bounds__(256) void k_match_clear(pft_match_stats* out, int32_t* input_idx, float* sq_dist, uint32_t M) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
+    input_idx[i] = -1;
+    sq_dist[i] = INFINITY;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int k = 0; k < 12; k++) out->transform[k] = 0.0f;
+    out->coherence = 0.0;
+    out->sum_sq_dist = 0.0;
+    out->n_reference = M;
+    out->n_matched = 0u;
+    out->n_crop = 0u;
+    out->evaluated = 0u;
+  }
+}
+
+extern "C" int pft_match(pft_tracker* t) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size != 1) {
+    t->err = "the match statistics are not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (t->cfg.exact_nearest) {
+    t->err = "the match statistics are not supported with the exact nearest-neighbour coherence (exact_nearest): that mode builds no octree";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (!t->initialized || !t->has_ref) {
+    t->err = "pft_match before the first pft_compute: there is no result yet";
+    return PFT_ERR_STATE;
+  }
+  if (!t->tree_of_compute) {
+    t->err = "pft_match: the tree on the device is not the last pft_compute's any more (pft_eval_weights, a debug hook, a new "
+             "reference or a larger input cloud came after it)";
+    return PFT_ERR_STATE;
+  }
+  hipSetDevice(t->cfg.device_id);
+  if (!t->d_match) {
+    HIPCHK(t, dalloc(&t->d_match, 1));
+    HIPCHK(t, hipMemsetAsync(t->d_match, 0, sizeof(pft_match_stats), t->stream));
+  }
+  const uint32_t M = t->prm.M;
+  if (M > t->match_cap) {
+    HIPCHK(t, hipStreamSynchronize(t->stream));  // a match in flight may still write the previous arrays
+    dfree(t->d_match_idx);
+    dfree(t->d_match_d2);
+    t->match_cap = 0;
+    HIPCHK(t, dalloc(&t->d_match_idx, M));
+    HIPCHK(t, dalloc(&t->d_match_d2, M));
+    t->match_cap = M;
+  }
+  if (t->match_n != M || !t->match_issued)  // (pft_set_reference zeroes match_n: no pair of another model survives it)
+    hipLaunchKernelGGL(k_match_clear, dim3(M / 256u < 1u ? 1u : (M / 256u > 64u ? 64u : M / 256u)), dim3(256), 0, t->stream,
+                       t->d_match, t->d_match_idx, t->d_match_d2, M);
+  sync_dev(t);
+  PftDev d = t->dev;
+  d.gate = t->cd_ever ? &t->cd.b.st->gate : nullptr;  // the last iteration's decision, still in the detector's state
+  pftk_match(t->stream, t->prm, d, t->match_min_ratio, (uint32_t)t->match_lost_after, t->d_match, t->d_match_idx,
+             t->d_match_d2);
+  HIPCHK(t, hipGetLastError());
+  t->match_issued = true;
+  t->match_n = M;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_match(pft_tracker* t, pft_match_stats* out) {
+  if (!t || !out) return PFT_ERR_INVALID_ARG;
+  if (!t->match_issued) {
+    t->err = "pft_get_match before the first pft_match";
+    return PFT_ERR_STATE;
+  }
+  HIPCHK(t, hipMemcpyAsync(out, t->d_match, sizeof(pft_match_stats), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  return check_device_error(t);
+}
+
+extern "C" int pft_get_match_pairs(pft_tracker* t, int32_t* input_idx, float* sq_dist, size_t cap, size_t* n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!t->match_issued || !t->match_n) {
+    t->err = "pft_get_match_pairs: no pairs (no pft_match since the reference cloud was last set)";
+    return PFT_ERR_STATE;
+  }
+  if (n) *n = t->match_n;
+  const size_t c = cap < t->match_n ? cap : t->match_n;
+  if (input_idx && c) HIPCHK(t, hipMemcpyAsync(input_idx, t->d_match_idx, c * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
+  if (sq_dist && c) HIPCHK(t, hipMemcpyAsync(sq_dist, t->d_match_d2, c * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  return check_device_error(t);
+}
+
+// ParticleFilterTracker::resetTracking(): the handle forgets its population.  The next pft_compute (or
+// pft_dist_begin_frame) is a first frame: initParticles(true) around the trans in force then, motion zero, resample
+// epoch 0, the first-frame schedule, builder hints reset -- host state plus the init launch the first frame already has.
+// The change detector keeps its state, as PCL keeps its detector.  One deliberate difference: PCL keeps changed_ and the
+// stale motion_ and would resample the fresh uniform population once before the first weight(); here the frame after a
+// reset runs exactly like the first frame of a fresh handle.
+extern "C" int pft_reset_tracking(pft_tracker* t) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  hipSetDevice(t->cfg.device_id);
+  t->initialized = false;
+  t->changed = false;
+  t->resample_epoch = 0;
+  t->tree_of_compute = false;
+  if (t->h_stat) t->h_stat[0] = t->h_stat[1] = 0;
+  return match_clear_streak(t);
 }

@@ -327,6 +327,10 @@ PftSwitches pft_read_switches();
 // the object report (pft_report.hip): one workgroup reads hdr->rep, writes the tracked cloud and the report
 void pftk_report(hipStream_t s, const pft_point_xyzrgba* pts, uint32_t n, const PftHeader* hdr, int sum_order,
                  pft_point_xyzrgba* tracked, pft_object_report* out);
+// the match statistics of the result pose (pft_match.hip): one workgroup reads hdr->rep and the tree of the last iteration
+// (d.gate: the change detector's gate word or null), writes the statistics, the lost rule's state and the pairs
+void pftk_match(hipStream_t s, const PftParams& p, const PftDev& d, double min_ratio, uint32_t lost_after,
+                pft_match_stats* out, int32_t* input_idx, float* sq_dist);
 void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, int argorder, float4* xyz,
                          float4* hsv);
 void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out,

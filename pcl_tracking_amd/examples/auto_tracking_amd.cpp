@@ -4,7 +4,7 @@
 // drawResult / viz_cb do with each pose (:300-326, :432-466).  The shared steps live in tracking_app.hpp.
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
-//                     [--model-leaf L] [--device-report] [--async] [--device-models]
+//                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -23,6 +23,10 @@
 // on the host.  --segment <scene> takes no model files: the scene goes through the pipeline of create_model_amd, with
 // its flags and their meaning (segment_options.hpp), and every cluster becomes an object, in cluster order, prepared on
 // the device from where it lies in HBM -- the reference's service call (:749-772) without files in between.
+// --match[=min_ratio[,lost_after]] enqueues the match statistics behind every compute (pft_match, still before any result is
+// read) and prints one `match` line per object and frame; an object whose result matched fewer than min_ratio of its model
+// points for lost_after frames in a row is lost: `Object not recognized` on stderr, the reference's message (:695), and with
+// --reset-on-loss a resetTracking(), so that the next frame starts over from the object's initial position.
 #include <cstdlib>
 
 #include "segment_options.hpp"
@@ -61,6 +65,21 @@ int main(int argc, char** argv) {
         opt.cd_resolution = res;
       }
     }
+    else if (!std::strncmp(argv[i], "--match", 7) && (argv[i][7] == 0 || argv[i][7] == '=')) {
+      opt.match = true;  // --match[=min_ratio[,lost_after]]; the defaults 0,1 never report a loss
+      if (argv[i][7] == '=') {
+        double ratio = 0.0;
+        int after = 1;
+        const int got = std::sscanf(argv[i] + 8, "%lf,%d", &ratio, &after);
+        if (got < 1 || !(ratio >= 0.0 && ratio <= 1.0) || after < 1) {
+          std::fprintf(stderr, "--match=min_ratio[,lost_after] with min_ratio in [0, 1] and lost_after >= 1\n");
+          return 2;
+        }
+        opt.match_min_ratio = ratio;
+        opt.match_lost_after = after;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--reset-on-loss")) opt.reset_on_loss = true;
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -72,8 +91,12 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
+    return 2;
+  }
+  if (opt.reset_on_loss && !opt.match) {
+    std::fprintf(stderr, "--reset-on-loss needs --match: it is the match that says an object is lost\n");
     return 2;
   }
   if (async && !raw) {
@@ -137,9 +160,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Object not recognized (%s)\n", pft_status_string(e));
       }
       if (opt.device_report) kv.second->computeReport();
+      if (opt.match) kv.second->computeMatch();
     }
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
+      if (opt.match) v.reportMatch(f + 1, kv.first);
       if (opt.device_report) {
         const pft_object_report rep = kv.second->getReport();
         printObjectLine(f + 1, kv.first, result, rep.centroid);

@@ -10,6 +10,8 @@
 //   setObjectsToTrackOnDevice()  the same step as one device pipeline per object (pft::ModelPreparation), from the model
 //                        clouds or straight from a segmenter's clusters in HBM                  :646-677, :749-772
 //   --device-report      the same on the device (pft_report), with viz_cb's principal-axis box       :432-466
+//   --match              the match statistics of every result (pft_match) and the lost rule that makes the
+//                        reference's "Object not recognized" handler fire; --reset-on-loss: resetTracking() then  :692-696
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -47,6 +49,10 @@ struct Options {
   unsigned int cd_interval = 10, cd_min_points = 10;
   double cd_resolution = 0.01;
   bool device_report = false;           // drawResult + viz_cb on the device: setReportCloud / computeReport / getReport
+  bool match = false;                   // match statistics of every result: setMatchThreshold / computeMatch / getMatch
+  double match_min_ratio = 0.0;         // lost after match_lost_after frames in a row below this matched share
+  int match_lost_after = 1;
+  bool reset_on_loss = false;           // resetTracking() on a lost object
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -142,6 +148,7 @@ class TrackingApp {
       coherence->setSearchMethod(std::make_shared<search::Octree<RefPointType>>(0.01));
       coherence->setMaximumDistance(0.1);
       tr->setCloudCoherence(coherence);
+      if (opt_.match) tr->setMatchThreshold(opt_.match_min_ratio, opt_.match_lost_after);
       configure(*tr, obj_id);
       tracker_dict[obj_id] = tr;
     }
@@ -217,6 +224,22 @@ class TrackingApp {
     centroid[0] = centroid[1] = centroid[2] = 0.0f;
     centroid[3] = 1.0f;
     compute3DCentroid(*result_cloud, centroid);
+  }
+
+  // the match hook of one object and frame, after its computeMatch(): prints the `match` line; a lost object gets the
+  // reference's message (:695) and, with --reset-on-loss, a resetTracking().  Returns true when the object is lost
+  bool reportMatch(size_t frame, int obj_id) {
+    ParticleFilter& tr = *tracker_dict[obj_id];
+    const pft_match_stats m = tr.getMatch();
+    const double ratio = m.n_reference ? (double)m.n_matched / (double)m.n_reference : 0.0;
+    std::printf("frame %zu object %d match %u / %u ratio %.6f coherence %.9g rms %.9g crop %u evaluated %u below %u streak %u lost %u\n",
+                frame, obj_id, m.n_matched, m.n_reference, ratio, m.coherence,
+                m.n_matched ? std::sqrt(m.sum_sq_dist / (double)m.n_matched) : 0.0, m.n_crop, m.evaluated, m.below, m.streak,
+                m.lost);
+    if (!m.lost) return false;
+    std::fprintf(stderr, "frame %zu object %d: Object not recognized\n", frame, obj_id);
+    if (opt_.reset_on_loss) tr.resetTracking();
+    return true;
   }
 
   const Options& options() const { return opt_; }

@@ -224,7 +224,12 @@ class ParticleFilterTracker {
   void setShard(int rank, int world_size) { guard(); cfg_.rank = rank; cfg_.world_size = world_size; }
   // compute() is asynchronous and PCL's returns void.  The reference wraps it in try / catch (int)
   // (auto_tracking.cpp:692-696): with this switch on, compute() waits for the frame and throws the pft_status (an int)
-  // if the device reported a failure for it (octree capacity / depth, crop time-out: pft.h)
+  // if the device reported a failure for it (octree capacity / depth, crop time-out: pft.h).  With a match threshold
+  // whose min_ratio is above 0 (setMatchThreshold) it also enqueues the match behind the frame, and throws
+  // (int)PFT_ERR_LOST when the lost rule fired: the reference's handler then prints its "Object not recognized".
+  // That match is the frame's: getMatch() / getMatchPairs() return it, and a computeMatch() of the caller's own on the same
+  // frame would be a second one and advance the streak twice.  Handles that cannot match (exact-NN coherence, a shard)
+  // get no implicit match: compute() reports their device failures only
   void setThrowOnFailure(bool b) { throw_on_failure_ = b; }
   // the handle exists from the first compute() on; create() makes it now (for callers of the C ABI's phase API)
   bool create() { return ensure(); }
@@ -370,6 +375,50 @@ class ParticleFilterTracker {
     cloud.height = 1;
   }
 
+  // ---- match statistics of the result pose, the lost rule, resetTracking (pft.h) ----
+  // lost after `lost_after` evaluated frames in a row with fewer than min_ratio * (reference points) matched points
+  int setMatchThreshold(double min_ratio, int lost_after = 1) {
+    if (!(min_ratio >= 0.0 && min_ratio <= 1.0) || lost_after < 1) return check(PFT_ERR_INVALID_ARG, "setMatchThreshold");
+    if (handle_) {
+      const int st = check(pft_set_match_threshold(handle_, min_ratio, lost_after), "setMatchThreshold");
+      if (st != PFT_OK) return st;
+    }
+    match_min_ratio_ = min_ratio;
+    match_lost_after_ = lost_after;
+    return PFT_OK;
+  }
+  // enqueues the match of the last compute() on the tracker's stream; nothing waits.  Every call is one step of the lost
+  // rule: not to be called for a frame whose compute() already matched (setThrowOnFailure(true) with min_ratio > 0)
+  int computeMatch() {
+    if (!handle_) return check(PFT_ERR_STATE, "computeMatch");
+    return check(pft_match(handle_), "computeMatch");
+  }
+  // waits for the last computeMatch()
+  pft_match_stats getMatch() const {
+    pft_match_stats m;
+    std::memset(&m, 0, sizeof(m));
+    if (handle_) check(pft_get_match(handle_, &m), "getMatch");
+    return m;
+  }
+  // per reference point, in the order of setReferenceCloud: the partner's index in the input cloud (-1: not matched) and
+  // the neighbour's squared distance
+  void getMatchPairs(std::vector<int32_t>& input_idx, std::vector<float>& sq_dist) const {
+    input_idx.clear();
+    sq_dist.clear();
+    size_t n = 0;
+    if (handle_ && check(pft_get_match_pairs(handle_, nullptr, nullptr, 0, &n), "getMatchPairs") == PFT_OK && n) {
+      input_idx.resize(n);
+      sq_dist.resize(n);
+      check(pft_get_match_pairs(handle_, input_idx.data(), sq_dist.data(), n, &n), "getMatchPairs");
+    }
+  }
+  bool isLost() const { return handle_ && getMatch().lost != 0; }
+  // pcl::tracking::ParticleFilterTracker::resetTracking(): the next compute() is a first frame around the trans in force
+  // then; the change detector keeps its state, the lost rule's streak is cleared
+  void resetTracking() {
+    if (handle_) check(pft_reset_tracking(handle_), "resetTracking");
+  }
+
   int getIterationNum() const { return cfg_.iteration_num; }
   int getParticleNum() const { return cfg_.particle_num; }
   pft_tracker* nativeHandle() { return handle_; }
@@ -410,8 +459,17 @@ class ParticleFilterTracker {
   }
   void finish(int st) {
     if (!throw_on_failure_) return;
+    const bool match = st == PFT_OK && match_min_ratio_ > 0.0 && !cfg_.exact_nearest && cfg_.world_size == 1;
+    if (match) st = check(pft_match(handle_), "compute");
     if (st == PFT_OK) st = check(pft_synchronize(handle_), "compute");
     if (st != PFT_OK) throw st;
+    if (match) {
+      pft_match_stats m;
+      std::memset(&m, 0, sizeof(m));
+      st = check(pft_get_match(handle_, &m), "compute");
+      if (st != PFT_OK) throw st;
+      if (m.lost) throw (int)PFT_ERR_LOST;
+    }
   }
   bool ensure() {
     if (handle_) return true;
@@ -423,6 +481,8 @@ class ParticleFilterTracker {
     }
     pft_set_trans(handle_, trans_.m);
     if (use_cd_ || cd_interval_ != 10 || cd_min_points_ != 10 || cd_resolution_ != 0.01) forwardChangeDetector();
+    if (match_min_ratio_ != 0.0 || match_lost_after_ != 1)
+      check(pft_set_match_threshold(handle_, match_min_ratio_, match_lost_after_), "setMatchThreshold");
     if (ref_) check(pft_set_reference(handle_, ref_->points.data(), ref_->points.size()), "setReferenceCloud");
     if (report_cloud_)
       check(pft_set_report_cloud(handle_, report_cloud_->points.data(), report_cloud_->points.size()), "setReportCloud");
@@ -442,6 +502,8 @@ class ParticleFilterTracker {
   bool use_cd_ = false;
   unsigned int cd_interval_ = 10, cd_min_points_ = 10;
   double cd_resolution_ = 0.01;
+  double match_min_ratio_ = 0.0;  // setMatchThreshold
+  int match_lost_after_ = 1;
 };
 
 // the class the reference actually news (auto_tracking.cpp:203-204); the thread count is the OpenMP team

@@ -59,6 +59,39 @@ class ObjectReport:
         return cls(n_points=int(r.n_points), info=int(r.info), **kw)
 
 
+@dataclass
+class MatchStats:
+    """pft_match_stats: how well the frame's result pose fits the frame, and the lost rule's state"""
+    transform: np.ndarray  # 3x4 float32, the T used: pose_to_matrix(result) on the device
+    coherence: float       # sum over the matched pairs of DistanceCoherence x HSVColorCoherence
+    sum_sq_dist: float     # sum over the matched pairs of the squared distance
+    n_reference: int
+    n_matched: int
+    n_crop: int
+    evaluated: bool        # False: the last iteration was skipped or failed; the other fields are the last evaluated frame's
+    below: bool            # n_matched < min_ratio * n_reference
+    streak: int            # evaluated frames in a row that were below
+    lost: bool             # streak >= lost_after
+    calls: int
+
+    @property
+    def ratio(self):
+        """matched share of the reference cloud (0 for an empty reference)"""
+        return self.n_matched / self.n_reference if self.n_reference else 0.0
+
+    @property
+    def rms_distance(self):
+        """root mean square distance of the matched pairs (nan without one)"""
+        return float(np.sqrt(self.sum_sq_dist / self.n_matched)) if self.n_matched else float("nan")
+
+    @classmethod
+    def from_struct(cls, r):
+        return cls(transform=np.array(r.transform, dtype=np.float32).reshape(3, 4), coherence=float(r.coherence),
+                   sum_sq_dist=float(r.sum_sq_dist), n_reference=int(r.n_reference), n_matched=int(r.n_matched),
+                   n_crop=int(r.n_crop), evaluated=bool(r.evaluated), below=bool(r.below), streak=int(r.streak),
+                   lost=bool(r.lost), calls=int(r.calls))
+
+
 class DistanceCoherence:
     """pcl::tracking::DistanceCoherence (auto_tracking.cpp:240-242)"""
 
@@ -139,6 +172,7 @@ class ParticleFilterTracker:
         self._h = None
         # ParticleFilterTracker's change detector: use, interval, min points, resolution (PCL's constructor defaults)
         self._cd = [False, 10, 10, 0.01]
+        self._match_thr = (0.0, 1)  # pft_set_match_threshold: min_ratio, lost_after
         self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
         self._ref = None
@@ -273,6 +307,8 @@ class ParticleFilterTracker:
             self._check(self._L.pft_set_trans(self._h, _ptr(self._trans)))
             if self._cd != [False, 10, 10, 0.01]:
                 self._forward_change_detector()
+            if self._match_thr != (0.0, 1):
+                self._check(self._L.pft_set_match_threshold(self._h, *self._match_thr))
             if self._ref is not None:
                 self._check(self._L.pft_set_reference(self._h, _ptr(self._ref), len(self._ref)))
             if self._report_cloud is not None:
@@ -398,6 +434,57 @@ class ParticleFilterTracker:
         out = np.zeros(n.value, POINT_DTYPE)
         self._check(self._L.pft_get_tracked_cloud(self._h, _ptr(out), n.value, C.byref(n)))
         return out
+
+    # ---- match statistics of the result pose, the lost rule, resetTracking ----
+    def setMatchThreshold(self, min_ratio, lost_after=1):
+        """the object counts as lost after `lost_after` evaluated frames in a row whose result matched fewer than
+        min_ratio * (reference points) points of the frame; (0, 1), the default, never fires.  Callable at any time"""
+        thr = (float(min_ratio), int(lost_after))
+        if not (0.0 <= thr[0] <= 1.0) or thr[1] < 1:
+            raise PftError(1, "setMatchThreshold: min_ratio in [0, 1], lost_after >= 1")
+        if self._h is not None:
+            self._check(self._L.pft_set_match_threshold(self._h, thr[0], thr[1]))
+        self._match_thr = thr
+
+    def getMatchThreshold(self):
+        return self._match_thr
+
+    def computeMatch(self):
+        """enqueues the match statistics of the last compute() on the tracker's stream; nothing waits"""
+        if self._h is None:
+            raise PftError(7, "computeMatch before the first compute()")
+        self._check(self._L.pft_match(self._h))
+
+    def getMatch(self):
+        """waits for the last computeMatch(); returns MatchStats"""
+        if self._h is None:
+            raise PftError(7, "getMatch before the first compute()")
+        r = _lib.MatchStatsStruct()
+        self._check(self._L.pft_get_match(self._h, C.byref(r)))
+        return MatchStats.from_struct(r)
+
+    def getMatchPairs(self):
+        """the pairs of the last computeMatch(), per reference point in the order of setReferenceCloud: (input_idx int32 --
+        the partner's index in the frame's input cloud, -1 if not matched --, sq_dist float32 -- the neighbour's squared
+        distance whether matched or not, inf for an empty crop)"""
+        if self._h is None:
+            raise PftError(7, "getMatchPairs before the first compute()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_match_pairs(self._h, None, None, 0, C.byref(n)))
+        idx = np.zeros(n.value, np.int32)
+        d2 = np.zeros(n.value, np.float32)
+        self._check(self._L.pft_get_match_pairs(self._h, _ptr(idx), _ptr(d2), n.value, C.byref(n)))
+        return idx, d2
+
+    def isLost(self):
+        """the lost flag of the last computeMatch() (waits for it)"""
+        return self.getMatch().lost
+
+    def resetTracking(self):
+        """pcl::tracking::ParticleFilterTracker::resetTracking(): the next compute() is a first frame around the trans
+        in force then; the change detector keeps its state, the lost rule's streak is cleared"""
+        if self._h is not None:
+            self._check(self._L.pft_reset_tracking(self._h))
 
     # ---- test hooks (stage-level parity against the oracle) ----
     def setParticles(self, p):
