@@ -364,9 +364,18 @@ int pft_debug_init_particles(pft_tracker* t, const pft_particle* rep, uint32_t i
 int pft_debug_resample(pft_tracker* t, const pft_particle* old, size_t n_total, const int32_t* a, const double* q,
                        const pft_particle* rep, uint32_t epoch, uint32_t id_offset, size_t n_local,
                        pft_particle* out);
+/* the product resample instances on explicit inputs: the prefix-sum form of the alias table is built on the device from
+ * old's weights exactly as given (in the handle's summation order), then the instance is launched as pft_compute does:
+ * 0 = one lane per particle, 1 = four lanes per particle, 2 = four lanes fused with the bounding box (PFT_ERR_STATE
+ * without a reference cloud, or when its support subset is too large for the fused form).  mats12 (nullable) receives
+ * the n_local 3x4 matrices the launch writes next to the particles.  The running filter is not touched. */
+int pft_debug_resample_prefix(pft_tracker* t, const pft_particle* old, size_t n_total, const pft_particle* rep,
+                              uint32_t epoch, uint32_t id_offset, size_t n_local, int instance, pft_particle* out,
+                              float* mats12);
 int pft_debug_pose_to_matrix(pft_tracker* t, const pft_particle* p, size_t n, float* m12);
 /* KLD resample alone: n_old particles + their explicit alias table (a, q) + motion -> the new particle set
- * (capacity maximum_particle_num), their 6-D bins, the new count and the number of distinct bins */
+ * (capacity maximum_particle_num), their 6-D bins, the new count and the number of distinct bins.  a == NULL and
+ * q == NULL: no table -- the prefix-sum form is built from old's weights as given and the product instance is launched */
 int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a, const double* q,
                            const pft_particle* motion, uint32_t epoch, pft_particle* out, int32_t* bins6,
                            uint32_t* n_out, uint32_t* k_out);

@@ -1898,6 +1898,60 @@ extern "C" int pft_debug_resample(pft_tracker* t, const pft_particle* old, size_
   return PFT_OK;
 }
 
+// The product resample instances (prefix-form alias table, two-level search) on explicit inputs: the prefix form is
+// built from old's weights as given (dbg_population, the handle's summation order), then the requested instance is
+// launched through the product launchers.  instance: 0 k_resample<false>, 1 k_resample4<false, false>,
+// 2 k_resample4<true, false> (needs a reference cloud whose support subset fits the fused form)
+extern "C" int pft_debug_resample_prefix(pft_tracker* t, const pft_particle* old, size_t n_total, const pft_particle* rep,
+                                         uint32_t epoch, uint32_t id_offset, size_t n_local, int instance,
+                                         pft_particle* out, float* mats12) {
+  if (!t || !old || !rep || !out || !n_total || !n_local || instance < 0 || instance > 2) return PFT_ERR_INVALID_ARG;
+  if (n_local > n_total || (size_t)id_offset > n_total - n_local) return PFT_ERR_INVALID_ARG;
+  if (instance == 2 && (!t->dev.ref_box || t->prm.M_box == 0u)) return PFT_ERR_STATE;
+  std::vector<pft_particle> h(old, old + n_total);
+  DbgPop b;
+  int r = dbg_population(t, h, 0, 0, 1, b, nullptr);
+  if (r != PFT_OK) return r;
+  PftParams p = t->prm;
+  p.id_offset = id_offset;
+  p.P_local = (uint32_t)n_local;
+  p.P_total = (uint32_t)n_total;
+  const uint32_t nparts = (4u * p.P_local + 255u) / 256u;
+  pft_particle* d_out = nullptr;
+  float *d_mats = nullptr, *d_box = nullptr;
+  hipError_t e = dalloc(&d_out, n_local);
+  if (e == hipSuccess) e = dalloc(&d_mats, n_local * 12);
+  if (e == hipSuccess) e = dalloc(&d_box, (size_t)nparts * 6);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&t->d_dbg_hdr->rep, rep, sizeof(pft_particle), hipMemcpyHostToDevice, t->stream);
+  bool launched = true;
+  if (e == hipSuccess) {
+    PftDev d = t->dev;
+    d.p_active = nullptr;
+    d.gate = nullptr;  // (the ungated instances)
+    d.part_all = b.part;
+    d.alias_list = b.list;
+    d.alias_pref = b.pref;
+    d.alias_pos = b.pos;
+    d.hdr = t->d_dbg_hdr;
+    d.mats = d_mats;
+    d.bbox_part = d_box;
+    d.bbox_part_cap = nparts;
+    if (instance == 2)
+      launched = pftk_resample_box(t->stream, p, d, epoch, d_out) != 0u;
+    else
+      pftk_resample(t->stream, p, d, epoch, d_out, instance == 0);
+    if (launched) e = hipMemcpyAsync(out, d_out, n_local * sizeof(pft_particle), hipMemcpyDeviceToHost, t->stream);
+    if (launched && e == hipSuccess && mats12)
+      e = hipMemcpyAsync(mats12, d_mats, n_local * 12 * sizeof(float), hipMemcpyDeviceToHost, t->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  hipFree(d_out); hipFree(d_mats); hipFree(d_box);
+  HIPCHK(t, e);
+  return launched ? PFT_OK : PFT_ERR_STATE;
+}
+
 extern "C" int pft_debug_pose_to_matrix(pft_tracker* t, const pft_particle* p, size_t n, float* m12) {
   if (!t || !p || !n || !m12) return PFT_ERR_INVALID_ARG;
   pft_particle* d = nullptr;
@@ -1918,9 +1972,18 @@ extern "C" int pft_debug_pose_to_matrix(pft_tracker* t, const pft_particle* p, s
 extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a,
                                       const double* q, const pft_particle* motion, uint32_t epoch, pft_particle* out,
                                       int32_t* bins6, uint32_t* n_out, uint32_t* k_out) {
-  if (!t || !old || !n_old || !a || !q || !motion || !out || !n_out) return PFT_ERR_INVALID_ARG;
+  if (!t || !old || !n_old || (!a) != (!q) || !motion || !out || !n_out) return PFT_ERR_INVALID_ARG;
   if (!t->prm.kld) return PFT_ERR_STATE;
   const uint32_t maxn = t->prm.kld_max;
+  const bool table = a != nullptr;
+  // without a table: the prefix form of old's weights as given (dbg_population, the handle's summation order) and the
+  // product instance k_resample_kld<false, false>
+  DbgPop b;
+  if (!table) {
+    std::vector<pft_particle> ho(old, old + n_old);
+    int r = dbg_population(t, ho, 0, 0, 1, b, nullptr);
+    if (r != PFT_OK) return r;
+  }
   pft_particle *d_old = nullptr, *d_out = nullptr;
   int32_t *d_a = nullptr, *d_bins = nullptr;
   double* d_q = nullptr;
@@ -1928,20 +1991,33 @@ extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, s
   memset(h, 0, sizeof(*h));
   h->p_active = (uint32_t)n_old;
   h->motion = *motion;
-  hipError_t e = dalloc(&d_old, n_old);
-  if (e == hipSuccess) e = dalloc(&d_out, maxn);
-  if (e == hipSuccess) e = dalloc(&d_a, n_old);
-  if (e == hipSuccess) e = dalloc(&d_q, n_old);
+  hipError_t e = dalloc(&d_out, maxn);
   if (e == hipSuccess) e = dalloc(&d_bins, (size_t)6 * maxn);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_old, old, n_old * sizeof(pft_particle), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_a, a, n_old * sizeof(int32_t), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_q, q, n_old * sizeof(double), hipMemcpyHostToDevice, t->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(t->d_dbg_hdr, h, sizeof(PftHeader), hipMemcpyHostToDevice, t->stream);
+  if (table) {
+    if (e == hipSuccess) e = dalloc(&d_old, n_old);
+    if (e == hipSuccess) e = dalloc(&d_a, n_old);
+    if (e == hipSuccess) e = dalloc(&d_q, n_old);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_old, old, n_old * sizeof(pft_particle), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_a, a, n_old * sizeof(int32_t), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_q, q, n_old * sizeof(double), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t->d_dbg_hdr, h, sizeof(PftHeader), hipMemcpyHostToDevice, t->stream);
+  } else {  // (the debug header holds alias_m / alias_nh of the prefix form: only the count and the motion are added)
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(&t->d_dbg_hdr->p_active, &h->p_active, sizeof(uint32_t), hipMemcpyHostToDevice, t->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(&t->d_dbg_hdr->motion, &h->motion, sizeof(pft_particle), hipMemcpyHostToDevice, t->stream);
+  }
   if (e == hipSuccess) {
     PftDev d = t->dev;
-    d.part_all = d_old;
+    d.part_all = table ? d_old : b.part;
     d.hdr = t->d_dbg_hdr;
     d.mats = nullptr;
+    if (!table) {
+      d.gate = nullptr;  // (the ungated instance)
+      d.alias_list = b.list;
+      d.alias_pref = b.pref;
+      d.alias_pos = b.pos;
+    }
     pftk_resample_kld(t->stream, t->prm, d, epoch, d_out, d_a, d_q, d_bins);
     e = hipMemcpyAsync(h, t->d_dbg_hdr, sizeof(PftHeader), hipMemcpyDeviceToHost, t->stream);
   }

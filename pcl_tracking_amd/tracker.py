@@ -612,6 +612,20 @@ class ParticleFilterTracker:
                                                id_offset, n_local, _ptr(out)))
         return out
 
+    def debugResamplePrefix(self, old, rep, epoch, id_offset=0, n_local=None, instance=1, want_mats=False):
+        """test hook: the product resample instances (no explicit table: the prefix-sum form is built from old's weights
+        as given).  instance 0 = one lane per particle, 1 = four lanes, 2 = four lanes fused with the bounding box (needs
+        a reference cloud).  -> particles, or (particles, matrices (n_local, 3, 4)) with want_mats"""
+        self._ensure()
+        old = np.ascontiguousarray(old, PARTICLE_DTYPE)
+        rep = np.ascontiguousarray(rep, PARTICLE_DTYPE).reshape(1)
+        n_local = len(old) if n_local is None else n_local
+        out = np.zeros(n_local, PARTICLE_DTYPE)
+        m = np.zeros((n_local, 12), np.float32) if want_mats else None
+        self._check(self._L.pft_debug_resample_prefix(self._h, _ptr(old), len(old), _ptr(rep), epoch, id_offset, n_local,
+                                                      int(instance), _ptr(out), _ptr(m) if want_mats else None))
+        return (out, m.reshape(n_local, 3, 4)) if want_mats else out
+
     def debugPoseToMatrix(self, p):
         self._ensure()
         p = np.ascontiguousarray(p, PARTICLE_DTYPE)
@@ -666,11 +680,15 @@ class KLDAdaptiveParticleFilterOMPTracker(ParticleFilterTracker):
             self._cfg.kld_bin_size[i] = float(bin_size[i])
 
     def debugKldResample(self, old, a, q, motion, epoch):
-        """test hook: the KLD resample alone, with an explicit alias table -> (particles, bins (n,6), k)"""
+        """test hook: the KLD resample alone, with an explicit alias table -> (particles, bins (n,6), k); a = q = None:
+        the product instance, on the prefix-sum form built from old's weights as given"""
         self._ensure()
         old = np.ascontiguousarray(old, PARTICLE_DTYPE)
-        a = np.ascontiguousarray(a, np.int32)
-        q = np.ascontiguousarray(q, np.float64)
+        if (a is None) != (q is None):
+            raise PftError(1, "debugKldResample: a and q are given together or not at all")
+        if a is not None:
+            a = np.ascontiguousarray(a, np.int32)
+            q = np.ascontiguousarray(q, np.float64)
         motion = np.ascontiguousarray(motion, PARTICLE_DTYPE).reshape(1)
         cap = self._cfg.maximum_particle_num
         out = np.zeros(cap, PARTICLE_DTYPE)

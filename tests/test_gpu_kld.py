@@ -42,6 +42,8 @@ def test_host_bound_matches_oracle(gpu, orc):
 @pytest.mark.parametrize("n_old,spread,maxn", [(400, 0.02, 500), (154, 0.2, 500), (37, 0.001, 500), (500, 0.05, 500),
                                                 (400, 0.3, 4000), (3000, 0.5, 16000)])
 def test_kld_resample_bit_exact(gpu, orc, n_old, spread, maxn):
+    """the explicit-table hook instance k_resample_kld<true, false>; the product instance (prefix-form table, two-level
+    search) is covered by tests/test_gpu_resample_prefix.py"""
     old = population(n_old, n_old + maxn, spread)
     a, q = orc.gen_alias_table(old["weight"])
     motion = np.zeros(1, scene.PARTICLE_DTYPE)

@@ -86,6 +86,8 @@ def test_init_particles(gpu, orc):
 
 
 def test_resample(gpu, orc, data):
+    """the explicit-table hook instance k_resample<true>; the product instances (prefix-form table, two-level search) are
+    covered by tests/test_gpu_resample_prefix.py"""
     P = 2048
     g = gpu.make_reference_tracker(particle_num=P, seed=5)
     cfg = orc.default_config(particle_num=P, seed=5)
