@@ -303,6 +303,24 @@ int pft_debug_get_octree(pft_tracker* t, int32_t* depth, double min_xyz[3], doub
                          uint32_t* n_nodes);
 int pft_debug_get_point_keys(pft_tracker* t, uint32_t* keys3, size_t cap_points);
 int pft_debug_get_scan_stats(pft_tracker* t, uint64_t* queries, uint64_t* scanned_points);
+/* the linearised octree of the last build, whichever launch built it (pft_eval_weights, or the last evaluated iteration of
+ * pft_compute): waits for the handle's stream and copies; launches nothing.  info receives PFT_TREE_INFO_WORDS words:
+ * [0] n_crop, [1] error, [2] depth, [3] use_table, [4] n_words, [5] n_leaves, [6] leaf_start, [7] n_grow, [8] build_path,
+ * [9] leaf_indirect, [10] jump_level, [11] margin_cells (float bits), [12] inv_res (float bits), [13..15] ominf (float
+ * bits), [16] build_epoch, [17] build_variant (k_octree_build: bits 0-2 the per-point store -- 1 RegStore<4>, 2 RegStore<8>,
+ * 3 RegStore<14>, 4 HybridStore<8>, 5 GlobStore --, bit 3 the node words ended in LDS, bit 4 the leaf scratch was in LDS,
+ * bit 5 an LDS attempt was abandoned and the tree rebuilt in HBM, bit 6 dense top levels, bit 7 the rescue launch built the
+ * tree, bits 8-9 who writes the leaf records: 0 k_leaf_gather, 1 the builder, 2 nobody; the sorted builder: 6 | radix
+ * passes << 10), [18] the dynamic LDS bytes k_octree_build is launched with on this device, [19] entries of the jump
+ * allocation, [20 .. 20 + depth + 1] lvl_start (the rest zero).
+ * Every array is optional (null or capacity 0) and receives min(capacity, count) elements: words [n_words] (0 after a
+ * build error), leaf_order [n_crop], leaf_pts and crop_pts [n_crop] 16-byte records, jump [info[19]]: the whole allocation,
+ * so entries beyond 8^jump_level can be looked at as well.  PFT_ERR_INVALID_ARG on sharded and exact_nearest handles (no
+ * octree), PFT_ERR_STATE before the first input cloud */
+#define PFT_TREE_INFO_WORDS 64
+int pft_debug_get_tree(pft_tracker* t, uint32_t* info, uint32_t* words, size_t words_cap, uint32_t* leaf_order,
+                       size_t leaf_order_cap, void* leaf_pts, size_t leaf_pts_cap, void* crop_pts, size_t crop_pts_cap,
+                       uint16_t* jump, size_t jump_cap);
 /* limits for the error-path tests: max_words != 0 lowers the octree node capacity (never above the allocation),
  * sorted_npass != 0 fixes the radix passes of the sorted builder (0 = derived from the previous depth) */
 int pft_debug_set_limits(pft_tracker* t, uint32_t max_words, int sorted_npass);

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("PFT_LIB_PATH") or os.path.join(_HERE, "_build", "libp
 PFT_ABI_VERSION = 5
 PFT_SUM_TREE, PFT_SUM_PCL = 0, 1  # pft_config::sum_order
 PFT_CD_RING = 32  # decisions kept by the change detector (pft_debug_change_state)
+PFT_TREE_INFO_WORDS = 64  # pft_debug_get_tree's info block
 K_RESAMPLE, K_AABB, K_CROP, K_OCTREE, K_LIKELIHOOD, K_POPULATION, K_PACK, K_COUNT = range(8)
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no input cloud", 3: "no reference cloud", 4: "no usable HIP device",
@@ -138,6 +139,7 @@ SYMBOLS = [
     ("pft_debug_get_input_records", C.c_int, [_vp, _vp, _sz, _sz]),
     ("pft_debug_get_octree", C.c_int, [_vp, _P(_i32), _vp, _vp, _P(_u32), _P(_u32)]),
     ("pft_debug_get_point_keys", C.c_int, [_vp, _vp, _sz]),
+    ("pft_debug_get_tree", C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz]),
     ("pft_debug_get_scan_stats", C.c_int, [_vp, _P(_u64), _P(_u64)]),
     ("pft_debug_set_limits", C.c_int, [_vp, _u32, C.c_int]),
     ("pft_debug_inject_error", C.c_int, [_vp, _u32]),

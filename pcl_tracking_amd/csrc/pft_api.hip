@@ -1684,6 +1684,52 @@ extern "C" int pft_debug_get_point_keys(pft_tracker* t, uint32_t* keys3, size_t 
   return PFT_OK;
 }
 
+extern "C" int pft_debug_get_tree(pft_tracker* t, uint32_t* info, uint32_t* words, size_t words_cap, uint32_t* leaf_order,
+                                  size_t leaf_order_cap, void* leaf_pts, size_t leaf_pts_cap, void* crop_pts,
+                                  size_t crop_pts_cap, uint16_t* jump, size_t jump_cap) {
+  if (!t || !info) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size != 1 || t->cfg.exact_nearest) {
+    t->err = "pft_debug_get_tree: sharded handles (world_size > 1) and the exact nearest-neighbour mode build no octree";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (t->in_cap == 0 || !t->d_words) {
+    t->err = "pft_debug_get_tree before the first input cloud: no tree buffers yet";
+    return PFT_ERR_STATE;
+  }
+  hipSetDevice(t->cfg.device_id);
+  PftHeader h;
+  int r = read_hdr(t, &h);  // (synchronises the stream)
+  if (r != PFT_OK) return r;
+  const size_t n_jump = (size_t)1 << (3 * PFT_JUMP_MAX_LEVEL);
+  uint32_t f32[5];
+  memcpy(&f32[0], &h.margin_cells, 4);
+  memcpy(&f32[1], &h.inv_res, 4);
+  memcpy(&f32[2], h.ominf, 12);
+  memset(info, 0, PFT_TREE_INFO_WORDS * sizeof(uint32_t));
+  info[0] = h.n_crop; info[1] = h.error; info[2] = (uint32_t)h.depth; info[3] = (uint32_t)h.use_table;
+  info[4] = h.n_words; info[5] = h.n_leaves; info[6] = h.leaf_start; info[7] = (uint32_t)h.n_grow;
+  info[8] = (uint32_t)h.build_path; info[9] = (uint32_t)h.leaf_indirect; info[10] = (uint32_t)h.jump_level;
+  for (int k = 0; k < 5; k++) info[11 + k] = f32[k];
+  info[16] = h.build_epoch; info[17] = h.build_variant;
+  info[18] = ((uint32_t)pftk_max_lds_bytes() - 10240u) & ~15u;  // pftk_octree's request
+  info[19] = (uint32_t)n_jump;
+  static_assert(20 + PFT_MAX_DEPTH + 3 <= PFT_TREE_INFO_WORDS, "lvl_start does not fit the info block");
+  for (int l = 0; l <= h.depth + 1 && l < PFT_MAX_DEPTH + 3 && h.depth > 0; l++) info[20 + l] = h.lvl_start[l];
+  // (counts are bounded by the allocations whatever the header says)
+  const size_t n_pts = std::min<size_t>(h.n_crop, t->in_cap);
+  const size_t n_words = std::min<size_t>(h.n_words, (size_t)t->in_cap * 8u + 64u);
+  auto copy = [&](void* dst, const void* src, size_t cap, size_t count, size_t elem) -> hipError_t {
+    const size_t c = std::min(cap, count);
+    return dst && src && c ? hipMemcpy(dst, src, c * elem, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  HIPCHK(t, copy(words, t->d_words, words_cap, n_words, sizeof(uint32_t)));
+  HIPCHK(t, copy(leaf_order, t->d_leaf_order, leaf_order_cap, n_pts, sizeof(uint32_t)));
+  HIPCHK(t, copy(leaf_pts, t->d_leaf_pts, leaf_pts_cap, n_pts, sizeof(float4)));
+  HIPCHK(t, copy(crop_pts, t->d_crop_pts, crop_pts_cap, n_pts, sizeof(float4)));
+  HIPCHK(t, copy(jump, t->d_jump, jump_cap, n_jump, sizeof(uint16_t)));
+  return PFT_OK;
+}
+
 extern "C" int pft_debug_get_ticks(pft_tracker* t, uint64_t* ticks32) {
   if (!t || !ticks32) return PFT_ERR_INVALID_ARG;
   PftHeader h;

@@ -104,6 +104,11 @@ struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (
   uint32_t lvl_start[PFT_MAX_DEPTH + 3];
   int32_t n_grow;
   int32_t build_path;   // 1 = register/LDS-resident builder, 0 = generic builder (diagnostic)
+  // which builder instance produced the tree (read by the test hook pft_debug_get_tree only).  k_octree_build: bits 0-2 the
+  // per-point store (1 RegStore<4>, 2 RegStore<8>, 3 RegStore<14>, 4 HybridStore<8>, 5 GlobStore), bit 3 the node words
+  // ended in LDS, bit 4 the leaf scratch was in LDS, bit 5 an LDS attempt was abandoned and the tree rebuilt in HBM, bit 6
+  // dense top levels (J > 0), bit 7 the rescue launch did the build, bits 8-9 copy_leaf_pts.  Sorted builder: 6 | npass << 10
+  uint32_t build_variant;
   int32_t leaf_indirect;  // 1: leaf_pts was NOT written for this tree; the likelihood kernel reads crop_pts[leaf_order[pos]]
   // fast descent (pft_likelihood.hip): direct-index table of the level-J nodes and the safety margin
   int32_t jump_level;   // J (0 = no table): jump[kx | ky<<J | kz<<2J] = 1 + index of the node inside level J

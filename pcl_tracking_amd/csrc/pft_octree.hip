@@ -161,6 +161,7 @@ struct RegStore {
   typedef uint32_t key_t;
   static constexpr int B = 10;
   static constexpr bool MORTON = true;  // 30-bit keys are kept bit-interleaved: a level's child index is one bit-field extract
+  static constexpr uint32_t CODE = K == 4 ? 1u : (K == 8 ? 2u : 3u);  // PftHeader::build_variant bits 0-2
   uint32_t key[K], node[K];
   __device__ RegStore(const PftDev&) {}
   template <class F>
@@ -180,6 +181,7 @@ struct HybridStore {
   typedef uint32_t key_t;
   static constexpr int B = 10;
   static constexpr bool MORTON = true;
+  static constexpr uint32_t CODE = 4u;
   uint32_t key[K], node[K];
   uint32_t* gkey;
   uint32_t* gnode;
@@ -200,6 +202,7 @@ struct GlobStore {
   typedef unsigned long long key_t;
   static constexpr int B = 21;
   static constexpr bool MORTON = false;  // (x << 42 | y << 21 | z)
+  static constexpr uint32_t CODE = 5u;
   unsigned long long* key;
   uint32_t* node;
   __device__ GlobStore(const PftDev& d) : key(d.pt_key64), node(d.pt_node) {}
@@ -478,7 +481,11 @@ __device__ __forceinline__ bool build_tree(const PftParams& prm, const PftDev& d
       start += c;
     }
   }
-  if (tid == 0) W[leaf_start + n_leaves] = n;  // sentinel: count(leaf j) = start[j+1] - start[j]
+  if (tid == 0) {
+    W[leaf_start + n_leaves] = n;  // sentinel: count(leaf j) = start[j+1] - start[j]
+    // the instance that got this far (compile-time constants: PftHeader::build_variant bits 0-4)
+    S.variant = Store::CODE | (LDSW ? 8u : 0u) | (TMPLDS ? 16u : 0u);
+  }
   __syncthreads();
   STAMP(4);
   uint32_t* TMP = TMPLDS ? lds_tmp : d.pt_tmp;
@@ -560,6 +567,7 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
     S.ngrow = 0;
     S.depth = 0;
     S.cur = 1;
+    S.variant = 0;  // (no instance has built anything yet)
     if (n > 0) box_init(S, p_first, prm.res);
   }
   __syncthreads();
@@ -611,6 +619,14 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
     hdr->use_table = use_table;
     hdr->n_grow = S.ngrow;
     hdr->build_path = path;
+    // which of this kernel's instances built the tree (tests/test_gpu_octree_structure.py): bits 0-2 store (1 RegStore<4>,
+    // 2 <8>, 3 <14>, 4 HybridStore<8>, 5 GlobStore), 3 node words ended in LDS, 4 leaf scratch in LDS, 5 an LDS attempt
+    // was abandoned, 6 dense top levels, 7 rescue launch, 8-9 copy_leaf_pts
+    // (bit 5: the tree was built in HBM although the carve, formed again here, left room for an LDS attempt)
+    const uint32_t lds_total = lds_bytes / 4u, var = S.variant;
+    const bool tried = lds_total - ((size_t)n * 5u / 2u + 64u <= lds_total ? ((n + 3u) & ~3u) : 0u) >= 64u;
+    hdr->build_variant = var | ((var && !(var & 8u) && tried) ? 32u : 0u) | ((ok && use_table && S.jump > 0) ? 64u : 0u) |
+                         (rescue ? 128u : 0u) | ((uint32_t)copy_leaf_pts << 8);
     hdr->leaf_indirect = copy_leaf_pts == 2 ? 1 : 0;  // 2: nobody copies the records, the likelihood kernel follows leaf_order
     if (d.host_stat) d.host_stat[1] = (uint32_t)D;
     hdr->jump_level = (ok && use_table) ? S.jump : 0;

@@ -9,7 +9,8 @@
 struct BuildSh {
   double mn[3], mx[3];
   int depth, ngrow;
-  uint32_t cur, err, carry;
+  uint32_t cur, err;
+  uint32_t variant;  // k_octree_build: bits 0-5 of PftHeader::build_variant, left by the instance that built the tree
   int jump;
   uint32_t u32s[40];
   uint32_t gidx[PFT_MAX_GROW], gshift[PFT_MAX_GROW], gold[PFT_MAX_GROW];

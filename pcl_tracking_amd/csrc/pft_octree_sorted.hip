@@ -407,6 +407,7 @@ __global__ __launch_bounds__(1024) void k_so_scan(PftDev d, SortBufs sb, uint32_
     if (lane == 0) tot[l] = run;
   }
   __syncthreads();
+  if (threadIdx.x == 0) hdr->build_variant = 6u | (npass << 10);  // (the rescue launch replaces it with its own)
   if (threadIdx.x == 0 && !hdr->error && D > 0 && n > 0) {
     uint32_t off = 1;
     hdr->lvl_start[0] = 0;

@@ -551,6 +551,30 @@ class ParticleFilterTracker:
         self._ensure()
         self._check(self._L.pft_debug_set_limits(self._h, int(max_words), int(sorted_npass)))
 
+    def debugGetTree(self):
+        """the linearised octree of the last build (pft_debug_get_tree): the header fields as ints (margin_cells, inv_res
+        and ominf as float bits), lvl_start [depth + 2], words [n_words], leaf_order [n_crop], leaf_pts and crop_pts
+        (n_crop, 4) uint32 records, jump: the whole uint16 allocation"""
+        self._ensure()
+        info = np.zeros(_lib.PFT_TREE_INFO_WORDS, np.uint32)
+        self._check(self._L.pft_debug_get_tree(self._h, _ptr(info), None, 0, None, 0, None, 0, None, 0, None, 0))
+        n, n_words, n_jump = int(info[0]), int(info[4]), int(info[19])
+        words = np.zeros(n_words, np.uint32)
+        order = np.zeros(n, np.uint32)
+        leaf_pts = np.zeros((n, 4), np.uint32)
+        crop_pts = np.zeros((n, 4), np.uint32)
+        jump = np.zeros(n_jump, np.uint16)
+        self._check(self._L.pft_debug_get_tree(self._h, _ptr(info), _ptr(words), n_words, _ptr(order), n, _ptr(leaf_pts), n,
+                                               _ptr(crop_pts), n, _ptr(jump), n_jump))
+        names = ("n_crop", "error", "depth", "use_table", "n_words", "n_leaves", "leaf_start", "n_grow", "build_path",
+                 "leaf_indirect", "jump_level", "margin_cells_bits", "inv_res_bits")
+        out = {k: int(info[i]) for i, k in enumerate(names)}
+        depth = out["depth"]
+        out.update(ominf_bits=info[13:16].copy(), build_epoch=int(info[16]), build_variant=int(info[17]),
+                   build_lds_bytes=int(info[18]), lvl_start=info[20:20 + depth + 2].copy() if depth > 0 else info[20:20].copy(),
+                   words=words, leaf_order=order, leaf_pts=leaf_pts, crop_pts=crop_pts, jump=jump)
+        return out
+
     def debugStateSave(self):
         """checkpoint of the filter state between two frames (HBM-resident)"""
         self._check(self._L.pft_debug_state_save(self._h))
