@@ -275,6 +275,63 @@ int pft_get_match_pairs(pft_tracker* t, int32_t* input_idx, float* sq_dist, size
  * fresh uniform population once before the first weight() */
 int pft_reset_tracking(pft_tracker* t);
 
+/* ---- re-acquisition of a lost object: candidate poses scored on the device ----
+ * K = n_centres * n_roll * n_pitch * n_yaw candidate poses -- every centre (usually the cluster centroids of a fresh
+ * segmentation of the current frame) with every orientation of a lattice -- are scored against the handle's current input
+ * cloud, the best one is selected, and with `apply` the tracker is restarted there.  Synchronous, like model preparation:
+ * re-acquisition is a rare event, not a per-frame cost.
+ *   candidate k = ((c * n_roll + ir) * n_pitch + ip) * n_yaw + iy:  position = centre c, per axis
+ *       angle = (float)((double)base + (double)span * (((double)i + 0.5) / (double)n - 0.5))
+ *     (offset 0 for n = 1, symmetric otherwise, no duplicate at a full-circle span); T_k = pose_to_matrix on the device
+ *   crop, tree  over the box of all K transformed reference clouds, by the handle's builders, as pft_eval_weights drives them
+ *   per reference point p_j:  q = T_k p_j, (partner, d2) = the search of pft_match;
+ *       matched_j = (double)d2 < max_distance^2,   inlier_j = (double)d2 < inlier_distance^2
+ *   n_matched, n_inliers  integers;  coherence, sum_sq_dist  as pft_match forms them (the same bits for the same T and
+ *       tree);  inlier_sq_dist = sum of inlier_j x (double)d2, the same adjacent-pair tree in double
+ *   best      the largest n_inliers; ties: the smaller inlier_sq_dist (in double), then the lowest k
+ *   accepted  K > 0 && n_inliers >= 1 && !((double)n_inliers < accept_ratio * (double)n_reference)
+ * With apply != 0 and accepted: pft_set_trans(the 4x4 of `transform`) + pft_reset_tracking -- the handle is exactly what those
+ * two calls leave.  Otherwise the population, the weights, the resample epoch and the match streak are left alone; like
+ * pft_eval_weights the call rebuilds the handle's tree, so a pft_match before the next pft_compute returns PFT_ERR_STATE.
+ * Device-side builder failures are reported as by pft_get_result; nothing is applied then.  Zero centres (or a segmenter
+ * without clusters): PFT_OK with n_candidates = 0, best = -1, accepted = 0.
+ * PFT_ERR_INVALID_ARG with a text: a sharded handle, an exact-NN handle, a bad configuration value, a non-finite centre, a
+ * segmenter on another device.  PFT_ERR_CAPACITY: K above PFT_REACQUIRE_MAX_CANDIDATES.  PFT_ERR_STATE: a segmenter that was
+ * never applied.  PFT_ERR_NO_INPUT / PFT_ERR_NO_REFERENCE as pft_compute. */
+#define PFT_REACQUIRE_MAX_CANDIDATES 65536
+typedef struct pft_reacquire_config {
+  int32_t n_roll, n_pitch, n_yaw;           /* >= 1 each */
+  float base_rpy[3], span_rpy[3];           /* finite, span >= 0 */
+  double inlier_distance;                   /* 0 < . <= max_distance; default 0.02 */
+  double accept_ratio;                      /* [0, 1]; default 0.5 */
+  int32_t apply;                            /* accepted: pft_set_trans(best) + pft_reset_tracking */
+} pft_reacquire_config;                     /* 64 B */
+
+typedef struct pft_reacquire_result {
+  uint32_t n_centres, n_candidates, n_reference, n_crop;
+  int32_t best, best_centre;                /* -1 when K == 0 */
+  pft_particle pose; float transform[12];   /* the best candidate and the T it was scored with (row-major 3x4) */
+  uint32_t n_inliers, n_matched, accepted, applied;
+  double coherence, sum_sq_dist, inlier_sq_dist;
+} pft_reacquire_result;                     /* 144 B */
+
+/* 1 x 1 x 8 orientations, base 0, span (0, 0, 2 pi): yaw over the full circle; 0.02, 0.5, apply = 1 */
+void pft_reacquire_config_default(pft_reacquire_config* cfg);
+/* centres_xyz: n_centres x 3 floats on the host */
+int pft_reacquire(pft_tracker* t, const float* centres_xyz, size_t n_centres, const pft_reacquire_config* cfg,
+                  pft_reacquire_result* out);
+/* the centres are compute3DCentroid (PCL's serial float chains) of every cluster of the segmenter's last apply, formed on
+ * the device from where the clusters lie in HBM, in cluster order */
+struct pft_segment;
+int pft_reacquire_from_segmenter(pft_tracker* t, struct pft_segment* s, const pft_reacquire_config* cfg,
+                                 pft_reacquire_result* out);
+/* the candidates and scores of the last re-acquisition call, in candidate order; every array is optional and receives
+ * min(cap, K) elements (mats12: 12 floats each), centres_xyz all of the call's centres (3 floats each; room for them is the
+ * caller's business: pft_reacquire_result::n_centres); *n = K.  PFT_ERR_STATE before the first call */
+int pft_get_reacquire_scores(pft_tracker* t, pft_particle* cand, float* mats12, uint32_t* n_inliers, uint32_t* n_matched,
+                             double* coherence, double* sum_sq_dist, double* inlier_sq_dist, float* centres_xyz,
+                             size_t cap, size_t* n);
+
 /* ---- multi-GPU phase API (one handle per rank; the collectives between the phases are issued by
  *      the host layer on the same stream, see pcl_tracking_amd/dist.py and DESIGN.md) ----
  * The host layer owns three device buffers and binds them once:

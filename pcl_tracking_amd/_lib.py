@@ -61,6 +61,29 @@ class MatchStatsStruct(C.Structure):
     ]
 
 
+class ReacquireConfig(C.Structure):
+    """pft_reacquire_config (include/pft.h): the orientation lattice, the inlier gate and the acceptance rule, 64 bytes"""
+    _fields_ = [
+        ("n_roll", C.c_int32), ("n_pitch", C.c_int32), ("n_yaw", C.c_int32),
+        ("base_rpy", C.c_float * 3), ("span_rpy", C.c_float * 3),
+        ("inlier_distance", C.c_double), ("accept_ratio", C.c_double), ("apply", C.c_int32),
+    ]
+
+
+class ReacquireResultStruct(C.Structure):
+    """pft_reacquire_result (include/pft.h): the selected candidate of one re-acquisition call, 144 bytes"""
+    _fields_ = [
+        ("n_centres", C.c_uint32), ("n_candidates", C.c_uint32), ("n_reference", C.c_uint32), ("n_crop", C.c_uint32),
+        ("best", C.c_int32), ("best_centre", C.c_int32),
+        ("pose", C.c_float * 8), ("transform", C.c_float * 12),
+        ("n_inliers", C.c_uint32), ("n_matched", C.c_uint32), ("accepted", C.c_uint32), ("applied", C.c_uint32),
+        ("coherence", C.c_double), ("sum_sq_dist", C.c_double), ("inlier_sq_dist", C.c_double),
+    ]
+
+
+PFT_REACQUIRE_MAX_CANDIDATES = 65536
+
+
 class FilterConfig(C.Structure):
     """pft_filter_config (include/pft_filters.h)"""
     _fields_ = [
@@ -175,6 +198,10 @@ SYMBOLS = [
     ("pft_get_match", C.c_int, [_vp, _P(MatchStatsStruct)]),
     ("pft_get_match_pairs", C.c_int, [_vp, _vp, _vp, _sz, _P(_sz)]),
     ("pft_reset_tracking", C.c_int, [_vp]),
+    ("pft_reacquire_config_default", None, [_P(ReacquireConfig)]),
+    ("pft_reacquire", C.c_int, [_vp, _vp, _sz, _P(ReacquireConfig), _P(ReacquireResultStruct)]),
+    ("pft_reacquire_from_segmenter", C.c_int, [_vp, _vp, _P(ReacquireConfig), _P(ReacquireResultStruct)]),
+    ("pft_get_reacquire_scores", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _P(_sz)]),
     ("pft_kld_normal_quantile", _f64, [_f64]),
     ("pft_kld_bound", _f64, [C.c_int, _f64, _f64]),
     ("pft_profile_enable", C.c_int, [_vp, C.c_int]),

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "pft_internal.h"
+#include "../../include/pft_segment.h"
 
 #define HIPCHK(t, call)                                                                       \
   do {                                                                                        \
@@ -160,6 +161,21 @@ struct pft_tracker {
   bool tree_of_compute = false;  // the tree, crop and result on the device are those of the last pft_compute
   double match_min_ratio = 0.0;
   int match_lost_after = 1;
+
+  // re-acquisition (pft_reacquire): buffers of the feature's own, sized for the largest K seen (never the handle's
+  // particle_num-sized ones): candidates, their matrices, the scores, the partial boxes of k_aabb, the result block
+  pft_particle* d_rq_part = nullptr;
+  float* d_rq_mats = nullptr;
+  PftRqScores rq_sc = {};
+  uint32_t rq_cap = 0;           // candidates the arrays above have room for
+  float* d_rq_centres = nullptr;
+  uint32_t *d_rq_first = nullptr, *d_rq_count = nullptr;  // the segmenter form: every cluster's first point and size
+  uint32_t rq_centres_cap = 0;
+  float* d_rq_bbox_part = nullptr;  // num_cus partial boxes
+  pft_reacquire_result* d_rq_result = nullptr;
+  uint32_t rq_n = 0;             // candidates of the last call
+  bool rq_valid = false;         // a call has completed: the arrays hold its candidates and scores
+  std::vector<float> rq_centres;  // the last call's centres (host copy)
 
   // state
   bool has_ref = false, has_input = false, initialized = false, changed = false;
@@ -759,6 +775,9 @@ extern "C" void pft_destroy(pft_tracker* t) {
   cd_free(t->cd); cd_free(t->cd_dbg);
   dfree(t->d_rep_pts); dfree(t->d_rep_tracked); dfree(t->d_report);
   dfree(t->d_match); dfree(t->d_match_idx); dfree(t->d_match_d2);
+  dfree(t->d_rq_part); dfree(t->d_rq_mats); dfree(t->rq_sc.n_inliers); dfree(t->rq_sc.n_matched); dfree(t->rq_sc.coherence);
+  dfree(t->rq_sc.sum_sq_dist); dfree(t->rq_sc.inlier_sq_dist); dfree(t->d_rq_centres); dfree(t->d_rq_first);
+  dfree(t->d_rq_count); dfree(t->d_rq_bbox_part); dfree(t->d_rq_result);
   dfree(t->sv_cd); dfree(t->sv_cd_key[0]); dfree(t->sv_cd_key[1]); dfree(t->sv_cd_cnt[0]); dfree(t->sv_cd_cnt[1]);
   if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
   delete t;
@@ -1048,7 +1067,8 @@ static void stage_resample_aabb(pft_tracker* t, bool finalize) {
 __global__ void k_inject_error(PftHeader* hdr, uint32_t bits) { hdr->error |= bits; }
 
 static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32_t np, bool debug_nn,
-                                         bool bbox_from_partials, bool keep_point_keys = false) {
+                                         bool bbox_from_partials, bool keep_point_keys = false,
+                                         bool likelihood = true) {
   {
     ProfScope ps(t, PFT_K_CROP);
     if (++t->crop_epoch == 0) t->crop_epoch = 1;
@@ -1178,6 +1198,7 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
       pftk_octree(t->stream, t->prm, db, last_n, t->leaf_indirect);
     }
   }
+  if (!likelihood) return;  // pft_reacquire: crop and tree only, its own kernel reads the tree
   {
     ProfScope ps(t, PFT_K_LIKELIHOOD);
     const int flags = (t->sw.generic_descent ? 0 : 1) | (t->sw.ancestor_table ? 2 : 0) | (t->sw.ablate << 8);
@@ -2441,4 +2462,238 @@ extern "C" int pft_reset_tracking(pft_tracker* t) {
   t->tree_of_compute = false;
   if (t->h_stat) t->h_stat[0] = t->h_stat[1] = 0;
   return match_clear_streak(t);
+}
+
+// ---- re-acquisition of a lost object (pft_reacquire.hip) ----
+extern "C" void pft_reacquire_config_default(pft_reacquire_config* c) {
+  if (!c) return;
+  memset(c, 0, sizeof(*c));
+  c->n_roll = c->n_pitch = 1;
+  c->n_yaw = 8;
+  c->span_rpy[2] = 6.2831853071795864769f;  // yaw over the full circle
+  c->inlier_distance = 0.02;
+  c->accept_ratio = 0.5;
+  c->apply = 1;
+}
+
+static int rq_reserve(pft_tracker* t, uint32_t K, uint32_t n_centres) {
+  if (K > t->rq_cap) {
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+    dfree(t->d_rq_part); dfree(t->d_rq_mats); dfree(t->rq_sc.n_inliers); dfree(t->rq_sc.n_matched);
+    dfree(t->rq_sc.coherence); dfree(t->rq_sc.sum_sq_dist); dfree(t->rq_sc.inlier_sq_dist);
+    t->rq_cap = 0;
+    t->rq_valid = false;
+    HIPCHK(t, dalloc(&t->d_rq_part, (size_t)K));
+    HIPCHK(t, dalloc(&t->d_rq_mats, (size_t)K * 12u));
+    HIPCHK(t, dalloc(&t->rq_sc.n_inliers, (size_t)K));
+    HIPCHK(t, dalloc(&t->rq_sc.n_matched, (size_t)K));
+    HIPCHK(t, dalloc(&t->rq_sc.coherence, (size_t)K));
+    HIPCHK(t, dalloc(&t->rq_sc.sum_sq_dist, (size_t)K));
+    HIPCHK(t, dalloc(&t->rq_sc.inlier_sq_dist, (size_t)K));
+    t->rq_cap = K;
+  }
+  if (n_centres > t->rq_centres_cap) {
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+    dfree(t->d_rq_centres); dfree(t->d_rq_first); dfree(t->d_rq_count);
+    t->rq_centres_cap = 0;
+    HIPCHK(t, dalloc(&t->d_rq_centres, (size_t)n_centres * 3u));
+    HIPCHK(t, dalloc(&t->d_rq_first, (size_t)n_centres));
+    HIPCHK(t, dalloc(&t->d_rq_count, (size_t)n_centres));
+    t->rq_centres_cap = n_centres;
+  }
+  if (!t->d_rq_bbox_part) HIPCHK(t, dalloc(&t->d_rq_bbox_part, (size_t)t->num_cus * 6u));
+  if (!t->d_rq_result) HIPCHK(t, dalloc(&t->d_rq_result, 1));
+  return PFT_OK;
+}
+
+// the refusals that do not depend on the centres; *per_centre = n_roll * n_pitch * n_yaw
+static int rq_check(pft_tracker* t, const pft_reacquire_config* c, const char* who, uint64_t* per_centre) {
+  if (t->cfg.world_size != 1) {
+    t->err = std::string(who) + " is not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (t->cfg.exact_nearest) {
+    t->err = std::string(who) + " is not supported with the exact nearest-neighbour coherence (exact_nearest): that mode builds no octree";
+    return PFT_ERR_INVALID_ARG;
+  }
+  const int r = check_ready(t);
+  if (r != PFT_OK) return r;
+  bool ok = c->n_roll >= 1 && c->n_pitch >= 1 && c->n_yaw >= 1;
+  for (int a = 0; a < 3; a++) ok = ok && std::isfinite(c->base_rpy[a]) && std::isfinite(c->span_rpy[a]) && c->span_rpy[a] >= 0.0f;
+  ok = ok && c->inlier_distance > 0.0 && c->inlier_distance <= t->cfg.max_distance;
+  ok = ok && c->accept_ratio >= 0.0 && c->accept_ratio <= 1.0;
+  if (!ok) {
+    t->err = std::string(who) + ": bad configuration value (n_roll, n_pitch, n_yaw >= 1; base_rpy finite; span_rpy finite and >= 0; "
+             "0 < inlier_distance <= max_distance; accept_ratio in [0, 1])";
+    return PFT_ERR_INVALID_ARG;
+  }
+  *per_centre = (uint64_t)c->n_roll * (uint64_t)c->n_pitch * (uint64_t)c->n_yaw;
+  return PFT_OK;
+}
+
+static int rq_capacity(pft_tracker* t, const char* who, uint64_t per_centre, size_t n_centres) {
+  if (per_centre > PFT_REACQUIRE_MAX_CANDIDATES || (uint64_t)n_centres > PFT_REACQUIRE_MAX_CANDIDATES ||
+      per_centre * (uint64_t)n_centres > PFT_REACQUIRE_MAX_CANDIDATES) {
+    t->err = std::string(who) + ": " + std::to_string(n_centres) + " centres x " + std::to_string(per_centre) +
+             " orientations exceed PFT_REACQUIRE_MAX_CANDIDATES (" + std::to_string(PFT_REACQUIRE_MAX_CANDIDATES) + ")";
+    return PFT_ERR_CAPACITY;
+  }
+  return PFT_OK;
+}
+
+// the centres are in t->rq_centres (host) and, with on_device, already in d_rq_centres as well
+static int rq_run(pft_tracker* t, const char* who, const pft_reacquire_config* c, uint64_t per_centre, bool on_device,
+                  pft_reacquire_result* out) {
+  const uint32_t n_centres = (uint32_t)(t->rq_centres.size() / 3u);
+  for (size_t i = 0; i < t->rq_centres.size(); i++)
+    if (!std::isfinite(t->rq_centres[i])) {
+      t->err = std::string(who) + ": centre " + std::to_string(i / 3u) + " has a non-finite coordinate";
+      t->rq_valid = false;
+      return PFT_ERR_INVALID_ARG;
+    }
+  const uint32_t K = (uint32_t)(per_centre * n_centres), M = t->prm.M;
+  memset(out, 0, sizeof(*out));
+  out->n_centres = n_centres;
+  out->n_reference = M;
+  out->best = out->best_centre = -1;
+  t->rq_n = K;
+  if (K == 0) {  // nothing to score: the tracker, its tree included, is left as it is
+    t->rq_valid = true;
+    return PFT_OK;
+  }
+  t->rq_valid = false;
+  int r = rq_reserve(t, K, n_centres);
+  if (r != PFT_OK) return r;
+  sync_dev(t);
+  t->tree_of_compute = false;  // the crop and the tree are rebuilt for the candidates
+  if (!on_device)
+    HIPCHK(t, hipMemcpyAsync(t->d_rq_centres, t->rq_centres.data(), t->rq_centres.size() * sizeof(float), hipMemcpyHostToDevice,
+                             t->stream));
+  PftRqLattice lat;
+  lat.n[0] = (uint32_t)c->n_roll;
+  lat.n[1] = (uint32_t)c->n_pitch;
+  lat.n[2] = (uint32_t)c->n_yaw;
+  for (int a = 0; a < 3; a++) {
+    lat.base[a] = c->base_rpy[a];
+    lat.span[a] = c->span_rpy[a];
+  }
+  pftk_reacquire_candidates(t->stream, t->d_rq_centres, K, lat, t->d_rq_part, t->d_rq_mats);
+  PftDev d = t->dev;
+  d.p_active = nullptr;  // explicit candidate count (a KLD handle's device-side count does not apply here)
+  d.part_cur = t->d_rq_part;
+  d.part_all = t->d_rq_part;
+  d.mats = t->d_rq_mats;
+  d.bbox_part = t->d_rq_bbox_part;
+  d.bbox_grid = (uint32_t)t->num_cus;
+  d.bbox_part_cap = (uint32_t)t->num_cus;
+  d.bbox6 = t->d_bbox6;
+  d.gate = nullptr;
+  // the change detector's state belongs to the frames the tracker computes: this crop is not tested
+  const bool gate_on = t->gate_on;
+  t->gate_on = false;
+  stage_aabb(t, d, K, false);
+  stage_crop_octree_likelihood(t, d, K, false, true, false, false);
+  t->gate_on = gate_on;
+  pftk_reacquire_score(t->stream, t->prm, d, K, c->inlier_distance * c->inlier_distance, t->rq_sc);
+  pftk_reacquire_select(t->stream, t->prm, d, t->rq_sc, K, n_centres, (uint32_t)per_centre, c->accept_ratio, t->d_rq_result);
+  HIPCHK(t, hipGetLastError());
+  HIPCHK(t, hipMemcpyAsync(out, t->d_rq_result, sizeof(*out), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  t->rq_valid = true;
+  r = check_device_error(t);
+  if (r != PFT_OK) {  // the scores had no target: nothing is accepted, nothing applied
+    out->accepted = 0u;
+    return r;
+  }
+  if (c->apply && out->accepted) {
+    float m[16] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    memcpy(m, out->transform, sizeof(float) * 12);
+    r = pft_set_trans(t, m);
+    if (r == PFT_OK) r = pft_reset_tracking(t);
+    if (r != PFT_OK) return r;
+    out->applied = 1u;
+  }
+  return PFT_OK;
+}
+
+extern "C" int pft_reacquire(pft_tracker* t, const float* centres_xyz, size_t n_centres, const pft_reacquire_config* cfg,
+                             pft_reacquire_result* out) {
+  if (!t || !cfg || !out || (!centres_xyz && n_centres)) return PFT_ERR_INVALID_ARG;
+  uint64_t per_centre = 0;
+  int r = rq_check(t, cfg, "pft_reacquire", &per_centre);
+  if (r != PFT_OK) return r;
+  r = rq_capacity(t, "pft_reacquire", per_centre, n_centres);
+  if (r != PFT_OK) return r;
+  t->rq_centres.assign(centres_xyz, centres_xyz + 3u * n_centres);
+  return rq_run(t, "pft_reacquire", cfg, per_centre, false, out);
+}
+
+extern "C" int pft_reacquire_from_segmenter(pft_tracker* t, pft_segment* s, const pft_reacquire_config* cfg,
+                                            pft_reacquire_result* out) {
+  if (!t || !s || !cfg || !out) return PFT_ERR_INVALID_ARG;
+  const char* who = "pft_reacquire_from_segmenter";
+  uint64_t per_centre = 0;
+  int r = rq_check(t, cfg, who, &per_centre);
+  if (r != PFT_OK) return r;
+  const pft_point_xyzrgba* d_pts = nullptr;
+  size_t total = 0, nc = 0;
+  if (pft_segment_clusters_device(s, &d_pts, &total) != PFT_OK || pft_segment_cluster_count(s, &nc) != PFT_OK) {
+    t->err = std::string(who) + ": the segmenter has not been applied yet";
+    return PFT_ERR_STATE;
+  }
+  if (pftsg_device_id(s) != t->cfg.device_id) {
+    t->err = std::string(who) + ": the segmenter lives on device " + std::to_string(pftsg_device_id(s)) +
+             ", the tracker on device " + std::to_string(t->cfg.device_id);
+    return PFT_ERR_INVALID_ARG;
+  }
+  r = rq_capacity(t, who, per_centre, nc);
+  if (r != PFT_OK) return r;
+  t->rq_centres.assign(3u * nc, 0.0f);
+  if (nc) {
+    std::vector<uint32_t> sizes(nc), first(nc);
+    r = pft_segment_cluster_sizes(s, sizes.data(), nc);
+    if (r != PFT_OK) return r;
+    size_t off = 0;
+    for (size_t k = 0; k < nc; k++) {
+      first[k] = (uint32_t)off;
+      off += sizes[k];
+    }
+    if (off > total || !d_pts) return PFT_ERR_STATE;
+    r = rq_reserve(t, 0u, (uint32_t)nc);
+    if (r != PFT_OK) return r;
+    // the segmenter's apply has finished on its stream (it returns when the clusters are known); the clusters are read by
+    // this call's launch only, which has finished when it returns
+    HIPCHK(t, hipMemcpyAsync(t->d_rq_first, first.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+    HIPCHK(t, hipMemcpyAsync(t->d_rq_count, sizes.data(), nc * sizeof(uint32_t), hipMemcpyHostToDevice, t->stream));
+    pftk_reacquire_centroids(t->stream, d_pts, t->d_rq_first, t->d_rq_count, (uint32_t)nc, t->d_rq_centres);
+    HIPCHK(t, hipGetLastError());
+    HIPCHK(t, hipMemcpyAsync(t->rq_centres.data(), t->d_rq_centres, 3u * nc * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+  }
+  return rq_run(t, who, cfg, per_centre, true, out);
+}
+
+extern "C" int pft_get_reacquire_scores(pft_tracker* t, pft_particle* cand, float* mats12, uint32_t* n_inliers,
+                                        uint32_t* n_matched, double* coherence, double* sum_sq_dist, double* inlier_sq_dist,
+                                        float* centres_xyz, size_t cap, size_t* n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!t->rq_valid) {
+    t->err = "pft_get_reacquire_scores: no completed pft_reacquire call to read";
+    return PFT_ERR_STATE;
+  }
+  if (n) *n = t->rq_n;
+  if (centres_xyz && !t->rq_centres.empty()) memcpy(centres_xyz, t->rq_centres.data(), t->rq_centres.size() * sizeof(float));
+  const size_t c = cap < t->rq_n ? cap : t->rq_n;
+  if (!c) return PFT_OK;
+  hipSetDevice(t->cfg.device_id);
+  const hipMemcpyKind k = hipMemcpyDeviceToHost;
+  if (cand) HIPCHK(t, hipMemcpyAsync(cand, t->d_rq_part, c * sizeof(pft_particle), k, t->stream));
+  if (mats12) HIPCHK(t, hipMemcpyAsync(mats12, t->d_rq_mats, c * 12u * sizeof(float), k, t->stream));
+  if (n_inliers) HIPCHK(t, hipMemcpyAsync(n_inliers, t->rq_sc.n_inliers, c * sizeof(uint32_t), k, t->stream));
+  if (n_matched) HIPCHK(t, hipMemcpyAsync(n_matched, t->rq_sc.n_matched, c * sizeof(uint32_t), k, t->stream));
+  if (coherence) HIPCHK(t, hipMemcpyAsync(coherence, t->rq_sc.coherence, c * sizeof(double), k, t->stream));
+  if (sum_sq_dist) HIPCHK(t, hipMemcpyAsync(sum_sq_dist, t->rq_sc.sum_sq_dist, c * sizeof(double), k, t->stream));
+  if (inlier_sq_dist) HIPCHK(t, hipMemcpyAsync(inlier_sq_dist, t->rq_sc.inlier_sq_dist, c * sizeof(double), k, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  return PFT_OK;
 }

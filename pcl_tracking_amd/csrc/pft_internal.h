@@ -336,6 +336,28 @@ void pftk_report(hipStream_t s, const pft_point_xyzrgba* pts, uint32_t n, const 
 // (d.gate: the change detector's gate word or null), writes the statistics, the lost rule's state and the pairs
 void pftk_match(hipStream_t s, const PftParams& p, const PftDev& d, double min_ratio, uint32_t lost_after,
                 pft_match_stats* out, int32_t* input_idx, float* sq_dist);
+// re-acquisition (pft_reacquire.hip): the orientation lattice, the per-candidate score arrays (K each, owned by the feature)
+struct PftRqLattice {
+  uint32_t n[3];             // roll, pitch, yaw steps (>= 1)
+  float base[3], span[3];
+};
+struct PftRqScores {
+  uint32_t *n_inliers, *n_matched;
+  double *coherence, *sum_sq_dist, *inlier_sq_dist;
+};
+// compute3DCentroid of n_clusters runs of points (first / count per cluster, device arrays) -> centres [3 * n_clusters]
+void pftk_reacquire_centroids(hipStream_t s, const pft_point_xyzrgba* pts, const uint32_t* first, const uint32_t* count,
+                              uint32_t n_clusters, float* centres);
+// candidate k = ((c n_roll + ir) n_pitch + ip) n_yaw + iy -> part [K], mats [12 K]
+void pftk_reacquire_candidates(hipStream_t s, const float* centres, uint32_t K, const PftRqLattice& lat, pft_particle* part,
+                               float* mats);
+// one workgroup per candidate d.mats[k] against the tree of the last build; reads no particle, no partial box
+void pftk_reacquire_score(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t K, double inlier_d2,
+                          const PftRqScores& out);
+// one workgroup: the best candidate (d.part_cur / d.mats are the candidates') and the result block; mirrors
+// PftHeader::error into the pinned status block
+void pftk_reacquire_select(hipStream_t s, const PftParams& p, const PftDev& d, const PftRqScores& sc, uint32_t K,
+                           uint32_t n_centres, uint32_t per_centre, double accept_ratio, pft_reacquire_result* out);
 void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, int argorder, float4* xyz,
                          float4* hsv);
 void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out,

@@ -5,6 +5,7 @@
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
 //                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
+//                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -27,6 +28,12 @@
 // read) and prints one `match` line per object and frame; an object whose result matched fewer than min_ratio of its model
 // points for lost_after frames in a row is lost: `Object not recognized` on stderr, the reference's message (:695), and with
 // --reset-on-loss a resetTracking(), so that the next frame starts over from the object's initial position.
+// --reacquire[=n_yaw[,accept_ratio[,inlier_distance]]] (with --match) looks for a lost object instead: the frame goes through
+// the segmenter with the model-creation flags (segment_options.hpp; one segmentation per frame, shared by all objects lost in
+// it), and every lost object, in id order, scores its model at the cluster centroids x n_yaw orientations (pft_reacquire); it
+// is restarted at the best candidate if that one has at least accept_ratio of the model's points within inlier_distance,
+// and the centre it took is dropped for the others.  One `reacquire obj <j>: centre <c> candidate <k> inliers <n>/<M>
+// accepted <0|1>` line per lost object; when nothing is accepted, --reset-on-loss applies if given.
 #include <cstdlib>
 
 #include "segment_options.hpp"
@@ -80,6 +87,21 @@ int main(int argc, char** argv) {
       }
     }
     else if (!std::strcmp(argv[i], "--reset-on-loss")) opt.reset_on_loss = true;
+    else if (!std::strncmp(argv[i], "--reacquire", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) {
+      opt.reacquire = true;  // --reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]; the defaults 8,0.5,0.02
+      if (argv[i][11] == '=') {
+        int n_yaw = opt.rq_n_yaw;
+        double ratio = opt.rq_accept_ratio, inl = opt.rq_inlier_distance;
+        const int got = std::sscanf(argv[i] + 12, "%d,%lf,%lf", &n_yaw, &ratio, &inl);
+        if (got < 1 || n_yaw < 1 || !(ratio >= 0.0 && ratio <= 1.0) || !(inl > 0.0)) {
+          std::fprintf(stderr, "--reacquire=n_yaw[,accept_ratio[,inlier_distance]] with n_yaw >= 1, accept_ratio in [0, 1] and inlier_distance > 0\n");
+          return 2;
+        }
+        opt.rq_n_yaw = n_yaw;
+        opt.rq_accept_ratio = ratio;
+        opt.rq_inlier_distance = inl;
+      }
+    }
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -91,12 +113,16 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
   if (opt.reset_on_loss && !opt.match) {
     std::fprintf(stderr, "--reset-on-loss needs --match: it is the match that says an object is lost\n");
+    return 2;
+  }
+  if (opt.reacquire && !opt.match) {
+    std::fprintf(stderr, "--reacquire needs --match: it is the match that says an object is lost\n");
     return 2;
   }
   if (async && !raw) {
@@ -162,9 +188,10 @@ int main(int argc, char** argv) {
       if (opt.device_report) kv.second->computeReport();
       if (opt.match) kv.second->computeMatch();
     }
+    std::vector<int> lost;  // --reacquire: the objects the match reported lost in this frame
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
-      if (opt.match) v.reportMatch(f + 1, kv.first);
+      if (opt.match && v.reportMatch(f + 1, kv.first, !opt.reacquire) && opt.reacquire) lost.push_back(kv.first);
       if (opt.device_report) {
         const pft_object_report rep = kv.second->getReport();
         printObjectLine(f + 1, kv.first, result, rep.centroid);
@@ -174,6 +201,18 @@ int main(int argc, char** argv) {
       float centroid[4];
       v.objectPosition(kv.first, result, centroid);
       printObjectLine(f + 1, kv.first, result, centroid);
+    }
+    if (!lost.empty()) {  // one segmentation of the frame for all of them
+      try {
+        pft::ModelSegmenter frame_seg;
+        pft::VoxelGrid frame_grid;
+        segmentScene(so, cloud, frame_grid, frame_seg);
+        v.reacquireLost(lost, frame_seg);
+      } catch (const std::exception& e) {
+        std::fprintf(stderr, "reacquire: %s\n", e.what());
+        if (opt.reset_on_loss)
+          for (const int obj_id : lost) v.tracker_dict[obj_id]->resetTracking();
+      }
     }
     if (async)  // the counts, now that the frame's results are on the host
       std::fprintf(stderr, "PointCloud before downsampled: %zu data points.\nPointCloud after downsampled: %zu data points.\n",

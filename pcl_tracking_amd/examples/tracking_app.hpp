@@ -12,6 +12,8 @@
 //   --device-report      the same on the device (pft_report), with viz_cb's principal-axis box       :432-466
 //   --match              the match statistics of every result (pft_match) and the lost rule that makes the
 //                        reference's "Object not recognized" handler fire; --reset-on-loss: resetTracking() then  :692-696
+//   --reacquire          a lost object is looked for among the cluster centroids of a segmentation of the frame
+//                        (reacquire) and restarted where it is found
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -53,6 +55,10 @@ struct Options {
   double match_min_ratio = 0.0;         // lost after match_lost_after frames in a row below this matched share
   int match_lost_after = 1;
   bool reset_on_loss = false;           // resetTracking() on a lost object
+  bool reacquire = false;               // a lost object is looked for among the clusters of the frame (pft_reacquire)
+  int rq_n_yaw = 8;                     // yaw steps over the full circle around the object's initial orientation
+  double rq_accept_ratio = 0.5;         // inliers / model points a candidate needs
+  double rq_inlier_distance = 0.02;
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -227,8 +233,9 @@ class TrackingApp {
   }
 
   // the match hook of one object and frame, after its computeMatch(): prints the `match` line; a lost object gets the
-  // reference's message (:695) and, with --reset-on-loss, a resetTracking().  Returns true when the object is lost
-  bool reportMatch(size_t frame, int obj_id) {
+  // reference's message (:695) and, with --reset-on-loss, a resetTracking() -- unless the caller deals with the loss itself
+  // (reset = false: --reacquire).  Returns true when the object is lost
+  bool reportMatch(size_t frame, int obj_id, bool reset = true) {
     ParticleFilter& tr = *tracker_dict[obj_id];
     const pft_match_stats m = tr.getMatch();
     const double ratio = m.n_reference ? (double)m.n_matched / (double)m.n_reference : 0.0;
@@ -238,8 +245,51 @@ class TrackingApp {
                 m.lost);
     if (!m.lost) return false;
     std::fprintf(stderr, "frame %zu object %d: Object not recognized\n", frame, obj_id);
-    if (opt_.reset_on_loss) tr.resetTracking();
+    if (reset && opt_.reset_on_loss) tr.resetTracking();
     return true;
+  }
+
+  // --reacquire: the objects `lost` in this frame (ascending ids) against the clusters of `seg`, a segmentation of the frame.
+  // The first object takes its centres from the segmenter on the device; a centre accepted by one object is dropped for
+  // the others.  One line per object; an object that finds no place falls back to --reset-on-loss
+  template <class Segmenter>
+  void reacquireLost(const std::vector<int>& lost, Segmenter& seg) {
+    std::vector<float> centres;
+    std::vector<int> cluster_of;  // the segmenter's cluster index of every centre still to be had
+    bool have_centres = false;
+    for (const int obj_id : lost) {
+      ParticleFilter& tr = *tracker_dict[obj_id];
+      pft_reacquire_config cfg = tr.reacquireConfig();
+      cfg.n_yaw = opt_.rq_n_yaw;
+      cfg.accept_ratio = opt_.rq_accept_ratio;
+      cfg.inlier_distance = opt_.rq_inlier_distance;
+      cfg.apply = 1;
+      pft_reacquire_result res;
+      int st;
+      if (!have_centres) {
+        st = tr.reacquireFromSegmenter(seg, cfg, res);
+        if (st == PFT_OK) {
+          centres.assign((size_t)res.n_centres * 3u, 0.0f);
+          size_t k = 0;
+          pft_get_reacquire_scores(tr.nativeHandle(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   centres.data(), 0, &k);
+          for (uint32_t c = 0; c < res.n_centres; c++) cluster_of.push_back((int)c);
+          have_centres = true;
+        }
+      } else {
+        st = tr.reacquire(centres.data(), cluster_of.size(), cfg, res);
+      }
+      const bool accepted = st == PFT_OK && res.accepted;
+      const int centre = st == PFT_OK && res.best_centre >= 0 ? cluster_of[(size_t)res.best_centre] : -1;
+      std::printf("reacquire obj %d: centre %d candidate %d inliers %u/%u accepted %d\n", obj_id, centre,
+                  st == PFT_OK ? res.best : -1, res.n_inliers, res.n_reference, accepted ? 1 : 0);
+      if (accepted) {
+        centres.erase(centres.begin() + 3 * res.best_centre, centres.begin() + 3 * res.best_centre + 3);
+        cluster_of.erase(cluster_of.begin() + res.best_centre);
+      } else if (opt_.reset_on_loss) {
+        tr.resetTracking();
+      }
+    }
   }
 
   const Options& options() const { return opt_; }

@@ -419,6 +419,42 @@ class ParticleFilterTracker {
     if (handle_) check(pft_reset_tracking(handle_), "resetTracking");
   }
 
+  // ---- re-acquisition of a lost object (pft.h, pft_reacquire) ----
+  // every centre (n_centres x 3 floats) with every orientation of cfg's lattice is scored against the input cloud the handle
+  // holds -- the one of the last compute() --; with cfg.apply and an accepted candidate the tracker is restarted at it:
+  // setTrans(the candidate's matrix) + resetTracking().  Synchronous.  Returns the pft_status
+  int reacquire(const float* centres_xyz, size_t n_centres, const pft_reacquire_config& cfg, pft_reacquire_result& out) {
+    std::memset(&out, 0, sizeof(out));
+    out.best = out.best_centre = -1;
+    int st = handInput("reacquire");
+    if (st != PFT_OK) return st;
+    st = check(pft_reacquire(handle_, centres_xyz, n_centres, &cfg, &out), "reacquire");
+    if (st == PFT_OK) applied(out);
+    return st;
+  }
+  // the same with the cluster centroids of a pft::ModelSegmenter's last apply as centres, formed on the device
+  template <class Segmenter>
+  int reacquireFromSegmenter(Segmenter& seg, const pft_reacquire_config& cfg, pft_reacquire_result& out) {
+    std::memset(&out, 0, sizeof(out));
+    out.best = out.best_centre = -1;
+    int st = handInput("reacquireFromSegmenter");
+    if (st != PFT_OK) return st;
+    st = check(pft_reacquire_from_segmenter(handle_, seg.nativeHandle(), &cfg, &out), "reacquireFromSegmenter");
+    if (st == PFT_OK) applied(out);
+    return st;
+  }
+  // pft_reacquire_config_default with the angles of the current trans as the lattice's base
+  pft_reacquire_config reacquireConfig() const {
+    pft_reacquire_config c;
+    pft_reacquire_config_default(&c);
+    StateT s;
+    pft_to_state(trans_.m, &s);
+    c.base_rpy[0] = s.roll;
+    c.base_rpy[1] = s.pitch;
+    c.base_rpy[2] = s.yaw;
+    return c;
+  }
+
   int getIterationNum() const { return cfg_.iteration_num; }
   int getParticleNum() const { return cfg_.particle_num; }
   pft_tracker* nativeHandle() { return handle_; }
@@ -456,6 +492,16 @@ class ParticleFilterTracker {
       std::fprintf(stderr, "[pft::ParticleFilterTracker::%s] %s: %s\n", what, pft_status_string(st),
                    handle_ ? pft_last_error_string(handle_) : "");
     return st;
+  }
+  // re-acquisition scores against the input cloud the handle holds: the one of the last compute()
+  int handInput(const char* what) {
+    if (!ensure()) return check(PFT_ERR_NO_DEVICE, what);
+    return PFT_OK;
+  }
+  void applied(const pft_reacquire_result& r) {
+    if (!r.applied) return;
+    trans_ = Affine3f::Identity();  // what the handle now holds: the candidate's 3x4 over (0, 0, 0, 1)
+    std::memcpy(trans_.m, r.transform, sizeof(float) * 12);
   }
   void finish(int st) {
     if (!throw_on_failure_) return;

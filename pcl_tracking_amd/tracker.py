@@ -92,6 +92,42 @@ class MatchStats:
                    lost=bool(r.lost), calls=int(r.calls))
 
 
+@dataclass
+class ReacquireResult:
+    """pft_reacquire_result: the candidate a re-acquisition call selected"""
+    n_centres: int
+    n_candidates: int
+    n_reference: int
+    n_crop: int
+    best: int              # candidate index, -1 without candidates
+    best_centre: int
+    pose: np.ndarray       # PARTICLE_DTYPE record of the best candidate
+    transform: np.ndarray  # 3x4 float32, the T it was scored with
+    n_inliers: int
+    n_matched: int
+    accepted: bool
+    applied: bool
+    coherence: float
+    sum_sq_dist: float
+    inlier_sq_dist: float
+
+    @property
+    def trans(self):
+        """the 4x4 that apply hands to setTrans: `transform` over the row (0, 0, 0, 1)"""
+        m = np.eye(4, dtype=np.float32)
+        m[:3] = self.transform
+        return m
+
+    @classmethod
+    def from_struct(cls, r):
+        pose = np.frombuffer(bytes(r.pose), PARTICLE_DTYPE)[0].copy()
+        return cls(n_centres=int(r.n_centres), n_candidates=int(r.n_candidates), n_reference=int(r.n_reference),
+                   n_crop=int(r.n_crop), best=int(r.best), best_centre=int(r.best_centre), pose=pose,
+                   transform=np.array(r.transform, dtype=np.float32).reshape(3, 4), n_inliers=int(r.n_inliers),
+                   n_matched=int(r.n_matched), accepted=bool(r.accepted), applied=bool(r.applied),
+                   coherence=float(r.coherence), sum_sq_dist=float(r.sum_sq_dist), inlier_sq_dist=float(r.inlier_sq_dist))
+
+
 class DistanceCoherence:
     """pcl::tracking::DistanceCoherence (auto_tracking.cpp:240-242)"""
 
@@ -173,6 +209,7 @@ class ParticleFilterTracker:
         # ParticleFilterTracker's change detector: use, interval, min points, resolution (PCL's constructor defaults)
         self._cd = [False, 10, 10, 0.01]
         self._match_thr = (0.0, 1)  # pft_set_match_threshold: min_ratio, lost_after
+        self._rq_centres = 0  # centres of the last reacquire()
         self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
         self._ref = None
@@ -485,6 +522,63 @@ class ParticleFilterTracker:
         in force then; the change detector keeps its state, the lost rule's streak is cleared"""
         if self._h is not None:
             self._check(self._L.pft_reset_tracking(self._h))
+
+    # ---- re-acquisition of a lost object ----
+    def reacquire(self, centres=None, segmenter=None, n=(1, 1, 8), span=(0.0, 0.0, 2.0 * np.pi), base_rpy=None,
+                  inlier_distance=0.02, accept_ratio=0.5, apply=True):
+        """scores every centre x every orientation of the lattice (n = steps of roll, pitch, yaw over `span` around
+        base_rpy; None: the angles of the current trans) against the current input cloud and returns the best candidate as
+        a ReacquireResult.  centres: (k, 3) positions; or segmenter: a ModelSegmenter that has been applied -- the centroids
+        of its clusters, formed on the device.  apply=True and an accepted candidate: setTrans(result.trans) +
+        resetTracking().  Synchronous"""
+        if (centres is None) == (segmenter is None):
+            raise PftError(1, "reacquire: give either centres or a segmenter")
+        self._ensure()
+        cfg = _lib.ReacquireConfig()
+        self._L.pft_reacquire_config_default(C.byref(cfg))
+        cfg.n_roll, cfg.n_pitch, cfg.n_yaw = (int(v) for v in n)
+        if base_rpy is None:
+            st = np.zeros(1, PARTICLE_DTYPE)
+            self._L.pft_to_state(_ptr(self._trans), _ptr(st))
+            base_rpy = (st[0]["roll"], st[0]["pitch"], st[0]["yaw"])
+        for a in range(3):
+            cfg.base_rpy[a] = float(base_rpy[a])
+            cfg.span_rpy[a] = float(span[a])
+        cfg.inlier_distance = float(inlier_distance)
+        cfg.accept_ratio = float(accept_ratio)
+        cfg.apply = 1 if apply else 0
+        r = _lib.ReacquireResultStruct()
+        if segmenter is not None:
+            if segmenter._h is None:
+                raise PftError(7, "reacquire: the segmenter has not been applied yet")
+            self._check(self._L.pft_reacquire_from_segmenter(self._h, segmenter._h, C.byref(cfg), C.byref(r)))
+        else:
+            c = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+            self._check(self._L.pft_reacquire(self._h, _ptr(c), len(c), C.byref(cfg), C.byref(r)))
+        res = ReacquireResult.from_struct(r)
+        self._rq_centres = res.n_centres  # getReacquireScores sizes its centre array by it
+        if res.applied:
+            self._trans = res.trans  # what a later close() and re-creation hands to the new handle
+        return res
+
+    def getReacquireScores(self):
+        """the candidates and scores of the last reacquire(), in candidate order: dict(candidates (PARTICLE_DTYPE), mats
+        (K, 3, 4), n_inliers, n_matched (uint32), coherence, sum_sq_dist, inlier_sq_dist (float64), centres (k, 3))"""
+        if self._h is None:
+            raise PftError(7, "getReacquireScores before the first reacquire()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_reacquire_scores(self._h, None, None, None, None, None, None, None, None, 0, C.byref(n)))
+        K = n.value
+        out = dict(candidates=np.zeros(K, PARTICLE_DTYPE), mats=np.zeros((K, 3, 4), np.float32),
+                   n_inliers=np.zeros(K, np.uint32), n_matched=np.zeros(K, np.uint32), coherence=np.zeros(K, np.float64),
+                   sum_sq_dist=np.zeros(K, np.float64), inlier_sq_dist=np.zeros(K, np.float64))
+        nc = self._rq_centres
+        centres = np.zeros((max(nc, 1), 3), np.float32)
+        self._check(self._L.pft_get_reacquire_scores(
+            self._h, _ptr(out["candidates"]), _ptr(out["mats"]), _ptr(out["n_inliers"]), _ptr(out["n_matched"]),
+            _ptr(out["coherence"]), _ptr(out["sum_sq_dist"]), _ptr(out["inlier_sq_dist"]), _ptr(centres), K, C.byref(n)))
+        out["centres"] = centres[:nc].copy()
+        return out
 
     # ---- test hooks (stage-level parity against the oracle) ----
     def setParticles(self, p):
