@@ -332,6 +332,64 @@ int pft_get_reacquire_scores(pft_tracker* t, pft_particle* cand, float* mats12, 
                              double* coherence, double* sum_sq_dist, double* inlier_sq_dist, float* centres_xyz,
                              size_t cap, size_t* n);
 
+/* ---- population statistics: pose covariance, effective sample size, the spread rule ----
+ * What neither the result pose nor its match statistics say: how sure the filter is.  Opt-in, enqueued on the handle's
+ * stream after pft_compute, never synchronises; it reduces the population pft_get_particles would return (after the last
+ * weight() / update() of the frame, weights normalised).  pft_compute itself is untouched.
+ * Particles i = 0 .. n-1 (n = particle_num, or the device-side active count of a KLD handle; slots beyond it are not read),
+ * w_i the float weight, p_ik the six float pose components x, y, z, roll, pitch, yaw, r the representative state in force
+ * (what pft_get_result returns), the pivot that keeps the second moments from cancelling:  d_ik = (double)p_ik - (double)r_k.
+ * All sums are adjacent-pair trees in double over the particle index 0 .. n-1 padded with +0.0 to a power of two (the tree
+ * of update() in the default order), built from aligned subtrees only: the bits depend neither on the workgroup size nor
+ * on the grid.  Unfused, as the library is built:
+ *   sum_w   sum of (double)w_i               sum_w2  sum of (double)w_i * (double)w_i
+ *   s[k]    sum of (double)w_i * d_ik        S[kl]   sum of ((double)w_i * d_ik) * d_il for k <= l, row by row (21 values)
+ *   n, n_zero (particles with w_i == 0: PCL's "no correspondence"), w_max and i_max (the lowest index on a tie)
+ * One lane then derives, in plain double arithmetic (+ - x / only):
+ *   n_eff    sum_w2 > 0 ? (sum_w * sum_w) / sum_w2 : 0
+ *   mean[k]  (double)r_k + m_k with m_k = s[k] / sum_w
+ *   cov[kl]  S[kl] / sum_w - m_k * m_l, symmetric 6 x 6, row-major, all 36 stored
+ *   (sum_w == 0: every derived field is 0 and evaluated is still 1)
+ *   pos_sigma, pos_axes, solve_info   the 3 x 3 block cov[0..2][0..2] rounded to float through the eigen solver of the object
+ *            report: pos_sigma[a] = sqrtf(max(eigenvalue_a, 0)), ascending; pos_axes its eigenvectors as columns (row-major,
+ *            col 2 = col 0 x col 1); solve_info its return value (1: no convergence)
+ *   rpy_sigma[a]  sqrt(max(cov[3+a][3+a], 0)) in double
+ * Euler angles are treated linearly, as PCL's update() treats them: particles are never wrapped, so a population does not
+ * straddle +-pi.  The summation order is the tree on every handle, PFT_SUM_PCL handles included: PCL has no such statistic
+ * to follow.  `mean` is formed in double and is not claimed to equal pft_get_result.
+ * The spread rule mirrors the lost rule:
+ *   uncertain  (double)pos_sigma[2] > max_pos_sigma || n_eff < min_n_eff
+ *   streak     uncertain ? streak + 1 : 0;   flagged  streak >= after;   calls  pft_spread launches so far
+ * The streak is cleared by pft_reset_tracking and pft_set_reference.
+ *   evaluated  1, or 0 when the last iteration of the last pft_compute raised a device-side failure: every other field
+ *              except calls then keeps its last value, the streak included.  An iteration skipped by the change detector is
+ *              evaluated: its weights were renormalised, the population is valid. */
+typedef struct pft_population_stats {
+  double   sum_w, sum_w2;
+  double   s[6];
+  double   S[21];
+  double   n_eff;
+  double   mean[6];
+  double   cov[36];
+  double   rpy_sigma[3];
+  float    pos_sigma[3];
+  float    pos_axes[9];
+  float    w_max;
+  uint32_t n, n_zero, i_max, solve_info;
+  uint32_t evaluated, uncertain, streak, flagged, calls;
+} pft_population_stats;                          /* 688 B */
+
+/* max_pos_sigma >= 0 (default +inf), min_n_eff >= 0 (default 0), after >= 1 (default 1): the defaults never fire.  Read by
+ * the pft_spread calls that follow.  PFT_ERR_INVALID_ARG for a NaN or negative threshold, or after < 1 */
+int pft_set_spread_threshold(pft_tracker* t, double max_pos_sigma, double min_n_eff, int after);
+int pft_get_spread_threshold(pft_tracker* t, double* max_pos_sigma, double* min_n_eff, int* after);
+/* enqueues the statistics of the population on the device (never synchronises).  Allowed after pft_set_particles, on KLD and
+ * exact-NN handles, and with PFT_GRAPH=1 (launched outside the captured frame).  PFT_ERR_INVALID_ARG with a text: a sharded
+ * handle (world_size > 1).  PFT_ERR_STATE: before a population exists (the first pft_compute or pft_set_particles) */
+int pft_spread(pft_tracker* t);
+/* synchronises and copies the last statistics out; device-side failures are reported as by pft_get_result */
+int pft_get_spread(pft_tracker* t, pft_population_stats* out);
+
 /* ---- multi-GPU phase API (one handle per rank; the collectives between the phases are issued by
  *      the host layer on the same stream, see pcl_tracking_amd/dist.py and DESIGN.md) ----
  * The host layer owns three device buffers and binds them once:

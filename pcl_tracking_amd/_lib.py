@@ -61,6 +61,18 @@ class MatchStatsStruct(C.Structure):
     ]
 
 
+class PopulationStatsStruct(C.Structure):
+    """pft_population_stats (include/pft.h): the population's sums, covariance and ellipsoid, the spread rule's state, 688 bytes"""
+    _fields_ = [
+        ("sum_w", C.c_double), ("sum_w2", C.c_double), ("s", C.c_double * 6), ("S", C.c_double * 21),
+        ("n_eff", C.c_double), ("mean", C.c_double * 6), ("cov", C.c_double * 36), ("rpy_sigma", C.c_double * 3),
+        ("pos_sigma", C.c_float * 3), ("pos_axes", C.c_float * 9), ("w_max", C.c_float),
+        ("n", C.c_uint32), ("n_zero", C.c_uint32), ("i_max", C.c_uint32), ("solve_info", C.c_uint32),
+        ("evaluated", C.c_uint32), ("uncertain", C.c_uint32), ("streak", C.c_uint32), ("flagged", C.c_uint32),
+        ("calls", C.c_uint32),
+    ]
+
+
 class ReacquireConfig(C.Structure):
     """pft_reacquire_config (include/pft.h): the orientation lattice, the inlier gate and the acceptance rule, 64 bytes"""
     _fields_ = [
@@ -198,6 +210,10 @@ SYMBOLS = [
     ("pft_get_match", C.c_int, [_vp, _P(MatchStatsStruct)]),
     ("pft_get_match_pairs", C.c_int, [_vp, _vp, _vp, _sz, _P(_sz)]),
     ("pft_reset_tracking", C.c_int, [_vp]),
+    ("pft_set_spread_threshold", C.c_int, [_vp, _f64, _f64, C.c_int]),
+    ("pft_get_spread_threshold", C.c_int, [_vp, _P(_f64), _P(_f64), _P(C.c_int)]),
+    ("pft_spread", C.c_int, [_vp]),
+    ("pft_get_spread", C.c_int, [_vp, _P(PopulationStatsStruct)]),
     ("pft_reacquire_config_default", None, [_P(ReacquireConfig)]),
     ("pft_reacquire", C.c_int, [_vp, _vp, _sz, _P(ReacquireConfig), _P(ReacquireResultStruct)]),
     ("pft_reacquire_from_segmenter", C.c_int, [_vp, _vp, _P(ReacquireConfig), _P(ReacquireResultStruct)]),

@@ -162,6 +162,16 @@ struct pft_tracker {
   double match_min_ratio = 0.0;
   int match_lost_after = 1;
 
+  // population statistics (pft_spread): the result block with the spread rule's state, and the per-block roots of the
+  // two-launch reduction (sized once for the handle's particle capacity)
+  pft_population_stats* d_spread = nullptr;
+  double* d_spread_part = nullptr;
+  uint32_t *d_spread_zero = nullptr, *d_spread_imax = nullptr;
+  float* d_spread_wmax = nullptr;
+  bool spread_issued = false;    // a pft_spread has been enqueued: d_spread holds (or will hold) its result
+  double spread_max_pos_sigma = INFINITY, spread_min_n_eff = 0.0;
+  int spread_after = 1;
+
   // re-acquisition (pft_reacquire): buffers of the feature's own, sized for the largest K seen (never the handle's
   // particle_num-sized ones): candidates, their matrices, the scores, the partial boxes of k_aabb, the result block
   pft_particle* d_rq_part = nullptr;
@@ -775,6 +785,7 @@ extern "C" void pft_destroy(pft_tracker* t) {
   cd_free(t->cd); cd_free(t->cd_dbg);
   dfree(t->d_rep_pts); dfree(t->d_rep_tracked); dfree(t->d_report);
   dfree(t->d_match); dfree(t->d_match_idx); dfree(t->d_match_d2);
+  dfree(t->d_spread); dfree(t->d_spread_part); dfree(t->d_spread_zero); dfree(t->d_spread_imax); dfree(t->d_spread_wmax);
   dfree(t->d_rq_part); dfree(t->d_rq_mats); dfree(t->rq_sc.n_inliers); dfree(t->rq_sc.n_matched); dfree(t->rq_sc.coherence);
   dfree(t->rq_sc.sum_sq_dist); dfree(t->rq_sc.inlier_sq_dist); dfree(t->d_rq_centres); dfree(t->d_rq_first);
   dfree(t->d_rq_count); dfree(t->d_rq_bbox_part); dfree(t->d_rq_result);
@@ -791,10 +802,10 @@ extern "C" int pft_synchronize(pft_tracker* t) {
   return check_device_error(t);
 }
 
-// the lost rule's state {below, streak, lost} back to zero, in stream order
+// the lost rule's state {below, streak, lost} and the spread rule's {uncertain, streak, flagged} back to zero, in stream order
 static int match_clear_streak(pft_tracker* t) {
-  if (!t->d_match) return PFT_OK;
-  HIPCHK(t, hipMemsetAsync(&t->d_match->below, 0, 3 * sizeof(uint32_t), t->stream));
+  if (t->d_match) HIPCHK(t, hipMemsetAsync(&t->d_match->below, 0, 3 * sizeof(uint32_t), t->stream));
+  if (t->d_spread) HIPCHK(t, hipMemsetAsync(&t->d_spread->uncertain, 0, 3 * sizeof(uint32_t), t->stream));
   return PFT_OK;
 }
 
@@ -2462,6 +2473,67 @@ extern "C" int pft_reset_tracking(pft_tracker* t) {
   t->tree_of_compute = false;
   if (t->h_stat) t->h_stat[0] = t->h_stat[1] = 0;
   return match_clear_streak(t);
+}
+
+// ---- population statistics and the spread rule (pft_spread.hip) ----
+extern "C" int pft_set_spread_threshold(pft_tracker* t, double max_pos_sigma, double min_n_eff, int after) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!(max_pos_sigma >= 0.0) || !(min_n_eff >= 0.0) || after < 1) {
+    t->err = "pft_set_spread_threshold: max_pos_sigma and min_n_eff must be numbers >= 0 and after must be at least 1";
+    return PFT_ERR_INVALID_ARG;
+  }
+  t->spread_max_pos_sigma = max_pos_sigma;
+  t->spread_min_n_eff = min_n_eff;
+  t->spread_after = after;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_spread_threshold(pft_tracker* t, double* max_pos_sigma, double* min_n_eff, int* after) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (max_pos_sigma) *max_pos_sigma = t->spread_max_pos_sigma;
+  if (min_n_eff) *min_n_eff = t->spread_min_n_eff;
+  if (after) *after = t->spread_after;
+  return PFT_OK;
+}
+
+extern "C" int pft_spread(pft_tracker* t) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size != 1) {
+    t->err = "the population statistics are not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (!t->initialized) {
+    t->err = "pft_spread before the first pft_compute: there is no population yet";
+    return PFT_ERR_STATE;
+  }
+  hipSetDevice(t->cfg.device_id);
+  const uint32_t n_max = t->prm.kld ? t->Pcap : t->prm.P_total;  // (a KLD handle's count is read on the device)
+  if (!t->d_spread) {
+    const size_t blocks = pftk_spread_blocks(n_max);
+    HIPCHK(t, dalloc(&t->d_spread_part, (size_t)29 * blocks));
+    HIPCHK(t, dalloc(&t->d_spread_zero, blocks));
+    HIPCHK(t, dalloc(&t->d_spread_wmax, blocks));
+    HIPCHK(t, dalloc(&t->d_spread_imax, blocks));
+    HIPCHK(t, dalloc(&t->d_spread, 1));
+    HIPCHK(t, hipMemsetAsync(t->d_spread, 0, sizeof(pft_population_stats), t->stream));
+  }
+  sync_dev(t);
+  pftk_spread(t->stream, t->dev, n_max, t->d_spread_part, t->d_spread_zero, t->d_spread_wmax, t->d_spread_imax,
+              t->spread_max_pos_sigma, t->spread_min_n_eff, (uint32_t)t->spread_after, t->d_spread);
+  HIPCHK(t, hipGetLastError());
+  t->spread_issued = true;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_spread(pft_tracker* t, pft_population_stats* out) {
+  if (!t || !out) return PFT_ERR_INVALID_ARG;
+  if (!t->spread_issued) {
+    t->err = "pft_get_spread before the first pft_spread";
+    return PFT_ERR_STATE;
+  }
+  HIPCHK(t, hipMemcpyAsync(out, t->d_spread, sizeof(pft_population_stats), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  return check_device_error(t);
 }
 
 // ---- re-acquisition of a lost object (pft_reacquire.hip) ----

@@ -336,6 +336,13 @@ void pftk_report(hipStream_t s, const pft_point_xyzrgba* pts, uint32_t n, const 
 // (d.gate: the change detector's gate word or null), writes the statistics, the lost rule's state and the pairs
 void pftk_match(hipStream_t s, const PftParams& p, const PftDev& d, double min_ratio, uint32_t lost_after,
                 pft_match_stats* out, int32_t* input_idx, float* sq_dist);
+// population statistics (pft_spread.hip): two launches over d.part_all[0 .. n) -- n = n_max, or a KLD handle's device-side
+// count (d.p_active), never above n_max -- around d.hdr->rep.  part [29][blocks], part_zero / part_wmax / part_imax [blocks]
+// with blocks = pftk_spread_blocks(n_max): the per-block roots, owned by the feature.  Writes the result block and the
+// spread rule's state; a failed last iteration (PftHeader::error) only clears `evaluated`
+uint32_t pftk_spread_blocks(uint32_t n_max);
+void pftk_spread(hipStream_t s, const PftDev& d, uint32_t n_max, double* part, uint32_t* part_zero, float* part_wmax,
+                 uint32_t* part_imax, double max_pos_sigma, double min_n_eff, uint32_t after, pft_population_stats* out);
 // re-acquisition (pft_reacquire.hip): the orientation lattice, the per-candidate score arrays (K each, owned by the feature)
 struct PftRqLattice {
   uint32_t n[3];             // roll, pitch, yaw steps (>= 1)

@@ -5,7 +5,7 @@
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
 //                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
-//                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]]
+//                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -34,6 +34,10 @@
 // is restarted at the best candidate if that one has at least accept_ratio of the model's points within inlier_distance,
 // and the centre it took is dropped for the others.  One `reacquire obj <j>: centre <c> candidate <k> inliers <n>/<M>
 // accepted <0|1>` line per lost object; when nothing is accepted, --reset-on-loss applies if given.
+// --spread[=max_pos_sigma[,min_n_eff[,after]]] enqueues the population statistics behind every compute (pft_spread, still
+// before any result is read) and prints one `spread obj <j>: n_eff ... zero ... pos_sigma ... rpy_sigma ... flagged <0|1>` line
+// per object and frame; the pose is flagged after `after` frames in a row whose largest position sigma exceeded max_pos_sigma
+// or whose effective sample size fell below min_n_eff (the defaults inf,0,1 never flag).
 #include <cstdlib>
 
 #include "segment_options.hpp"
@@ -87,6 +91,21 @@ int main(int argc, char** argv) {
       }
     }
     else if (!std::strcmp(argv[i], "--reset-on-loss")) opt.reset_on_loss = true;
+    else if (!std::strncmp(argv[i], "--spread", 8) && (argv[i][8] == 0 || argv[i][8] == '=')) {
+      opt.spread = true;  // --spread[=max_pos_sigma[,min_n_eff[,after]]]; the defaults inf,0,1 never flag
+      if (argv[i][8] == '=') {
+        double sigma = opt.spread_max_pos_sigma, n_eff = opt.spread_min_n_eff;
+        int after = opt.spread_after;
+        const int got = std::sscanf(argv[i] + 9, "%lf,%lf,%d", &sigma, &n_eff, &after);
+        if (got < 1 || !(sigma >= 0.0) || !(n_eff >= 0.0) || after < 1) {
+          std::fprintf(stderr, "--spread=max_pos_sigma[,min_n_eff[,after]] with max_pos_sigma >= 0, min_n_eff >= 0 and after >= 1\n");
+          return 2;
+        }
+        opt.spread_max_pos_sigma = sigma;
+        opt.spread_min_n_eff = n_eff;
+        opt.spread_after = after;
+      }
+    }
     else if (!std::strncmp(argv[i], "--reacquire", 11) && (argv[i][11] == 0 || argv[i][11] == '=')) {
       opt.reacquire = true;  // --reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]; the defaults 8,0.5,0.02
       if (argv[i][11] == '=') {
@@ -113,7 +132,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -187,10 +206,12 @@ int main(int argc, char** argv) {
       }
       if (opt.device_report) kv.second->computeReport();
       if (opt.match) kv.second->computeMatch();
+      if (opt.spread) kv.second->computeSpread();
     }
     std::vector<int> lost;  // --reacquire: the objects the match reported lost in this frame
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
+      if (opt.spread) v.reportSpread(kv.first);
       if (opt.match && v.reportMatch(f + 1, kv.first, !opt.reacquire) && opt.reacquire) lost.push_back(kv.first);
       if (opt.device_report) {
         const pft_object_report rep = kv.second->getReport();

@@ -12,6 +12,8 @@
 //   --device-report      the same on the device (pft_report), with viz_cb's principal-axis box       :432-466
 //   --match              the match statistics of every result (pft_match) and the lost rule that makes the
 //                        reference's "Object not recognized" handler fire; --reset-on-loss: resetTracking() then  :692-696
+//   --spread             the population statistics behind every result (pft_spread): effective sample size, position
+//                        ellipsoid, angle sigmas and the spread rule
 //   --reacquire          a lost object is looked for among the cluster centroids of a segmentation of the frame
 //                        (reacquire) and restarted where it is found
 #pragma once
@@ -55,6 +57,10 @@ struct Options {
   double match_min_ratio = 0.0;         // lost after match_lost_after frames in a row below this matched share
   int match_lost_after = 1;
   bool reset_on_loss = false;           // resetTracking() on a lost object
+  bool spread = false;                  // population statistics of every frame: setSpreadThreshold / computeSpread / getSpread
+  double spread_max_pos_sigma = HUGE_VAL;  // uncertain after spread_after calls in a row above this position sigma
+  double spread_min_n_eff = 0.0;        // or below this effective sample size
+  int spread_after = 1;
   bool reacquire = false;               // a lost object is looked for among the clusters of the frame (pft_reacquire)
   int rq_n_yaw = 8;                     // yaw steps over the full circle around the object's initial orientation
   double rq_accept_ratio = 0.5;         // inliers / model points a candidate needs
@@ -155,6 +161,7 @@ class TrackingApp {
       coherence->setMaximumDistance(0.1);
       tr->setCloudCoherence(coherence);
       if (opt_.match) tr->setMatchThreshold(opt_.match_min_ratio, opt_.match_lost_after);
+      if (opt_.spread) tr->setSpreadThreshold(opt_.spread_max_pos_sigma, opt_.spread_min_n_eff, opt_.spread_after);
       configure(*tr, obj_id);
       tracker_dict[obj_id] = tr;
     }
@@ -247,6 +254,16 @@ class TrackingApp {
     std::fprintf(stderr, "frame %zu object %d: Object not recognized\n", frame, obj_id);
     if (reset && opt_.reset_on_loss) tr.resetTracking();
     return true;
+  }
+
+  // the spread hook of one object and frame, after its computeSpread(): prints the `spread` line (every value round-trips)
+  void reportSpread(int obj_id) {
+    const pft_population_stats p = tracker_dict[obj_id]->getSpread();
+    std::printf("spread obj %d: n_eff %.17g n %u zero %u w_max %.9g pos_sigma %.9g %.9g %.9g rpy_sigma %.17g %.17g %.17g "
+                "evaluated %u uncertain %u streak %u flagged %u\n",
+                obj_id, p.n_eff, p.n, p.n_zero, (double)p.w_max, (double)p.pos_sigma[0], (double)p.pos_sigma[1],
+                (double)p.pos_sigma[2], p.rpy_sigma[0], p.rpy_sigma[1], p.rpy_sigma[2], p.evaluated, p.uncertain, p.streak,
+                p.flagged);
   }
 
   // --reacquire: the objects `lost` in this frame (ascending ids) against the clusters of `seg`, a segmentation of the frame.

@@ -14,6 +14,7 @@
 // namespace pft so the header can sit next to a real PCL; on a machine that has PCL, the two lines of
 // INTEGRATION.md switch auto_tracking.cpp over.  All compute happens in the HIP library.
 #pragma once
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -419,6 +420,34 @@ class ParticleFilterTracker {
     if (handle_) check(pft_reset_tracking(handle_), "resetTracking");
   }
 
+  // ---- population statistics and the spread rule (pft.h, pft_spread) ----
+  // uncertain after `after` evaluated computeSpread() calls in a row whose largest position sigma exceeded max_pos_sigma or
+  // whose effective sample size fell below min_n_eff; the defaults never fire
+  int setSpreadThreshold(double max_pos_sigma, double min_n_eff = 0.0, int after = 1) {
+    if (!(max_pos_sigma >= 0.0) || !(min_n_eff >= 0.0) || after < 1) return check(PFT_ERR_INVALID_ARG, "setSpreadThreshold");
+    if (handle_) {
+      const int st = check(pft_set_spread_threshold(handle_, max_pos_sigma, min_n_eff, after), "setSpreadThreshold");
+      if (st != PFT_OK) return st;
+    }
+    spread_max_pos_sigma_ = max_pos_sigma;
+    spread_min_n_eff_ = min_n_eff;
+    spread_after_ = after;
+    return PFT_OK;
+  }
+  // enqueues the statistics of the population the last compute() left on the device; nothing waits
+  int computeSpread() {
+    if (!handle_) return check(PFT_ERR_STATE, "computeSpread");
+    return check(pft_spread(handle_), "computeSpread");
+  }
+  // waits for the last computeSpread()
+  pft_population_stats getSpread() const {
+    pft_population_stats p;
+    std::memset(&p, 0, sizeof(p));
+    if (handle_) check(pft_get_spread(handle_, &p), "getSpread");
+    return p;
+  }
+  bool isUncertain() const { return handle_ && getSpread().flagged != 0; }
+
   // ---- re-acquisition of a lost object (pft.h, pft_reacquire) ----
   // every centre (n_centres x 3 floats) with every orientation of cfg's lattice is scored against the input cloud the handle
   // holds -- the one of the last compute() --; with cfg.apply and an accepted candidate the tracker is restarted at it:
@@ -529,6 +558,8 @@ class ParticleFilterTracker {
     if (use_cd_ || cd_interval_ != 10 || cd_min_points_ != 10 || cd_resolution_ != 0.01) forwardChangeDetector();
     if (match_min_ratio_ != 0.0 || match_lost_after_ != 1)
       check(pft_set_match_threshold(handle_, match_min_ratio_, match_lost_after_), "setMatchThreshold");
+    if (spread_max_pos_sigma_ != HUGE_VAL || spread_min_n_eff_ != 0.0 || spread_after_ != 1)
+      check(pft_set_spread_threshold(handle_, spread_max_pos_sigma_, spread_min_n_eff_, spread_after_), "setSpreadThreshold");
     if (ref_) check(pft_set_reference(handle_, ref_->points.data(), ref_->points.size()), "setReferenceCloud");
     if (report_cloud_)
       check(pft_set_report_cloud(handle_, report_cloud_->points.data(), report_cloud_->points.size()), "setReportCloud");
@@ -550,6 +581,8 @@ class ParticleFilterTracker {
   double cd_resolution_ = 0.01;
   double match_min_ratio_ = 0.0;  // setMatchThreshold
   int match_lost_after_ = 1;
+  double spread_max_pos_sigma_ = HUGE_VAL, spread_min_n_eff_ = 0.0;  // setSpreadThreshold
+  int spread_after_ = 1;
 };
 
 // the class the reference actually news (auto_tracking.cpp:203-204); the thread count is the OpenMP team

@@ -93,6 +93,41 @@ class MatchStats:
 
 
 @dataclass
+class PopulationStats:
+    """pft_population_stats: how sure the filter is about its pose"""
+    sum_w: float           # the 29 tree sums in double: weights, squared weights,
+    sum_w2: float
+    s: np.ndarray          # 6, weighted offsets from the representative state,
+    S: np.ndarray          # 21, weighted products of offsets (k <= l, row by row)
+    n_eff: float           # effective sample size (sum_w)^2 / sum_w2
+    mean: np.ndarray       # 6 float64: x, y, z, roll, pitch, yaw
+    cov: np.ndarray        # 6x6 float64, symmetric
+    rpy_sigma: np.ndarray  # 3 float64
+    pos_sigma: np.ndarray  # 3 float32, ascending: the semi-axes of the position ellipsoid
+    pos_axes: np.ndarray   # 3x3 float32, its axes as columns
+    w_max: float
+    n: int                 # particles reduced
+    n_zero: int            # particles with weight 0 (no correspondence)
+    i_max: int             # the first particle of weight w_max
+    solve_info: int        # 0, or 1: the eigen solver did not converge
+    evaluated: bool        # False: the last iteration failed on the device; the other fields are the last evaluated call's
+    uncertain: bool        # pos_sigma[2] > max_pos_sigma or n_eff < min_n_eff
+    streak: int            # evaluated calls in a row that were uncertain
+    flagged: bool          # streak >= after
+    calls: int
+
+    @classmethod
+    def from_struct(cls, r):
+        return cls(sum_w=float(r.sum_w), sum_w2=float(r.sum_w2), s=np.array(r.s, dtype=np.float64),
+                   S=np.array(r.S, dtype=np.float64), n_eff=float(r.n_eff), mean=np.array(r.mean, dtype=np.float64),
+                   cov=np.array(r.cov, dtype=np.float64).reshape(6, 6), rpy_sigma=np.array(r.rpy_sigma, dtype=np.float64),
+                   pos_sigma=np.array(r.pos_sigma, dtype=np.float32),
+                   pos_axes=np.array(r.pos_axes, dtype=np.float32).reshape(3, 3), w_max=float(r.w_max), n=int(r.n),
+                   n_zero=int(r.n_zero), i_max=int(r.i_max), solve_info=int(r.solve_info), evaluated=bool(r.evaluated),
+                   uncertain=bool(r.uncertain), streak=int(r.streak), flagged=bool(r.flagged), calls=int(r.calls))
+
+
+@dataclass
 class ReacquireResult:
     """pft_reacquire_result: the candidate a re-acquisition call selected"""
     n_centres: int
@@ -209,6 +244,7 @@ class ParticleFilterTracker:
         # ParticleFilterTracker's change detector: use, interval, min points, resolution (PCL's constructor defaults)
         self._cd = [False, 10, 10, 0.01]
         self._match_thr = (0.0, 1)  # pft_set_match_threshold: min_ratio, lost_after
+        self._spread_thr = (float("inf"), 0.0, 1)  # pft_set_spread_threshold: max_pos_sigma, min_n_eff, after
         self._rq_centres = 0  # centres of the last reacquire()
         self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
@@ -346,6 +382,8 @@ class ParticleFilterTracker:
                 self._forward_change_detector()
             if self._match_thr != (0.0, 1):
                 self._check(self._L.pft_set_match_threshold(self._h, *self._match_thr))
+            if self._spread_thr != (float("inf"), 0.0, 1):
+                self._check(self._L.pft_set_spread_threshold(self._h, *self._spread_thr))
             if self._ref is not None:
                 self._check(self._L.pft_set_reference(self._h, _ptr(self._ref), len(self._ref)))
             if self._report_cloud is not None:
@@ -522,6 +560,39 @@ class ParticleFilterTracker:
         in force then; the change detector keeps its state, the lost rule's streak is cleared"""
         if self._h is not None:
             self._check(self._L.pft_reset_tracking(self._h))
+
+    # ---- population statistics and the spread rule ----
+    def setSpreadThreshold(self, max_pos_sigma=float("inf"), min_n_eff=0.0, after=1):
+        """the pose counts as uncertain after `after` evaluated computeSpread() calls in a row whose largest position sigma
+        exceeded max_pos_sigma (metres) or whose effective sample size fell below min_n_eff; (inf, 0, 1), the default,
+        never fires.  Callable at any time"""
+        thr = (float(max_pos_sigma), float(min_n_eff), int(after))
+        if not (thr[0] >= 0.0) or not (thr[1] >= 0.0) or thr[2] < 1:
+            raise PftError(1, "setSpreadThreshold: max_pos_sigma >= 0, min_n_eff >= 0, after >= 1")
+        if self._h is not None:
+            self._check(self._L.pft_set_spread_threshold(self._h, thr[0], thr[1], thr[2]))
+        self._spread_thr = thr
+
+    def getSpreadThreshold(self):
+        return self._spread_thr
+
+    def computeSpread(self):
+        """enqueues the statistics of the population compute() left on the device; nothing waits"""
+        if self._h is None:
+            raise PftError(7, "computeSpread before the first compute()")
+        self._check(self._L.pft_spread(self._h))
+
+    def getSpread(self):
+        """waits for the last computeSpread(); returns PopulationStats"""
+        if self._h is None:
+            raise PftError(7, "getSpread before the first compute()")
+        r = _lib.PopulationStatsStruct()
+        self._check(self._L.pft_get_spread(self._h, C.byref(r)))
+        return PopulationStats.from_struct(r)
+
+    def isUncertain(self):
+        """the flag of the spread rule after the last computeSpread() (waits for it)"""
+        return self.getSpread().flagged
 
     # ---- re-acquisition of a lost object ----
     def reacquire(self, centres=None, segmenter=None, n=(1, 1, 8), span=(0.0, 0.0, 2.0 * np.pi), base_rpy=None,
