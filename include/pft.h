@@ -332,6 +332,86 @@ int pft_get_reacquire_scores(pft_tracker* t, pft_particle* cand, float* mats12, 
                              double* coherence, double* sum_sq_dist, double* inlier_sq_dist, float* centres_xyz,
                              size_t cap, size_t* n);
 
+/* ---- refinement of a pose against the frame: iterated closest-point fit on the device ----
+ * Point-to-point ICP from a start pose, against the handle's current input cloud, with the search of pft_match as the
+ * pairing.  Opt-in and synchronous: all iterations are enqueued at once, the stop decision is taken on the device, the
+ * host waits once.  Quaternions are {w, x, y, z}; all arithmetic is IEEE, unfused, left to right.
+ *   state     a unit quaternion Q and a translation t, both double.  The start is a row-major 3x4 float matrix: Q by the
+ *             Shoemake branches of Quaternion(Matrix3) evaluated in double, then normalised; t its last column.  NULL: the
+ *             matrix of the last result pose, exactly the T pft_match stores (only after a pft_compute).
+ *   T         pass 0 runs with the start matrix itself; after a solve T = ((float)R(Q), (float)t), R(Q) the usual
+ *             polynomial (R00 = 1 - 2 (yy + zz), R01 = 2 (xy - wz), ...).  A solve whose step is exactly zero (dq the
+ *             identity and t_new == c) leaves Q, t and T as they are.
+ *   crop, tree  once per call, by the handle's builders as pft_reacquire drives them: the box of the reference cloud under
+ *             the eight copies of the start shifted by (+-(float)margin, +-(float)margin, +-(float)margin); reported in `bbox`
+ *   one pass, over the reference points p_j at positions 0 .. M-1 of the stored (Morton) order:
+ *       q = T p_j;  (partner, d2) = the search of pft_match;  pair_j = (double)d2 < pair_distance^2,
+ *       inlier_j = (double)d2 < inlier_distance^2;  pivot c = (double) of T's translation;  a = (double)q - c,
+ *       b = (double)partner - c;  n_pairs, n_inliers integers;  17 sums, each the adjacent-pair tree in double over the
+ *       positions padded with +0.0 (pft_match's tree; the terms are signed, a step is taken only inside the padded size):
+ *       sums[0..2] = sum pair a_r,  [3..5] = sum pair b_r,  [6 + 3 r + c] = sum pair a_r b_c,  [15] = sum pair (double)d2,
+ *       [16] = sum inlier (double)d2
+ *   solve     am = A / n, bm = B / n, S = H - A B^T / n (S_rc = H_rc - A_r B_c / n), S divided by its largest absolute entry
+ *             (1 if zero); Horn's symmetric 4x4 matrix of S; cyclic Jacobi sweeps over (0,1),(0,2),(0,3),(1,2),(1,3),(2,3),
+ *             a pair whose off-diagonal entry is exactly 0 skipped, theta = (a_qq - a_pp) / (2 a_pq),
+ *             t = +-1 / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c, until every off-diagonal entry is 0
+ *             or 16 sweeps; dq = the normalised eigenvector of the largest diagonal entry (the first on ties) with w >= 0;
+ *             Q <- normalise(dq (x) Q), t <- c + (bm - R(dq) am);  step_t2 = |t_new - c|^2, step_r2 = 4 (dq_x^2 + dq_y^2 +
+ *             dq_z^2).  The quaternion form never returns a reflection
+ *   loop      pass k evaluates T_k (k = 0: `before`).  n_pairs < min_pairs: TOO_FEW_PAIRS, nothing is solved, T is kept and
+ *             this pass is also `after`.  Else solve (iterations = k + 1): CONVERGED when step_t2 < trans_eps^2 and
+ *             step_r2 < rot_eps^2, else MAX_ITERATIONS at k + 1 == max_iterations; then one more pass gives `after`.
+ *             The trace holds iterations + 1 entries, one per pass
+ *   improved  after.n_inliers > before.n_inliers, or equal and after.inlier_sq_dist < before.inlier_sq_dist
+ *   pose      pft_to_state of the final transform (its angles carry that function's float tolerance; `transform` is exact)
+ * With apply != 0 and improved: pft_set_trans(the 4x4 of `transform`) + pft_reset_tracking, and nothing else.  Otherwise the
+ * population, weights, epoch, change detector and streaks are left alone; like pft_reacquire the call rebuilds the handle's
+ * tree, so a pft_match before the next pft_compute returns PFT_ERR_STATE.  Device-side builder failures are reported as by
+ * pft_get_result; nothing is applied then.
+ * PFT_ERR_INVALID_ARG with a text: a sharded handle, an exact-NN handle, a bad configuration value, a non-finite start.
+ * PFT_ERR_STATE: a NULL start without a pft_compute.  PFT_ERR_NO_INPUT / PFT_ERR_NO_REFERENCE as pft_compute. */
+#define PFT_REFINE_MAX_ITERATIONS 64
+#define PFT_REFINE_N_SUMS 17
+enum { PFT_REFINE_CONVERGED = 0, PFT_REFINE_MAX_ITERATIONS_REACHED = 1, PFT_REFINE_TOO_FEW_PAIRS = 2 };
+typedef struct pft_refine_config {
+  int32_t max_iterations;                   /* 1 .. PFT_REFINE_MAX_ITERATIONS; default 16 */
+  int32_t min_pairs;                        /* >= 3; default 3 */
+  double pair_distance;                     /* >= 0; 0 = the handle's max_distance */
+  double inlier_distance;                   /* > 0; default 0.02 */
+  double margin;                            /* >= 0; 0 = pair_distance */
+  double trans_eps, rot_eps;                /* >= 0; defaults 1e-4 m, 1e-3 rad */
+  int32_t apply;                            /* improved: pft_set_trans(final) + pft_reset_tracking; default 0 */
+} pft_refine_config;                        /* 56 B */
+
+typedef struct pft_refine_score {
+  uint32_t n_pairs, n_inliers;
+  double sum_sq_dist, inlier_sq_dist;
+} pft_refine_score;                         /* 24 B */
+
+typedef struct pft_refine_result {
+  uint32_t status, iterations, n_reference, n_crop;
+  double bbox[6];                           /* x_min, x_max, y_min, y_max, z_min, z_max of the crop */
+  float start[12], transform[12];           /* the start and the final T (row-major 3x4) */
+  pft_particle pose;
+  pft_refine_score before, after;
+  uint32_t improved, applied;
+} pft_refine_result;                        /* 248 B */
+
+typedef struct pft_refine_trace_entry {
+  float transform[12];                      /* the T of the pass */
+  uint32_t n_pairs, n_inliers;
+  double sums[PFT_REFINE_N_SUMS];
+  double step_t2, step_r2;                  /* of the solve that followed the pass; 0 when none did */
+} pft_refine_trace_entry;                   /* 208 B */
+
+/* 16, 3, 0, 0.02, 0, 1e-4, 1e-3, apply = 0 */
+void pft_refine_config_default(pft_refine_config* cfg);
+/* start12: row-major 3x4 floats on the host, or NULL for the matrix of the last result pose */
+int pft_refine(pft_tracker* t, const float* start12, const pft_refine_config* cfg, pft_refine_result* out);
+/* the passes of the last pft_refine call; receives min(cap, iterations + 1) entries, *n = iterations + 1.  PFT_ERR_STATE
+ * before the first completed call */
+int pft_get_refine_trace(pft_tracker* t, pft_refine_trace_entry* entries, size_t cap, size_t* n);
+
 /* ---- population statistics: pose covariance, effective sample size, the spread rule ----
  * What neither the result pose nor its match statistics say: how sure the filter is.  Opt-in, enqueued on the handle's
  * stream after pft_compute, never synchronises; it reduces the population pft_get_particles would return (after the last

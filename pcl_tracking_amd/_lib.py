@@ -94,6 +94,40 @@ class ReacquireResultStruct(C.Structure):
 
 
 PFT_REACQUIRE_MAX_CANDIDATES = 65536
+PFT_REFINE_MAX_ITERATIONS = 64
+PFT_REFINE_N_SUMS = 17
+REFINE_STATUS = ("CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS")
+
+
+class RefineConfig(C.Structure):
+    """pft_refine_config (include/pft.h): the loop's limits, the two gates, the crop margin and the stop rule, 56 bytes"""
+    _fields_ = [
+        ("max_iterations", C.c_int32), ("min_pairs", C.c_int32),
+        ("pair_distance", C.c_double), ("inlier_distance", C.c_double), ("margin", C.c_double),
+        ("trans_eps", C.c_double), ("rot_eps", C.c_double), ("apply", C.c_int32),
+    ]
+
+
+class RefineScore(C.Structure):
+    """pft_refine_score: the score of one transform, 24 bytes"""
+    _fields_ = [("n_pairs", C.c_uint32), ("n_inliers", C.c_uint32), ("sum_sq_dist", C.c_double), ("inlier_sq_dist", C.c_double)]
+
+
+class RefineResultStruct(C.Structure):
+    """pft_refine_result (include/pft.h), 248 bytes"""
+    _fields_ = [
+        ("status", C.c_uint32), ("iterations", C.c_uint32), ("n_reference", C.c_uint32), ("n_crop", C.c_uint32),
+        ("bbox", C.c_double * 6), ("start", C.c_float * 12), ("transform", C.c_float * 12), ("pose", C.c_float * 8),
+        ("before", RefineScore), ("after", RefineScore), ("improved", C.c_uint32), ("applied", C.c_uint32),
+    ]
+
+
+class RefineTraceEntry(C.Structure):
+    """pft_refine_trace_entry (include/pft.h): one pass of a refinement, 208 bytes"""
+    _fields_ = [
+        ("transform", C.c_float * 12), ("n_pairs", C.c_uint32), ("n_inliers", C.c_uint32),
+        ("sums", C.c_double * 17), ("step_t2", C.c_double), ("step_r2", C.c_double),
+    ]
 
 
 class FilterConfig(C.Structure):
@@ -218,6 +252,9 @@ SYMBOLS = [
     ("pft_reacquire", C.c_int, [_vp, _vp, _sz, _P(ReacquireConfig), _P(ReacquireResultStruct)]),
     ("pft_reacquire_from_segmenter", C.c_int, [_vp, _vp, _P(ReacquireConfig), _P(ReacquireResultStruct)]),
     ("pft_get_reacquire_scores", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _P(_sz)]),
+    ("pft_refine_config_default", None, [_P(RefineConfig)]),
+    ("pft_refine", C.c_int, [_vp, _vp, _P(RefineConfig), _P(RefineResultStruct)]),
+    ("pft_get_refine_trace", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_kld_normal_quantile", _f64, [_f64]),
     ("pft_kld_bound", _f64, [C.c_int, _f64, _f64]),
     ("pft_profile_enable", C.c_int, [_vp, C.c_int]),

@@ -186,6 +186,11 @@ struct pft_tracker {
   uint32_t rq_n = 0;             // candidates of the last call
   bool rq_valid = false;         // a call has completed: the arrays hold its candidates and scores
   std::vector<float> rq_centres;  // the last call's centres (host copy)
+  // pose refinement (pft_refine): buffers of the feature's own
+  PftRefineDev rf = {};
+  float* d_rf_mats = nullptr;       // the eight shifted copies of the start the crop box is taken over
+  uint32_t rf_n = 0;                // trace entries of the last completed call
+  bool rf_valid = false;
 
   // state
   bool has_ref = false, has_input = false, initialized = false, changed = false;
@@ -789,6 +794,7 @@ extern "C" void pft_destroy(pft_tracker* t) {
   dfree(t->d_rq_part); dfree(t->d_rq_mats); dfree(t->rq_sc.n_inliers); dfree(t->rq_sc.n_matched); dfree(t->rq_sc.coherence);
   dfree(t->rq_sc.sum_sq_dist); dfree(t->rq_sc.inlier_sq_dist); dfree(t->d_rq_centres); dfree(t->d_rq_first);
   dfree(t->d_rq_count); dfree(t->d_rq_bbox_part); dfree(t->d_rq_result);
+  dfree(t->rf.ctl); dfree(t->rf.part); dfree(t->rf.part_n); dfree(t->rf.result); dfree(t->rf.trace); dfree(t->d_rf_mats);
   dfree(t->sv_cd); dfree(t->sv_cd_key[0]); dfree(t->sv_cd_key[1]); dfree(t->sv_cd_cnt[0]); dfree(t->sv_cd_cnt[1]);
   if (t->own_stream && t->stream) hipStreamDestroy(t->stream);
   delete t;
@@ -2766,6 +2772,146 @@ extern "C" int pft_get_reacquire_scores(pft_tracker* t, pft_particle* cand, floa
   if (coherence) HIPCHK(t, hipMemcpyAsync(coherence, t->rq_sc.coherence, c * sizeof(double), k, t->stream));
   if (sum_sq_dist) HIPCHK(t, hipMemcpyAsync(sum_sq_dist, t->rq_sc.sum_sq_dist, c * sizeof(double), k, t->stream));
   if (inlier_sq_dist) HIPCHK(t, hipMemcpyAsync(inlier_sq_dist, t->rq_sc.inlier_sq_dist, c * sizeof(double), k, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  return PFT_OK;
+}
+
+// ---- refinement of a pose against the frame (pft_refine.hip) ----
+extern "C" void pft_refine_config_default(pft_refine_config* c) {
+  if (!c) return;
+  memset(c, 0, sizeof(*c));
+  c->max_iterations = 16;
+  c->min_pairs = 3;
+  c->inlier_distance = 0.02;
+  c->trans_eps = 1e-4;
+  c->rot_eps = 1e-3;
+}
+
+static int rf_reserve(pft_tracker* t, uint32_t M) {
+  const uint32_t G = pftk_refine_blocks(M) ? pftk_refine_blocks(M) : 1u;
+  if (G > t->rf.g_cap) {
+    HIPCHK(t, hipStreamSynchronize(t->stream));
+    dfree(t->rf.part); dfree(t->rf.part_n);
+    t->rf.g_cap = 0;
+    HIPCHK(t, dalloc(&t->rf.part, (size_t)PFT_REFINE_N_SUMS * G));
+    HIPCHK(t, dalloc(&t->rf.part_n, (size_t)2 * G));
+    t->rf.g_cap = G;
+  }
+  if (!t->rf.ctl) {
+    void* p = nullptr;
+    HIPCHK(t, hipMalloc(&p, pftk_refine_ctl_bytes()));
+    t->rf.ctl = static_cast<PftRefineCtl*>(p);
+  }
+  if (!t->rf.result) HIPCHK(t, dalloc(&t->rf.result, 1));
+  if (!t->rf.trace) HIPCHK(t, dalloc(&t->rf.trace, (size_t)PFT_REFINE_MAX_ITERATIONS + 1u));
+  if (!t->d_rf_mats) HIPCHK(t, dalloc(&t->d_rf_mats, (size_t)8 * 12));
+  if (!t->d_rq_bbox_part) HIPCHK(t, dalloc(&t->d_rq_bbox_part, (size_t)t->num_cus * 6u));
+  return PFT_OK;
+}
+
+extern "C" int pft_refine(pft_tracker* t, const float* start12, const pft_refine_config* c, pft_refine_result* out) {
+  if (!t || !c || !out) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size != 1) {
+    t->err = "pft_refine is not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (t->cfg.exact_nearest) {
+    t->err = "pft_refine is not supported with the exact nearest-neighbour coherence (exact_nearest): that mode builds no octree";
+    return PFT_ERR_INVALID_ARG;
+  }
+  int r = check_ready(t);
+  if (r != PFT_OK) return r;
+  bool ok = c->max_iterations >= 1 && c->max_iterations <= PFT_REFINE_MAX_ITERATIONS && c->min_pairs >= 3;
+  ok = ok && std::isfinite(c->pair_distance) && c->pair_distance >= 0.0;
+  ok = ok && std::isfinite(c->inlier_distance) && c->inlier_distance > 0.0;
+  ok = ok && std::isfinite(c->margin) && c->margin >= 0.0;
+  ok = ok && std::isfinite(c->trans_eps) && c->trans_eps >= 0.0 && std::isfinite(c->rot_eps) && c->rot_eps >= 0.0;
+  if (!ok) {
+    t->err = "pft_refine: bad configuration value (1 <= max_iterations <= PFT_REFINE_MAX_ITERATIONS; min_pairs >= 3; "
+             "pair_distance, margin, trans_eps, rot_eps finite and >= 0; inlier_distance finite and > 0)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (start12) {
+    for (int k = 0; k < 12; k++)
+      if (!std::isfinite(start12[k])) {
+        t->err = "pft_refine: the start has a non-finite entry";
+        return PFT_ERR_INVALID_ARG;
+      }
+  } else if (!t->initialized) {
+    t->err = "pft_refine without a start before the first pft_compute: there is no result pose yet";
+    return PFT_ERR_STATE;
+  }
+  const uint32_t M = t->prm.M;
+  t->rf_valid = false;
+  r = rf_reserve(t, M);
+  if (r != PFT_OK) return r;
+  PftRefineArgs a;
+  memset(&a, 0, sizeof(a));
+  if (start12) memcpy(a.start, start12, sizeof(a.start));
+  a.use_rep = start12 ? 0u : 1u;
+  a.max_iterations = (uint32_t)c->max_iterations;
+  a.min_pairs = (uint32_t)c->min_pairs;
+  const double pd = c->pair_distance > 0.0 ? c->pair_distance : t->cfg.max_distance;
+  a.pair2 = pd * pd;
+  a.inl2 = c->inlier_distance * c->inlier_distance;
+  a.margin = c->margin > 0.0 ? c->margin : pd;
+  a.trans_eps2 = c->trans_eps * c->trans_eps;
+  a.rot_eps2 = c->rot_eps * c->rot_eps;
+  sync_dev(t);
+  t->tree_of_compute = false;  // the crop and the tree are rebuilt around the start
+  pftk_refine_init(t->stream, a, t->rf, t->d_hdr, t->d_rf_mats);
+  PftDev d = t->dev;
+  d.p_active = nullptr;  // explicit matrix count (a KLD handle's device-side count does not apply here)
+  d.mats = t->d_rf_mats;
+  d.bbox_part = t->d_rq_bbox_part;
+  d.bbox_grid = (uint32_t)t->num_cus;
+  d.bbox_part_cap = (uint32_t)t->num_cus;
+  d.bbox6 = t->d_bbox6;
+  d.gate = nullptr;
+  // the change detector's state belongs to the frames the tracker computes: this crop is not tested
+  const bool gate_on = t->gate_on;
+  t->gate_on = false;
+  stage_aabb(t, d, 8u, false);
+  stage_crop_octree_likelihood(t, d, 8u, false, true, false, false);
+  t->gate_on = gate_on;
+  pftk_refine_passes(t->stream, t->prm, d, t->rf, a);
+  HIPCHK(t, hipGetLastError());
+  HIPCHK(t, hipMemcpyAsync(out, t->rf.result, sizeof(*out), hipMemcpyDeviceToHost, t->stream));
+  HIPCHK(t, hipStreamSynchronize(t->stream));
+  t->rf_n = out->iterations + 1u;
+  t->rf_valid = true;
+  {
+    float m[16] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    memcpy(m, out->transform, sizeof(float) * 12);
+    pft_to_state(m, &out->pose);
+  }
+  r = check_device_error(t);
+  if (r != PFT_OK) {  // the passes had no target: nothing is applied
+    out->improved = 0u;
+    return r;
+  }
+  if (c->apply && out->improved) {
+    float m[16] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    memcpy(m, out->transform, sizeof(float) * 12);
+    r = pft_set_trans(t, m);
+    if (r == PFT_OK) r = pft_reset_tracking(t);
+    if (r != PFT_OK) return r;
+    out->applied = 1u;
+  }
+  return PFT_OK;
+}
+
+extern "C" int pft_get_refine_trace(pft_tracker* t, pft_refine_trace_entry* entries, size_t cap, size_t* n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!t->rf_valid) {
+    t->err = "pft_get_refine_trace: no completed pft_refine call to read";
+    return PFT_ERR_STATE;
+  }
+  if (n) *n = t->rf_n;
+  const size_t c = cap < t->rf_n ? cap : t->rf_n;
+  if (!c || !entries) return PFT_OK;
+  hipSetDevice(t->cfg.device_id);
+  HIPCHK(t, hipMemcpyAsync(entries, t->rf.trace, c * sizeof(pft_refine_trace_entry), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(t, hipStreamSynchronize(t->stream));
   return PFT_OK;
 }

@@ -365,6 +365,30 @@ void pftk_reacquire_score(hipStream_t s, const PftParams& p, const PftDev& d, ui
 // PftHeader::error into the pinned status block
 void pftk_reacquire_select(hipStream_t s, const PftParams& p, const PftDev& d, const PftRqScores& sc, uint32_t K,
                            uint32_t n_centres, uint32_t per_centre, double accept_ratio, pft_reacquire_result* out);
+// refinement of a pose (pft_refine.hip): the control block (state, current T, the loop's words) lives in HBM and is defined
+// there; part [17][g_cap] and part_n [2 g_cap] hold the per-block roots and counts, g_cap = pftk_refine_blocks(M); trace has
+// room for PFT_REFINE_MAX_ITERATIONS + 1 entries.  All owned by the feature
+struct PftRefineCtl;
+struct PftRefineDev {
+  PftRefineCtl* ctl;
+  double* part;
+  uint32_t* part_n;
+  uint32_t g_cap;
+  pft_refine_result* result;
+  pft_refine_trace_entry* trace;
+};
+struct PftRefineArgs {
+  float start[12];
+  uint32_t use_rep;     // the start is pose_to_matrix(PftHeader::rep)
+  uint32_t max_iterations, min_pairs;
+  double pair2, inl2, margin, trans_eps2, rot_eps2;
+};
+size_t pftk_refine_ctl_bytes();
+uint32_t pftk_refine_blocks(uint32_t M);
+// one lane: the start, its state, the eight shifted matrices (mats [8 x 12]) the crop box is taken over
+void pftk_refine_init(hipStream_t s, const PftRefineArgs& a, const PftRefineDev& r, const PftHeader* hdr, float* mats);
+// max_iterations + 1 passes (k_refine_pairs + k_refine_step each) against the tree of the last build
+void pftk_refine_passes(hipStream_t s, const PftParams& p, const PftDev& d, const PftRefineDev& r, const PftRefineArgs& a);
 void pftk_pack_reference(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, int argorder, float4* xyz,
                          float4* hsv);
 void pftk_pack_input(hipStream_t s, const pft_point_xyzrgba* d_pts, uint32_t n, float4* out,

@@ -5,7 +5,8 @@
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
 //                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
-//                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]]
+//                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]]
+//                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -34,6 +35,10 @@
 // is restarted at the best candidate if that one has at least accept_ratio of the model's points within inlier_distance,
 // and the centre it took is dropped for the others.  One `reacquire obj <j>: centre <c> candidate <k> inliers <n>/<M>
 // accepted <0|1>` line per lost object; when nothing is accepted, --reset-on-loss applies if given.
+// --refine[=max_iterations[,pair_distance]] (with --reacquire) refines the best candidate against the frame before the restart
+// (pft_refine: point-to-point ICP on the device); of an accepted candidate the refined pose is applied if it has more model
+// points within the inlier distance, else the candidate's own.  One `refine obj <j>: iterations <n> status <s> inliers
+// <before> -> <after>/<M> improved <0|1>` line follows the `reacquire obj` line.
 // --spread[=max_pos_sigma[,min_n_eff[,after]]] enqueues the population statistics behind every compute (pft_spread, still
 // before any result is read) and prints one `spread obj <j>: n_eff ... zero ... pos_sigma ... rpy_sigma ... flagged <0|1>` line
 // per object and frame; the pose is flagged after `after` frames in a row whose largest position sigma exceeded max_pos_sigma
@@ -121,6 +126,20 @@ int main(int argc, char** argv) {
         opt.rq_inlier_distance = inl;
       }
     }
+    else if (!std::strncmp(argv[i], "--refine", 8) && (argv[i][8] == 0 || argv[i][8] == '=')) {
+      opt.refine = true;  // --refine[=max_iterations[,pair_distance]]; the defaults 16 and the tracker's max_distance
+      if (argv[i][8] == '=') {
+        int it = opt.rf_max_iterations;
+        double pd = opt.rf_pair_distance;
+        const int got = std::sscanf(argv[i] + 9, "%d,%lf", &it, &pd);
+        if (got < 1 || it < 1 || it > PFT_REFINE_MAX_ITERATIONS || !(pd >= 0.0)) {
+          std::fprintf(stderr, "--refine=max_iterations[,pair_distance] with 1 <= max_iterations <= %d and pair_distance >= 0\n", PFT_REFINE_MAX_ITERATIONS);
+          return 2;
+        }
+        opt.rf_max_iterations = it;
+        opt.rf_pair_distance = pd;
+      }
+    }
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -132,7 +151,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -142,6 +161,10 @@ int main(int argc, char** argv) {
   }
   if (opt.reacquire && !opt.match) {
     std::fprintf(stderr, "--reacquire needs --match: it is the match that says an object is lost\n");
+    return 2;
+  }
+  if (opt.refine && !opt.reacquire) {
+    std::fprintf(stderr, "--refine needs --reacquire: it is the re-acquired pose that is refined\n");
     return 2;
   }
   if (async && !raw) {

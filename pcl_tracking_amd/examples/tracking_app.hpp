@@ -16,6 +16,7 @@
 //                        ellipsoid, angle sigmas and the spread rule
 //   --reacquire          a lost object is looked for among the cluster centroids of a segmentation of the frame
 //                        (reacquire) and restarted where it is found
+//   --refine             the pose found by --reacquire is refined against the frame (refine) before the restart
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -62,6 +63,9 @@ struct Options {
   double spread_min_n_eff = 0.0;        // or below this effective sample size
   int spread_after = 1;
   bool reacquire = false;               // a lost object is looked for among the clusters of the frame (pft_reacquire)
+  bool refine = false;                  // --refine: the best candidate of a re-acquisition is refined (pft_refine)
+  int rf_max_iterations = 16;
+  double rf_pair_distance = 0.0;        // 0: the tracker's max_distance
   int rq_n_yaw = 8;                     // yaw steps over the full circle around the object's initial orientation
   double rq_accept_ratio = 0.5;         // inliers / model points a candidate needs
   double rq_inlier_distance = 0.02;
@@ -280,7 +284,7 @@ class TrackingApp {
       cfg.n_yaw = opt_.rq_n_yaw;
       cfg.accept_ratio = opt_.rq_accept_ratio;
       cfg.inlier_distance = opt_.rq_inlier_distance;
-      cfg.apply = 1;
+      cfg.apply = opt_.refine ? 0 : 1;  // --refine: the lattice call only selects
       pft_reacquire_result res;
       int st;
       if (!have_centres) {
@@ -300,12 +304,34 @@ class TrackingApp {
       const int centre = st == PFT_OK && res.best_centre >= 0 ? cluster_of[(size_t)res.best_centre] : -1;
       std::printf("reacquire obj %d: centre %d candidate %d inliers %u/%u accepted %d\n", obj_id, centre,
                   st == PFT_OK ? res.best : -1, res.n_inliers, res.n_reference, accepted ? 1 : 0);
+      if (opt_.refine && st == PFT_OK && res.best >= 0) refineBest(obj_id, tr, res, accepted);
       if (accepted) {
         centres.erase(centres.begin() + 3 * res.best_centre, centres.begin() + 3 * res.best_centre + 3);
         cluster_of.erase(cluster_of.begin() + res.best_centre);
       } else if (opt_.reset_on_loss) {
         tr.resetTracking();
       }
+    }
+  }
+
+  // --refine: the best candidate of a re-acquisition refined against the frame (refine).  Of an accepted candidate the
+  // refined pose is applied if the refinement improved it, else the candidate's own
+  void refineBest(int obj_id, ParticleFilter& tr, const pft_reacquire_result& res, bool accepted) {
+    pft_refine_config cfg = tr.refineConfig();
+    cfg.max_iterations = opt_.rf_max_iterations;
+    cfg.pair_distance = opt_.rf_pair_distance;
+    cfg.apply = accepted ? 1 : 0;
+    pft_refine_result r;
+    const int st = tr.refine(res.transform, cfg, r);
+    static const char* const names[] = {"CONVERGED", "MAX_ITERATIONS", "TOO_FEW_PAIRS"};
+    std::printf("refine obj %d: iterations %u status %s inliers %u -> %u/%u improved %d\n", obj_id, r.iterations,
+                st == PFT_OK && r.status < 3u ? names[r.status] : "FAILED", r.before.n_inliers, r.after.n_inliers, res.n_reference,
+                st == PFT_OK && r.improved ? 1 : 0);
+    if (accepted && !(st == PFT_OK && r.applied)) {
+      Affine3f m = Affine3f::Identity();
+      std::memcpy(m.m, res.transform, sizeof(float) * 12);
+      tr.setTrans(m);
+      tr.resetTracking();
     }
   }
 

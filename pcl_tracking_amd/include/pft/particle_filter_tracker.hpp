@@ -484,6 +484,27 @@ class ParticleFilterTracker {
     return c;
   }
 
+  // ---- refinement of a pose against the frame (pft.h, pft_refine) ----
+  // point-to-point ICP from start12 (row-major 3x4; nullptr: the last result pose) against the input cloud the handle holds,
+  // all iterations on the device; with cfg.apply and an improved pose the tracker is restarted at it: setTrans(the final
+  // matrix) + resetTracking().  Synchronous.  Returns the pft_status
+  int refine(const float* start12 /*nullptr: the result*/, const pft_refine_config& cfg, pft_refine_result& out) {
+    std::memset(&out, 0, sizeof(out));
+    int st = handInput("refine");
+    if (st != PFT_OK) return st;
+    st = check(pft_refine(handle_, start12, &cfg, &out), "refine");
+    if (st == PFT_OK && out.applied) {
+      trans_ = Affine3f::Identity();
+      std::memcpy(trans_.m, out.transform, sizeof(float) * 12);
+    }
+    return st;
+  }
+  pft_refine_config refineConfig() const {
+    pft_refine_config c;
+    pft_refine_config_default(&c);
+    return c;
+  }
+
   int getIterationNum() const { return cfg_.iteration_num; }
   int getParticleNum() const { return cfg_.particle_num; }
   pft_tracker* nativeHandle() { return handle_; }

@@ -145,6 +145,7 @@ class ReacquireResult:
     coherence: float
     sum_sq_dist: float
     inlier_sq_dist: float
+    refined: object = None  # reacquire(refine=True): the RefineResult of the best candidate
 
     @property
     def trans(self):
@@ -161,6 +162,52 @@ class ReacquireResult:
                    transform=np.array(r.transform, dtype=np.float32).reshape(3, 4), n_inliers=int(r.n_inliers),
                    n_matched=int(r.n_matched), accepted=bool(r.accepted), applied=bool(r.applied),
                    coherence=float(r.coherence), sum_sq_dist=float(r.sum_sq_dist), inlier_sq_dist=float(r.inlier_sq_dist))
+
+
+@dataclass
+class RefineResult:
+    """pft_refine_result: what a refinement call did"""
+    status: int            # index into _lib.REFINE_STATUS
+    iterations: int        # solves taken
+    n_reference: int
+    n_crop: int
+    bbox: np.ndarray       # float64 x_min, x_max, y_min, y_max, z_min, z_max of the crop
+    start: np.ndarray      # 3x4 float32
+    transform: np.ndarray  # 3x4 float32, the final T
+    pose: np.ndarray       # PARTICLE_DTYPE record: toState of `transform`
+    n_pairs_before: int
+    n_inliers_before: int
+    sum_sq_dist_before: float
+    inlier_sq_dist_before: float
+    n_pairs_after: int
+    n_inliers_after: int
+    sum_sq_dist_after: float
+    inlier_sq_dist_after: float
+    improved: bool
+    applied: bool
+
+    @property
+    def status_name(self):
+        return _lib.REFINE_STATUS[self.status]
+
+    @property
+    def trans(self):
+        """the 4x4 that apply hands to setTrans: `transform` over the row (0, 0, 0, 1)"""
+        m = np.eye(4, dtype=np.float32)
+        m[:3] = self.transform
+        return m
+
+    @classmethod
+    def from_struct(cls, r):
+        pose = np.frombuffer(bytes(r.pose), PARTICLE_DTYPE)[0].copy()
+        b, a = r.before, r.after
+        return cls(status=int(r.status), iterations=int(r.iterations), n_reference=int(r.n_reference), n_crop=int(r.n_crop),
+                   bbox=np.array(r.bbox, dtype=np.float64), start=np.array(r.start, dtype=np.float32).reshape(3, 4),
+                   transform=np.array(r.transform, dtype=np.float32).reshape(3, 4), pose=pose,
+                   n_pairs_before=int(b.n_pairs), n_inliers_before=int(b.n_inliers), sum_sq_dist_before=float(b.sum_sq_dist),
+                   inlier_sq_dist_before=float(b.inlier_sq_dist), n_pairs_after=int(a.n_pairs), n_inliers_after=int(a.n_inliers),
+                   sum_sq_dist_after=float(a.sum_sq_dist), inlier_sq_dist_after=float(a.inlier_sq_dist),
+                   improved=bool(r.improved), applied=bool(r.applied))
 
 
 class DistanceCoherence:
@@ -596,12 +643,14 @@ class ParticleFilterTracker:
 
     # ---- re-acquisition of a lost object ----
     def reacquire(self, centres=None, segmenter=None, n=(1, 1, 8), span=(0.0, 0.0, 2.0 * np.pi), base_rpy=None,
-                  inlier_distance=0.02, accept_ratio=0.5, apply=True):
+                  inlier_distance=0.02, accept_ratio=0.5, apply=True, refine=False):
         """scores every centre x every orientation of the lattice (n = steps of roll, pitch, yaw over `span` around
         base_rpy; None: the angles of the current trans) against the current input cloud and returns the best candidate as
         a ReacquireResult.  centres: (k, 3) positions; or segmenter: a ModelSegmenter that has been applied -- the centroids
         of its clusters, formed on the device.  apply=True and an accepted candidate: setTrans(result.trans) +
-        resetTracking().  Synchronous"""
+        resetTracking().  refine=True: the lattice call only selects; its best transform is refined (refine(), the
+        defaults), and of an accepted candidate the refined pose is applied if the refinement improved it, else the
+        candidate's own (result.refined holds the RefineResult).  Synchronous"""
         if (centres is None) == (segmenter is None):
             raise PftError(1, "reacquire: give either centres or a segmenter")
         self._ensure()
@@ -617,7 +666,7 @@ class ParticleFilterTracker:
             cfg.span_rpy[a] = float(span[a])
         cfg.inlier_distance = float(inlier_distance)
         cfg.accept_ratio = float(accept_ratio)
-        cfg.apply = 1 if apply else 0
+        cfg.apply = 1 if (apply and not refine) else 0
         r = _lib.ReacquireResultStruct()
         if segmenter is not None:
             if segmenter._h is None:
@@ -628,9 +677,60 @@ class ParticleFilterTracker:
             self._check(self._L.pft_reacquire(self._h, _ptr(c), len(c), C.byref(cfg), C.byref(r)))
         res = ReacquireResult.from_struct(r)
         self._rq_centres = res.n_centres  # getReacquireScores sizes its centre array by it
+        if refine and res.best >= 0:
+            res.refined = self.refine(start=res.transform, apply=bool(apply and res.accepted))
+            if apply and res.accepted:
+                if not res.refined.applied:
+                    self.setTrans(res.trans)
+                    self.resetTracking()
+                res.applied = True
+                return res
         if res.applied:
             self._trans = res.trans  # what a later close() and re-creation hands to the new handle
         return res
+
+    # ---- refinement of a pose against the frame ----
+    def refine(self, start=None, max_iterations=16, pair_distance=None, inlier_distance=0.02, margin=None, trans_eps=1e-4,
+               rot_eps=1e-3, min_pairs=3, apply=False):
+        """point-to-point ICP from `start` (3x4 or 4x4; None: the last result pose) against the current input cloud, all
+        iterations on the device; returns a RefineResult.  pair_distance None: the tracker's max_distance; margin None:
+        pair_distance.  apply=True and an improved pose: setTrans(result.trans) + resetTracking().  Synchronous"""
+        self._ensure()
+        cfg = _lib.RefineConfig()
+        self._L.pft_refine_config_default(C.byref(cfg))
+        cfg.max_iterations, cfg.min_pairs = int(max_iterations), int(min_pairs)
+        cfg.pair_distance = 0.0 if pair_distance is None else float(pair_distance)
+        cfg.inlier_distance = float(inlier_distance)
+        cfg.margin = 0.0 if margin is None else float(margin)
+        cfg.trans_eps, cfg.rot_eps = float(trans_eps), float(rot_eps)
+        cfg.apply = 1 if apply else 0
+        s = None
+        if start is not None:
+            s = np.asarray(start, np.float32)
+            if s.shape not in ((3, 4), (4, 4), (12,), (16,)):
+                raise PftError(1, "refine: start must be a 3x4 or 4x4 matrix")
+            s = np.ascontiguousarray(s.reshape(-1)[:12])
+        r = _lib.RefineResultStruct()
+        self._check(self._L.pft_refine(self._h, _ptr(s), C.byref(cfg), C.byref(r)))
+        res = RefineResult.from_struct(r)
+        if res.applied:
+            self._trans = res.trans
+        return res
+
+    def getRefineTrace(self):
+        """the passes of the last refine(): dict(transform (n, 3, 4) float32, n_pairs, n_inliers (uint32), sums (n, 17),
+        step_t2, step_r2 (float64)), n = iterations + 1"""
+        if self._h is None:
+            raise PftError(7, "getRefineTrace before the first refine()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_refine_trace(self._h, None, 0, C.byref(n)))
+        e = (_lib.RefineTraceEntry * max(n.value, 1))()
+        self._check(self._L.pft_get_refine_trace(self._h, C.cast(e, C.c_void_p), n.value, C.byref(n)))
+        e = e[:n.value]
+        return dict(transform=np.array([list(x.transform) for x in e], np.float32).reshape(-1, 3, 4),
+                    n_pairs=np.array([x.n_pairs for x in e], np.uint32), n_inliers=np.array([x.n_inliers for x in e], np.uint32),
+                    sums=np.array([list(x.sums) for x in e], np.float64).reshape(-1, 17),
+                    step_t2=np.array([x.step_t2 for x in e], np.float64), step_r2=np.array([x.step_r2 for x in e], np.float64))
 
     def getReacquireScores(self):
         """the candidates and scores of the last reacquire(), in candidate order: dict(candidates (PARTICLE_DTYPE), mats
