@@ -2584,8 +2584,8 @@ static int rq_reserve(pft_tracker* t, uint32_t K, uint32_t n_centres) {
   return PFT_OK;
 }
 
-// the refusals that do not depend on the centres; *per_centre = n_roll * n_pitch * n_yaw
-static int rq_check(pft_tracker* t, const pft_reacquire_config* c, const char* who, uint64_t* per_centre) {
+// ---- shared by the evaluators that score foreign poses in the handle's octree (pft_reacquire*, pft_refine) ----
+static int tree_refusals(pft_tracker* t, const char* who) {
   if (t->cfg.world_size != 1) {
     t->err = std::string(who) + " is not supported on a sharded handle (world_size > 1)";
     return PFT_ERR_INVALID_ARG;
@@ -2594,7 +2594,46 @@ static int rq_check(pft_tracker* t, const pft_reacquire_config* c, const char* w
     t->err = std::string(who) + " is not supported with the exact nearest-neighbour coherence (exact_nearest): that mode builds no octree";
     return PFT_ERR_INVALID_ARG;
   }
-  const int r = check_ready(t);
+  return PFT_OK;
+}
+
+// the crop and the tree of the n matrices at `mats`, built by the handle's own launches; returns what the scoring
+// launches take.  (pft_eval_weights keeps a block of its own: the handle's bbox_part, the gate, other flags)
+static PftDev rebuild_tree_for(pft_tracker* t, float* mats, uint32_t n) {
+  PftDev d = t->dev;
+  d.p_active = nullptr;  // explicit matrix count (a KLD handle's device-side count does not apply here)
+  d.mats = mats;
+  d.bbox_part = t->d_rq_bbox_part;
+  d.bbox_grid = (uint32_t)t->num_cus;
+  d.bbox_part_cap = (uint32_t)t->num_cus;
+  d.bbox6 = t->d_bbox6;
+  d.gate = nullptr;
+  // the change detector's state belongs to the frames the tracker computes: this crop is not tested
+  const bool gate_on = t->gate_on;
+  t->gate_on = false;
+  stage_aabb(t, d, n, false);
+  stage_crop_octree_likelihood(t, d, n, false, true, false, false);
+  t->gate_on = gate_on;
+  return d;
+}
+
+static void m16_from_m12(const float* m12, float m[16]) {
+  memcpy(m, m12, sizeof(float) * 12);
+  m[12] = m[13] = m[14] = 0.0f;
+  m[15] = 1.0f;
+}
+// a row-major 3x4 transform becomes the handle's pose, and tracking starts over from it
+static int apply_pose(pft_tracker* t, const float* m12) {
+  float m[16];
+  m16_from_m12(m12, m);
+  const int r = pft_set_trans(t, m);
+  return r == PFT_OK ? pft_reset_tracking(t) : r;
+}
+
+// the refusals that do not depend on the centres; *per_centre = n_roll * n_pitch * n_yaw
+static int rq_check(pft_tracker* t, const pft_reacquire_config* c, const char* who, uint64_t* per_centre) {
+  int r = tree_refusals(t, who);
+  if (r == PFT_OK) r = check_ready(t);
   if (r != PFT_OK) return r;
   bool ok = c->n_roll >= 1 && c->n_pitch >= 1 && c->n_yaw >= 1;
   for (int a = 0; a < 3; a++) ok = ok && std::isfinite(c->base_rpy[a]) && std::isfinite(c->span_rpy[a]) && c->span_rpy[a] >= 0.0f;
@@ -2656,22 +2695,9 @@ static int rq_run(pft_tracker* t, const char* who, const pft_reacquire_config* c
     lat.span[a] = c->span_rpy[a];
   }
   pftk_reacquire_candidates(t->stream, t->d_rq_centres, K, lat, t->d_rq_part, t->d_rq_mats);
-  PftDev d = t->dev;
-  d.p_active = nullptr;  // explicit candidate count (a KLD handle's device-side count does not apply here)
-  d.part_cur = t->d_rq_part;
+  PftDev d = rebuild_tree_for(t, t->d_rq_mats, K);
+  d.part_cur = t->d_rq_part;  // (k_reacquire_select reads the candidates' poses)
   d.part_all = t->d_rq_part;
-  d.mats = t->d_rq_mats;
-  d.bbox_part = t->d_rq_bbox_part;
-  d.bbox_grid = (uint32_t)t->num_cus;
-  d.bbox_part_cap = (uint32_t)t->num_cus;
-  d.bbox6 = t->d_bbox6;
-  d.gate = nullptr;
-  // the change detector's state belongs to the frames the tracker computes: this crop is not tested
-  const bool gate_on = t->gate_on;
-  t->gate_on = false;
-  stage_aabb(t, d, K, false);
-  stage_crop_octree_likelihood(t, d, K, false, true, false, false);
-  t->gate_on = gate_on;
   pftk_reacquire_score(t->stream, t->prm, d, K, c->inlier_distance * c->inlier_distance, t->rq_sc);
   pftk_reacquire_select(t->stream, t->prm, d, t->rq_sc, K, n_centres, (uint32_t)per_centre, c->accept_ratio, t->d_rq_result);
   HIPCHK(t, hipGetLastError());
@@ -2684,10 +2710,7 @@ static int rq_run(pft_tracker* t, const char* who, const pft_reacquire_config* c
     return r;
   }
   if (c->apply && out->accepted) {
-    float m[16] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    memcpy(m, out->transform, sizeof(float) * 12);
-    r = pft_set_trans(t, m);
-    if (r == PFT_OK) r = pft_reset_tracking(t);
+    r = apply_pose(t, out->transform);
     if (r != PFT_OK) return r;
     out->applied = 1u;
   }
@@ -2811,15 +2834,8 @@ static int rf_reserve(pft_tracker* t, uint32_t M) {
 
 extern "C" int pft_refine(pft_tracker* t, const float* start12, const pft_refine_config* c, pft_refine_result* out) {
   if (!t || !c || !out) return PFT_ERR_INVALID_ARG;
-  if (t->cfg.world_size != 1) {
-    t->err = "pft_refine is not supported on a sharded handle (world_size > 1)";
-    return PFT_ERR_INVALID_ARG;
-  }
-  if (t->cfg.exact_nearest) {
-    t->err = "pft_refine is not supported with the exact nearest-neighbour coherence (exact_nearest): that mode builds no octree";
-    return PFT_ERR_INVALID_ARG;
-  }
-  int r = check_ready(t);
+  int r = tree_refusals(t, "pft_refine");
+  if (r == PFT_OK) r = check_ready(t);
   if (r != PFT_OK) return r;
   bool ok = c->max_iterations >= 1 && c->max_iterations <= PFT_REFINE_MAX_ITERATIONS && c->min_pairs >= 3;
   ok = ok && std::isfinite(c->pair_distance) && c->pair_distance >= 0.0;
@@ -2860,41 +2876,23 @@ extern "C" int pft_refine(pft_tracker* t, const float* start12, const pft_refine
   sync_dev(t);
   t->tree_of_compute = false;  // the crop and the tree are rebuilt around the start
   pftk_refine_init(t->stream, a, t->rf, t->d_hdr, t->d_rf_mats);
-  PftDev d = t->dev;
-  d.p_active = nullptr;  // explicit matrix count (a KLD handle's device-side count does not apply here)
-  d.mats = t->d_rf_mats;
-  d.bbox_part = t->d_rq_bbox_part;
-  d.bbox_grid = (uint32_t)t->num_cus;
-  d.bbox_part_cap = (uint32_t)t->num_cus;
-  d.bbox6 = t->d_bbox6;
-  d.gate = nullptr;
-  // the change detector's state belongs to the frames the tracker computes: this crop is not tested
-  const bool gate_on = t->gate_on;
-  t->gate_on = false;
-  stage_aabb(t, d, 8u, false);
-  stage_crop_octree_likelihood(t, d, 8u, false, true, false, false);
-  t->gate_on = gate_on;
+  const PftDev d = rebuild_tree_for(t, t->d_rf_mats, 8u);
   pftk_refine_passes(t->stream, t->prm, d, t->rf, a);
   HIPCHK(t, hipGetLastError());
   HIPCHK(t, hipMemcpyAsync(out, t->rf.result, sizeof(*out), hipMemcpyDeviceToHost, t->stream));
   HIPCHK(t, hipStreamSynchronize(t->stream));
   t->rf_n = out->iterations + 1u;
   t->rf_valid = true;
-  {
-    float m[16] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    memcpy(m, out->transform, sizeof(float) * 12);
-    pft_to_state(m, &out->pose);
-  }
+  float m[16];
+  m16_from_m12(out->transform, m);
+  pft_to_state(m, &out->pose);
   r = check_device_error(t);
   if (r != PFT_OK) {  // the passes had no target: nothing is applied
     out->improved = 0u;
     return r;
   }
   if (c->apply && out->improved) {
-    float m[16] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    memcpy(m, out->transform, sizeof(float) * 12);
-    r = pft_set_trans(t, m);
-    if (r == PFT_OK) r = pft_reset_tracking(t);
+    r = apply_pose(t, out->transform);
     if (r != PFT_OK) return r;
     out->applied = 1u;
   }

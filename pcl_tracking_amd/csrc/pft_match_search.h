@@ -1,5 +1,8 @@
-// pft_match_search.h -- the pieces of the result-pose search that pft_match.hip (k_match) and pft_reacquire.hip
-// (k_reacquire_score) share: the choice among the existing children of one octree level and the value of a matched pair.
+// pft_match_search.h -- the result-pose search of pft_match.hip (k_match), pft_reacquire.hip (k_reacquire_score) and
+// pft_refine.hip (k_refine_pairs), DESIGN.md section 3.10: the view of the frame's tree, the choice among the existing
+// children of one octree level, the descent with the leaf scan, and the value of a matched pair.  The tree is read where
+// the builder left it (words and leaf records through L2): no LDS staging, no centre tables, no jump or ancestor table --
+// the queries are a downsampled model of a few thousand points, one descent each.
 #pragma once
 #include "pft_device_utils.h"
 
@@ -27,6 +30,77 @@ __device__ __forceinline__ uint32_t mt_min_child(uint32_t mask, double vs, const
     }
   }
   return bc;
+}
+
+// the tree the handle's last crop and build left, as the search reads it
+struct MtTree {
+  int D;
+  uint32_t n_words, n_crop;  // n_crop == 0: the tree must not be read, nothing finds a partner
+  bool indirect;             // the leaf records are followed through leaf_order into the crop
+  double omin[3], res;
+};
+
+// the one gate on the tree: a failed crop or build (PftHeader::error), an empty crop, or a tree that was never built or
+// does not fit the words the search may read
+__device__ __forceinline__ MtTree mt_load_tree(const PftHeader* hdr, const PftDev& d, const PftParams& prm) {
+  MtTree t;
+  t.D = hdr->depth;
+  t.n_words = hdr->n_words;
+  const bool usable = hdr->error == 0u && t.D > 0 && t.D <= PFT_MAX_DEPTH && t.n_words != 0u && t.n_words <= d.max_words;
+  t.n_crop = usable ? hdr->n_crop : 0u;
+  t.indirect = hdr->leaf_indirect != 0;
+  for (int a = 0; a < 3; a++) t.omin[a] = hdr->omin[a];
+  t.res = prm.res;
+  return t;
+}
+
+// OctreePointCloudSearch::approxNearestSearch of q: at every level the existing child whose voxel centre is closest, then
+// the leaf's points in insertion order.  Returns whether q has a partner; bd = its float d2 (INFINITY without one), bt its
+// record, pos its position among the leaf records (the crop index is min(d.leaf_order[pos], n_crop - 1))
+__device__ __forceinline__ bool mt_search(const MtTree& t, const PftDev& d, float qx, float qy, float qz, float& bd,
+                                          float4& bt, uint32_t& pos) {
+  bd = INFINITY;
+  bt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  pos = 0xffffffffu;
+  if (t.n_crop == 0u) return false;
+  const int D = t.D;
+  uint32_t node = 0u, kx = 0u, ky = 0u, kz = 0u;
+  bool ok = true;
+  for (int lvl = 0; lvl < D; lvl++) {
+    const uint32_t wv = d.words[node];
+    const uint32_t mask = wv & 0xffu, base = wv >> 8;
+    const double vs = t.res * (double)(1u << (D - lvl - 1));
+    const uint32_t bc = mt_min_child(mask, vs, t.omin, kx, ky, kz, qx, qy, qz);
+    node = base + __popc(mask & ((1u << (bc & 7u)) - 1u));
+    // (a node without children, or a child index past the words: not a tree the builders write -- no partner instead of
+    // a read out of bounds)
+    ok = ok && bc != 0xffu && node + 1u < t.n_words;
+    if (!ok) break;
+    // U10 (switch point -- carried here, in the likelihood kernel and in the CPU restatement under
+    // oracle/): the key handed down is the chosen (minimum) child's, PCL's `minChildKey`; the upstream variant that
+    // handed down `new_key` -- the last existing child iterated -- would take the bits of 31 - clz(mask) here instead of bc
+    kx = 2u * kx + ((bc >> 2) & 1u);
+    ky = 2u * ky + ((bc >> 1) & 1u);
+    kz = 2u * kz + (bc & 1u);
+  }
+  if (!ok) return false;
+  const uint32_t ls = d.words[node], le = min(d.words[node + 1u], t.n_crop);
+  // leaf scan in float: the first strictly smaller candidate wins (insertion order)
+  for (uint32_t p = ls; p < le; p++) {
+    float4 c;
+    if (t.indirect)
+      c = d.crop_pts[min(d.leaf_order[p], t.n_crop - 1u)];
+    else
+      c = d.leaf_pts[p];
+    const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
+    const float dd = dx * dx + (dy * dy + dz * dz);
+    if (dd < bd) {
+      bd = dd;
+      bt = c;
+      pos = p;
+    }
+  }
+  return pos != 0xffffffffu;
 }
 
 // DistanceCoherence x HSVColorCoherence of the pair (restated from pft_likelihood.hip, A7; PCL's two double divisions)

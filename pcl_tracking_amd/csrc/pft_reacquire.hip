@@ -7,21 +7,18 @@
 //                           k_md_centroid), one workgroup per cluster: the centres of pft_reacquire_from_segmenter
 //   k_reacquire_candidates  candidate k = ((c n_roll + ir) n_pitch + ip) n_yaw + iy: the pose and its 3x4 matrix
 //   k_reacquire_score       one workgroup per candidate over tiles of RQ_THREADS reference points in stored (Morton) order:
-//                           q = T_k p_j, k_match's descent and leaf scan, the two gates, five sums
+//                           q = T_k p_j, mt_search (pft_match_search.h), the two gates, five sums
 //   k_reacquire_select      one workgroup: the best candidate and the result block
 //
 // Sums: n_matched and n_inliers are integers; coherence, sum_sq_dist and inlier_sq_dist are adjacent-pair trees in double
-// over the positions 0 .. M-1 padded with +0.0 (every term is >= +0.0): a lane's one position, the wave (xor 1 .. 32), the
-// waves of the tile (LDS), then the tiles (a binary counter in LDS).  Every level is an aligned subtree of the one tree, so
-// the bits do not depend on the workgroup size: the first two are k_match's bits for the same T and the same tree.
-//
-// The tree is read where the builder left it (words and leaf records through L2), as k_match reads it.
+// (pft_pair_tree.h, ungated) over the positions 0 .. M-1 padded with +0.0 (every term is >= +0.0): a lane's one position,
+// the wave, the waves of the tile, then the tiles.  The first two are k_match's bits for the same T and the same tree.
 #include "pft_device_utils.h"
 #include "pft_match_search.h"
+#include "pft_pair_tree.h"
 
 #define RQ_THREADS 256
 #define RQ_WAVES (RQ_THREADS / 64)
-#define RQ_MAX_LEVELS 32
 #define RQ_CEN_THREADS 256u
 #define RQ_CEN_STAGE 1024u  // points per round: 12 KiB of LDS
 
@@ -84,13 +81,13 @@ __global__ __launch_bounds__(256) void k_reacquire_candidates(const float* __res
 // ---- the scores ----
 struct RqSh {
   double part[RQ_WAVES][3];
-  double stk[RQ_MAX_LEVELS][3];
+  double stk[PT_MAX_LEVELS][3];
   uint32_t n_matched, n_inliers;
 };
 
 __global__ void __launch_bounds__(RQ_THREADS) k_reacquire_score(PftParams prm, PftDev d, double inl2, PftRqScores out) {
   __shared__ RqSh sh;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, k = blockIdx.x;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, k = blockIdx.x;
   const PftHeader* hdr = d.hdr;
   if (tid == 0) {
     sh.n_matched = 0u;
@@ -101,99 +98,35 @@ __global__ void __launch_bounds__(RQ_THREADS) k_reacquire_score(PftParams prm, P
   load_matrix(d.mats, k, T);
 
   const uint32_t M = prm.M;
-  const int D = hdr->depth;
-  const uint32_t n_words = hdr->n_words;
-  // a failed crop or build (PftHeader::error), an empty crop or a tree that was never built: nothing matches
-  const uint32_t n_crop =
-      (hdr->error != 0u || D <= 0 || D > PFT_MAX_DEPTH || n_words == 0u || n_words > d.max_words) ? 0u : hdr->n_crop;
-  const bool indirect = hdr->leaf_indirect != 0;
-  const double omin[3] = {hdr->omin[0], hdr->omin[1], hdr->omin[2]};
-  const double res = prm.res, maxd2 = prm.maxd2;
+  const MtTree tree = mt_load_tree(hdr, d, prm);
+  const double maxd2 = prm.maxd2;
 
   uint32_t my_matched = 0u, my_inliers = 0u;
   const uint32_t n_tiles = (M + RQ_THREADS - 1u) / RQ_THREADS;
   for (uint32_t tile = 0; tile < n_tiles; tile++) {
     const uint32_t j = tile * RQ_THREADS + tid;
-    double v_coh = 0.0, v_d2 = 0.0, v_in = 0.0;
+    double v[3] = {0.0, 0.0, 0.0};  // coherence, sum_sq_dist, inlier_sq_dist
     if (j < M) {
       const float4 r = d.ref_xyz[j];
       float qx, qy, qz;
       xform(T, r.x, r.y, r.z, qx, qy, qz);
-      float bd = INFINITY;
-      bool found = false;
-      float4 bt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      if (n_crop != 0u) {
-        uint32_t node = 0u, kx = 0u, ky = 0u, kz = 0u;
-        bool ok = true;
-        for (int lvl = 0; lvl < D; lvl++) {
-          const uint32_t wv = d.words[node];
-          const uint32_t mask = wv & 0xffu, base = wv >> 8;
-          const double vs = res * (double)(1u << (D - lvl - 1));
-          const uint32_t bc = mt_min_child(mask, vs, omin, kx, ky, kz, qx, qy, qz);
-          node = base + __popc(mask & ((1u << (bc & 7u)) - 1u));
-          // (a node without children, or a child index past the words: no partner instead of a read out of bounds)
-          ok = ok && bc != 0xffu && node + 1u < n_words;
-          if (!ok) break;
-          // U10: the key handed down is the chosen (minimum) child's, as in k_match
-          kx = 2u * kx + ((bc >> 2) & 1u);
-          ky = 2u * ky + ((bc >> 1) & 1u);
-          kz = 2u * kz + (bc & 1u);
-        }
-        if (ok) {
-          const uint32_t ls = d.words[node], le = min(d.words[node + 1u], n_crop);
-          // leaf scan in float: the first strictly smaller candidate wins (insertion order)
-          for (uint32_t pos = ls; pos < le; pos++) {
-            float4 c;
-            if (indirect)
-              c = d.crop_pts[min(d.leaf_order[pos], n_crop - 1u)];
-            else
-              c = d.leaf_pts[pos];
-            const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
-            const float dd = dx * dx + (dy * dy + dz * dz);
-            if (dd < bd) {
-              bd = dd;
-              found = true;
-              bt = c;
-            }
-          }
-        }
-      }
+      float bd;
+      float4 bt;
+      uint32_t pos;
+      const bool found = mt_search(tree, d, qx, qy, qz, bd, bt, pos);
       if (found && (double)bd < maxd2) {
-        v_coh = mt_pair_value(prm, qx, qy, qz, bt, d.ref_hsv[j]);
-        v_d2 = (double)bd;
+        v[0] = mt_pair_value(prm, qx, qy, qz, bt, d.ref_hsv[j]);
+        v[1] = (double)bd;
         my_matched++;
       }
       if (found && (double)bd < inl2) {
-        v_in = (double)bd;
+        v[2] = (double)bd;
         my_inliers++;
       }
     }
-    // lanes 2i and 2i+1 hold the two halves; both form left + right (addition commutes bit for bit)
-    for (int o = 1; o < 64; o <<= 1) {
-      v_coh = v_coh + __shfl_xor(v_coh, o);
-      v_d2 = v_d2 + __shfl_xor(v_d2, o);
-      v_in = v_in + __shfl_xor(v_in, o);
-    }
-    if (lane == 0) {
-      sh.part[wave][0] = v_coh;
-      sh.part[wave][1] = v_d2;
-      sh.part[wave][2] = v_in;
-    }
-    __syncthreads();
-    if (tid < 3u) {
-      double w[RQ_WAVES];
-#pragma unroll
-      for (int q = 0; q < RQ_WAVES; q++) w[q] = sh.part[q][tid];
-#pragma unroll
-      for (int h = RQ_WAVES / 2; h >= 1; h >>= 1)
-#pragma unroll
-        for (int q = 0; q < h; q++) w[q] = w[2 * q] + w[2 * q + 1];
-      // tiles: binary counter (tile t merges the pending subtrees its trailing one bits name)
-      double v = w[0];
-      uint32_t l = 0;
-      for (uint32_t b = tile; b & 1u; b >>= 1, l++) v = sh.stk[l][tid] + v;
-      sh.stk[l][tid] = v;
-    }
+    pt_wave<false>(v);
+    const double root = pt_waves<false, RQ_WAVES>(v, sh.part);
+    if (tid < 3u) pt_push(sh.stk, tile, root);
     __syncthreads();
   }
   my_matched = wave_sum(my_matched);
@@ -202,17 +135,8 @@ __global__ void __launch_bounds__(RQ_THREADS) k_reacquire_score(PftParams prm, P
   if (lane == 0 && my_inliers) atomicAdd(&sh.n_inliers, my_inliers);
   __syncthreads();
   if (tid < 3u) {
-    // the pending subtrees, from the smallest (rightmost) up: the padded tree's root is the right-to-left fold of what the
-    // counter holds (the padding adds +0.0 to sums that are >= +0.0)
-    double v = 0.0;
-    bool any = false;
-    for (uint32_t l = 0; l < RQ_MAX_LEVELS; l++)
-      if ((n_tiles >> l) & 1u) {
-        v = any ? sh.stk[l][tid] + v : sh.stk[l][tid];
-        any = true;
-      }
     double* dst = tid == 0u ? out.coherence : (tid == 1u ? out.sum_sq_dist : out.inlier_sq_dist);
-    dst[k] = v;
+    dst[k] = pt_fold(sh.stk, n_tiles);
   }
   if (tid == 0) {
     out.n_matched[k] = sh.n_matched;

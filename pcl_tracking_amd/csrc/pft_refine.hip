@@ -4,8 +4,8 @@
 //
 //   k_refine_init    one lane: the start matrix (the argument, or pose_to_matrix of PftHeader::rep), the state (Q, t) of
 //                    it, the eight shifted copies the box is taken over, the control words
-//   k_refine_pairs   workgroups of 256 lanes over aligned blocks of 256 stored (Morton) positions: q = T p_j, k_match's
-//                    descent and leaf scan, the two gates, the 17 terms in registers, then the lane -> wave -> workgroup
+//   k_refine_pairs   workgroups of 256 lanes over aligned blocks of 256 stored (Morton) positions: q = T p_j, mt_search
+//                    (pft_match_search.h), the two gates, the 17 terms in registers, then the lane -> wave -> workgroup
 //                    levels of the one adjacent-pair tree; the block's 17 roots and two counts go to the partial arrays
 //   k_refine_step    one workgroup: the grid level of the same tree over the blocks' roots, then pft_refine_solve.h in one
 //                    lane: the next T, the trace entry, the loop's decision
@@ -13,16 +13,14 @@
 // Every pass is one k_refine_pairs and one k_refine_step; all max_iterations + 1 passes are enqueued at once and a launch
 // that finds the `done` word set returns at once: no atomics, fences or device-scope barriers, and the host waits once.
 //
-// The tree: positions 0 .. M-1 padded with +0.0 to N = the smallest power of two >= M, T(k+1)[i] = Tk[2i] + Tk[2i+1].  The
-// terms are signed, so (as in pft_spread.hip) a step is taken only while its span lies inside N: above the root nothing is
-// added, and the bits depend on neither the workgroup size nor the grid.
+// The tree (pft_pair_tree.h): positions 0 .. M-1 padded with +0.0.  The terms are signed, so every level is the gated form.
 #include "pft_device_utils.h"
 #include "pft_match_search.h"
+#include "pft_pair_tree.h"
 #include "pft_refine_solve.h"
 
 #define RF_THREADS 256
 #define RF_WAVES (RF_THREADS / 64)
-#define RF_MAX_LEVELS 32
 
 struct PftRefineCtl {
   PftRefineState s;   // the state behind T (unchanged by a zero step)
@@ -31,8 +29,6 @@ struct PftRefineCtl {
   uint32_t decided;   // the status is known, the next pass is the one that scores the final T
   uint32_t iterations, passes, status;
 };
-
-__device__ __forceinline__ uint32_t rf_pow2_ceil(uint32_t n) { return n <= 1u ? 1u : 1u << (32 - __clz((int)(n - 1u))); }
 
 __global__ void k_refine_init(PftRefineArgs a, PftRefineDev r, const PftHeader* __restrict__ hdr, float* __restrict__ mats) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -65,41 +61,11 @@ __global__ void k_refine_init(PftRefineArgs a, PftRefineDev r, const PftHeader* 
   }
 }
 
-// the lane -> wave -> workgroup levels: v holds one value per lane of `unit` positions each; npad = the padded size in
-// positions.  The workgroup's roots arrive in lanes 0 .. PFT_REFINE_SUMS-1 (return value; other lanes: unspecified)
-__device__ __forceinline__ double rf_block_tree(double (&v)[PFT_REFINE_SUMS], uint32_t unit, uint32_t npad,
-                                                double (*sh)[PFT_REFINE_SUMS]) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  // lanes 2i and 2i+1 hold the two halves; both form left + right (addition commutes bit for bit)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const bool take = unit * (uint32_t)o < npad;
-#pragma unroll
-    for (int q = 0; q < PFT_REFINE_SUMS; q++) {
-      const double t = v[q] + __shfl_xor(v[q], o);
-      v[q] = take ? t : v[q];
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < PFT_REFINE_SUMS; q++) sh[wave][q] = v[q];
-  }
-  __syncthreads();
-  double root = 0.0;
-  if (tid < PFT_REFINE_SUMS) {
-    double w[RF_WAVES];
-#pragma unroll
-    for (int q = 0; q < RF_WAVES; q++) w[q] = sh[q][tid];
-#pragma unroll
-    for (int h = 1; h < RF_WAVES; h <<= 1) {
-      const bool take = unit * (uint32_t)(64 * h) < npad;
-#pragma unroll
-      for (int q = 0; q + h < RF_WAVES; q += 2 * h) w[q] = take ? w[q] + w[q + h] : w[q];
-    }
-    root = w[0];
-  }
-  __syncthreads();
-  return root;
+// the lane -> wave -> workgroup levels: v holds one value per lane; npad = the padded size in positions.  The workgroup's
+// roots arrive in lanes 0 .. PFT_REFINE_SUMS-1
+__device__ __forceinline__ double rf_block_tree(double (&v)[PFT_REFINE_SUMS], uint32_t npad, double (*sh)[PFT_REFINE_SUMS]) {
+  pt_wave<true>(v, 1u, npad);
+  return pt_waves<true, RF_WAVES>(v, sh, 1u, npad);
 }
 
 __global__ void __launch_bounds__(RF_THREADS) k_refine_pairs(PftParams prm, PftDev d, PftRefineDev r, double pair2, double inl2) {
@@ -116,14 +82,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_pairs(PftParams prm, PftD
   for (int k = 0; k < 12; k++) T[k] = ctl->T[k];
   const double c0 = (double)T[3], c1 = (double)T[7], c2 = (double)T[11];
 
-  const int D = hdr->depth;
-  const uint32_t n_words = hdr->n_words;
-  // a failed crop or build (PftHeader::error), an empty crop or a tree that was never built: nothing pairs
-  const uint32_t n_crop =
-      (hdr->error != 0u || D <= 0 || D > PFT_MAX_DEPTH || n_words == 0u || n_words > d.max_words) ? 0u : hdr->n_crop;
-  const bool indirect = hdr->leaf_indirect != 0;
-  const double omin[3] = {hdr->omin[0], hdr->omin[1], hdr->omin[2]};
-  const double res = prm.res;
+  const MtTree tree = mt_load_tree(hdr, d, prm);
 
   double v[PFT_REFINE_SUMS];
 #pragma unroll
@@ -134,45 +93,10 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_pairs(PftParams prm, PftD
     const float4 p = d.ref_xyz[j];
     float qx, qy, qz;
     xform(T, p.x, p.y, p.z, qx, qy, qz);
-    float bd = INFINITY;
-    bool found = false;
-    float4 bt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (n_crop != 0u) {
-      uint32_t node = 0u, kx = 0u, ky = 0u, kz = 0u;
-      bool ok = true;
-      for (int lvl = 0; lvl < D; lvl++) {
-        const uint32_t wv = d.words[node];
-        const uint32_t mask = wv & 0xffu, base = wv >> 8;
-        const double vs = res * (double)(1u << (D - lvl - 1));
-        const uint32_t bc = mt_min_child(mask, vs, omin, kx, ky, kz, qx, qy, qz);
-        node = base + __popc(mask & ((1u << (bc & 7u)) - 1u));
-        // (a node without children, or a child index past the words: no partner instead of a read out of bounds)
-        ok = ok && bc != 0xffu && node + 1u < n_words;
-        if (!ok) break;
-        // U10: the key handed down is the chosen (minimum) child's, as in k_match
-        kx = 2u * kx + ((bc >> 2) & 1u);
-        ky = 2u * ky + ((bc >> 1) & 1u);
-        kz = 2u * kz + (bc & 1u);
-      }
-      if (ok) {
-        const uint32_t ls = d.words[node], le = min(d.words[node + 1u], n_crop);
-        // leaf scan in float: the first strictly smaller candidate wins (insertion order)
-        for (uint32_t pos = ls; pos < le; pos++) {
-          float4 c;
-          if (indirect)
-            c = d.crop_pts[min(d.leaf_order[pos], n_crop - 1u)];
-          else
-            c = d.leaf_pts[pos];
-          const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
-          const float dd = dx * dx + (dy * dy + dz * dz);
-          if (dd < bd) {
-            bd = dd;
-            found = true;
-            bt = c;
-          }
-        }
-      }
-    }
+    float bd;
+    float4 bt;
+    uint32_t pos;
+    const bool found = mt_search(tree, d, qx, qy, qz, bd, bt, pos);
     if (found && (double)bd < pair2) {
       const double a[3] = {(double)qx - c0, (double)qy - c1, (double)qz - c2};
       const double b[3] = {(double)bt.x - c0, (double)bt.y - c1, (double)bt.z - c2};
@@ -196,7 +120,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_pairs(PftParams prm, PftD
     sh_n[wave][0] = np;
     sh_n[wave][1] = ni;
   }
-  const double root = rf_block_tree(v, 1u, rf_pow2_ceil(M), sh);  // (its barriers also publish sh_n)
+  const double root = rf_block_tree(v, pt_pow2_ceil(M), sh);  // (its barrier also publishes sh_n)
   if (tid < PFT_REFINE_SUMS) r.part[(size_t)tid * r.g_cap + g] = root;
   if (tid == 64) {
     uint32_t a = 0u, b = 0u;
@@ -211,14 +135,14 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_pairs(PftParams prm, PftD
 
 __global__ void __launch_bounds__(RF_THREADS) k_refine_step(PftDev d, PftRefineDev r, PftRefineArgs a, uint32_t M) {
   __shared__ double sh[RF_WAVES][PFT_REFINE_SUMS];
-  __shared__ double stk[RF_MAX_LEVELS][PFT_REFINE_SUMS];
+  __shared__ double stk[PT_MAX_LEVELS][PFT_REFINE_SUMS];
   __shared__ double sums[PFT_REFINE_SUMS];
   __shared__ uint32_t sh_n[RF_WAVES][2];
   PftRefineCtl* ctl = r.ctl;
   if (ctl->done != 0u) return;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t G = min((M + RF_THREADS - 1u) / RF_THREADS, r.g_cap);  // blocks k_refine_pairs wrote
-  const uint32_t NG = rf_pow2_ceil(G);                                   // blocks of the padded tree
+  const uint32_t NG = pt_pow2_ceil(G);                                   // blocks of the padded tree
   // the grid level: chunks of 256 block roots (one per lane; beyond G the padding), the chunks by a binary counter
   const uint32_t n_chunks = (NG + RF_THREADS - 1u) / RF_THREADS;
   uint32_t my_pairs = 0u, my_inliers = 0u;
@@ -231,13 +155,12 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_step(PftDev d, PftRefineD
       my_pairs += r.part_n[2u * g];
       my_inliers += r.part_n[2u * g + 1u];
     }
-    double root = rf_block_tree(v, 1u, NG, sh);
-    if (tid < PFT_REFINE_SUMS) {  // chunk ch merges the pending subtrees its trailing one bits name (all inside NG)
-      uint32_t l = 0;
-      for (uint32_t b = ch; b & 1u; b >>= 1, l++) root = stk[l][tid] + root;
-      stk[l][tid] = root;
+    double root = rf_block_tree(v, NG, sh);
+    if (tid < PFT_REFINE_SUMS) {
+      root = pt_push(stk, ch, root);
       if (ch + 1u == n_chunks) sums[tid] = root;  // (n_chunks is a power of two: the last merge is the root)
     }
+    __syncthreads();  // (sh is written again by the next chunk)
   }
   my_pairs = wave_sum(my_pairs);
   my_inliers = wave_sum(my_inliers);

@@ -13,16 +13,15 @@
 // in LDS; the transform is 9 multiplies and adds).
 //
 // Summation order (pft_config::sum_order):
-//   PFT_SUM_TREE  adjacent-pair trees over the index range padded with -0.0 (the exact additive identity) to a power of
-//                 two: a thread's 8 consecutive points (registers), the wave (xor 1 .. 32), the 16 waves (LDS), then the
-//                 8192-point tiles (a binary counter in LDS).  Every level is a subtree of the one tree, so the bits do
-//                 not depend on the launch shape.
+//   PFT_SUM_TREE  adjacent-pair trees (pft_pair_tree.h, ungated) over the index range padded with -0.0 (the exact additive
+//                 identity): a thread's 8 consecutive points (registers), the wave, the 16 waves, then the 8192-point tiles.
 //   PFT_SUM_PCL   index-order float chains from +0.0 (PCL's loops): 1024-point tiles are staged in LDS by all threads,
 //                 then one lane per sum runs its chain over the tile.
 // Min / max are index-ordered with ties to the later point (SSE minps / maxps as getMinMax3D runs them) in both orders.
 #include <float.h>
 
 #include "pft_device_utils.h"
+#include "pft_pair_tree.h"
 #include "pft_report_solve.h"
 
 #define RP_THREADS 1024
@@ -32,14 +31,13 @@
 #define RP_TILE (RP_THREADS * RP_PER_THREAD)  // points per tree tile (an aligned subtree of 8192)
 #define RP_SEQ_TILE RP_THREADS                // points per LDS tile of the PCL-order chains
 #define RP_SEQ_STRIDE (RP_SEQ_TILE + 1)       // one word of padding: the chain lanes read different banks
-#define RP_MAX_LEVELS 32
 
 struct RpSh {
   float T[12];     // the transform used (row-major 3x4)
   float P[12];     // p2w (row-major 3x4)
   float c[3];      // centroid
   float part[RP_WAVES][6];            // per-wave partial sums / minima / maxima
-  float stk[RP_MAX_LEVELS][6];        // tile-level binary counter (tree order)
+  float stk[PT_MAX_LEVELS][6];        // tile-level binary counter (tree order)
   float acc[6];                       // running results (tile sums, chains, min / max)
   float seq[6][RP_SEQ_STRIDE];        // PCL order: the staged terms of one tile
 };
@@ -63,7 +61,7 @@ __device__ __forceinline__ float rp_max(float lo, float hi) { return lo > hi ? l
 // ---- tree order: K sums of term(i, v[K]) over [0, n); the result lands in sh.acc[0 .. K) ----
 template <int K, class Term>
 __device__ void rp_tree_sums(RpSh& sh, uint32_t n, Term term) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t tid = threadIdx.x;
   const uint32_t n_tiles = (n + RP_TILE - 1) / RP_TILE;
   for (uint32_t tile = 0; tile < n_tiles; tile++) {
     const uint32_t base = tile * RP_TILE + tid * RP_PER_THREAD;
@@ -88,43 +86,13 @@ __device__ void rp_tree_sums(RpSh& sh, uint32_t n, Term term) {
     }
     float s[K];
 #pragma unroll
-    for (int j = 0; j < K; j++) {
-      s[j] = stk[RP_PT_LEVELS - 1][j];
-      // lanes 2i and 2i+1 hold the two halves; both form left + right (float addition commutes bit for bit)
-      for (int o = 1; o < 64; o <<= 1) s[j] = s[j] + __shfl_xor(s[j], o);
-    }
-    if (lane == 0)
-#pragma unroll
-      for (int j = 0; j < K; j++) sh.part[wave][j] = s[j];
-    __syncthreads();
-    if (tid < (uint32_t)K) {
-      float w[RP_WAVES];
-#pragma unroll
-      for (int q = 0; q < RP_WAVES; q++) w[q] = sh.part[q][tid];
-#pragma unroll
-      for (int h = RP_WAVES / 2; h >= 1; h >>= 1)
-#pragma unroll
-        for (int q = 0; q < h; q++) w[q] = w[2 * q] + w[2 * q + 1];
-      // tiles: binary counter (tile t merges the pending subtrees its trailing one bits name)
-      float v = w[0];
-      uint32_t l = 0;
-      for (uint32_t b = tile; b & 1u; b >>= 1, l++) v = sh.stk[l][tid] + v;
-      sh.stk[l][tid] = v;
-    }
+    for (int j = 0; j < K; j++) s[j] = stk[RP_PT_LEVELS - 1][j];
+    pt_wave<false>(s);
+    const float root = pt_waves<false, RP_WAVES>(s, sh.part);
+    if (tid < (uint32_t)K) pt_push(sh.stk, tile, root);
     __syncthreads();
   }
-  if (tid < (uint32_t)K) {
-    // the pending subtrees, from the smallest (rightmost) up: padding with -0.0 adds nothing, so the padded tree's root
-    // is the right-to-left fold of what the counter holds
-    float v = 0.0f;
-    bool any = false;
-    for (uint32_t l = 0; l < RP_MAX_LEVELS; l++)
-      if ((n_tiles >> l) & 1u) {
-        v = any ? sh.stk[l][tid] + v : sh.stk[l][tid];
-        any = true;
-      }
-    sh.acc[tid] = v;
-  }
+  if (tid < (uint32_t)K) sh.acc[tid] = pt_fold(sh.stk, n_tiles);
   __syncthreads();
 }
 

@@ -9,18 +9,16 @@
 //   k_spread_final     one workgroup: the grid level of the same tree over the blocks' roots (4 or 16 blocks per lane, the
 //                      wave, the waves), the integers, then pft_spread_final.h in one lane
 //
-// The tree: positions 0 .. n-1 padded with +0.0 to N = the smallest power of two >= n, T(k+1)[i] = Tk[2i] + Tk[2i+1].  Every
-// level here is an aligned subtree of it.  A step is taken only while its span lies inside N ("o < N"): above the root
-// nothing is added, so the sign of a -0.0 root (all weights zero, all offsets negative) survives as in the definition.
-// Blocks wholly beyond n are not read and not written; the final launch takes them as +0.0.
+// The tree (pft_pair_tree.h): positions 0 .. n-1 padded with +0.0.  The terms are signed, so every level is the gated form:
+// the sign of a -0.0 root (all weights zero, all offsets negative) survives as in the definition.  Blocks wholly beyond n
+// are not read and not written; the final launch takes them as +0.0.
 #include "pft_device_utils.h"
+#include "pft_pair_tree.h"
 #include "pft_spread_final.h"
 
 #define SP_BLOCK 256                 // particles per workgroup of k_spread_partial (a power of two, one per lane)
 #define SP_WAVES (SP_BLOCK / 64)
 #define SP_FINAL_MAX 256             // lanes of k_spread_final: 16 blocks each cover PFT_MAX_PARTICLES / SP_BLOCK = 4096
-
-__device__ __forceinline__ uint32_t sp_pow2_ceil(uint32_t n) { return n <= 1u ? 1u : 1u << (32 - __clz((int)(n - 1u))); }
 
 __device__ __forceinline__ uint32_t sp_count(const PftDev& d, uint32_t n_arg) {
   // (a KLD handle's count lives on the device; never beyond what the launch was sized for)
@@ -46,7 +44,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spread_partial(PftDev d, uint32_t 
   if (d.hdr->error != 0u) return;  // a failed iteration is not evaluated (k_spread_final says so)
   const uint32_t n = sp_count(d, n_arg);
   if (g >= g_cap || g * SP_BLOCK >= n) return;  // (uniform: a block wholly beyond the population)
-  const uint32_t N = sp_pow2_ceil(n);
+  const uint32_t N = pt_pow2_ceil(n);
   const uint32_t i = g * SP_BLOCK + tid;
 
   double v[PFT_SPREAD_SUMS];
@@ -80,39 +78,21 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spread_partial(PftDev d, uint32_t 
     wmax = b.w;
     imax = i;
   }
-  // the wave: lanes 2i and 2i+1 hold the two halves; both form left + right (addition commutes bit for bit)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const bool take = (uint32_t)o < N;
-#pragma unroll
-    for (int q = 0; q < PFT_SPREAD_SUMS; q++) {
-      const double t = v[q] + __shfl_xor(v[q], o);
-      v[q] = take ? t : v[q];
-    }
+  pt_wave<true>(v, 1u, N);
+  for (int o = 1; o < 64; o <<= 1) {  // the first maximum of the wave
     const float ow = __shfl_xor(wmax, o);
     const uint32_t oi = __shfl_xor(imax, o);
     sp_max_merge(wmax, imax, ow, oi);
   }
   zero = wave_sum(zero);
   if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < PFT_SPREAD_SUMS; q++) sh[wave][q] = v[q];
     sh_zero[wave] = zero;
     sh_wmax[wave] = wmax;
     sh_imax[wave] = imax;
   }
-  __syncthreads();
-  if (tid < PFT_SPREAD_SUMS) {  // the waves of the block
-    double w[SP_WAVES];
-#pragma unroll
-    for (int q = 0; q < SP_WAVES; q++) w[q] = sh[q][tid];
-#pragma unroll
-    for (int h = 1; h < SP_WAVES; h <<= 1) {
-      const bool take = (uint32_t)(64 * h) < N;
-#pragma unroll
-      for (int q = 0; q + h < SP_WAVES; q += 2 * h) w[q] = take ? w[q] + w[q + h] : w[q];
-    }
-    part[(size_t)tid * g_cap + g] = w[0];
+  const double root = pt_waves<true, SP_WAVES>(v, sh, 1u, N);  // (its barrier also publishes the integers and the maxima)
+  if (tid < PFT_SPREAD_SUMS) {
+    part[(size_t)tid * g_cap + g] = root;
   } else if (tid == 64) {
     uint32_t z = 0u, bi = 0xffffffffu;
     float bw = -INFINITY;
@@ -134,7 +114,7 @@ __global__ void __launch_bounds__(SP_FINAL_MAX) k_spread_final(PftDev d, uint32_
                                                                const uint32_t* __restrict__ part_imax, double max_pos_sigma,
                                                                double min_n_eff, uint32_t after,
                                                                pft_population_stats* __restrict__ out) {
-  __shared__ double sh[PFT_SPREAD_SUMS][SP_FINAL_MAX / 64];
+  __shared__ double sh[SP_FINAL_MAX / 64][PFT_SPREAD_SUMS];
   __shared__ double sums[PFT_SPREAD_SUMS];
   __shared__ uint32_t sh_zero[SP_FINAL_MAX / 64], sh_imax[SP_FINAL_MAX / 64];
   __shared__ float sh_wmax[SP_FINAL_MAX / 64];
@@ -148,7 +128,7 @@ __global__ void __launch_bounds__(SP_FINAL_MAX) k_spread_final(PftDev d, uint32_
   }
   const uint32_t n = sp_count(d, n_arg);
   const uint32_t G = min((n + SP_BLOCK - 1u) / SP_BLOCK, g_cap);  // blocks k_spread_partial wrote
-  const uint32_t NG = sp_pow2_ceil(G);                           // blocks of the padded tree (1 when n <= SP_BLOCK)
+  const uint32_t NG = pt_pow2_ceil(G);                           // blocks of the padded tree (1 when n <= SP_BLOCK)
   // the grid level: B blocks per lane, the wave, the waves -- positions beyond G are the padding.  The loop over the sums
   // is unrolled so that the loads of several sums are in flight together: a few memory latencies, not 29
   const uint32_t g0 = (uint32_t)B * tid;
@@ -173,29 +153,16 @@ __global__ void __launch_bounds__(SP_FINAL_MAX) k_spread_final(PftDev d, uint32_
 #pragma unroll
       for (int q = 0; q < PFT_SPREAD_SUMS; q++) v[q] = lane_root(q);
     }
-    if (NG > (uint32_t)B) {  // (uniform)
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const bool take = (uint32_t)(B * o) < NG;
-#pragma unroll
-        for (int q = 0; q < PFT_SPREAD_SUMS; q++) {
-          const double t = v[q] + __shfl_xor(v[q], o);
-          v[q] = take ? t : v[q];
-        }
-      }
-    }
+    if (NG > (uint32_t)B) pt_wave<true>(v, (uint32_t)B, NG);  // (uniform)
     if (lane == 0) {
 #pragma unroll
-      for (int q = 0; q < PFT_SPREAD_SUMS; q++) sh[q][wave] = v[q];
+      for (int q = 0; q < PFT_SPREAD_SUMS; q++) sh[wave][q] = v[q];
     }
   } else {  // above 262 144 particles: one sum at a time (29 x 16 roots per lane do not fit the registers)
     for (int q = 0; q < PFT_SPREAD_SUMS; q++) {
-      double v = g0 < G ? lane_root(q) : 0.0;
-      for (int o = 1; o < 64; o <<= 1) {
-        const double t = v + __shfl_xor(v, o);
-        v = (uint32_t)(B * o) < NG ? t : v;
-      }
-      if (lane == 0) sh[q][wave] = v;
+      double v[1] = {g0 < G ? lane_root(q) : 0.0};
+      pt_wave<true>(v, (uint32_t)B, NG);
+      if (lane == 0) sh[wave][q] = v[0];
     }
   }
   uint32_t zero = 0u, imax = 0xffffffffu;
@@ -216,14 +183,7 @@ __global__ void __launch_bounds__(SP_FINAL_MAX) k_spread_final(PftDev d, uint32_
     sh_imax[wave] = imax;
   }
   __syncthreads();
-  if (tid < PFT_SPREAD_SUMS) {  // the waves: 64 B blocks each
-    for (uint32_t h = 1; h < nw; h <<= 1) {
-      const bool take = 64u * (uint32_t)B * h < NG;
-      for (uint32_t q = 0; q + h < nw; q += 2u * h)
-        if (take) sh[tid][q] = sh[tid][q] + sh[tid][q + h];
-    }
-    sums[tid] = sh[tid][0];
-  }
+  if (tid < PFT_SPREAD_SUMS) sums[tid] = pt_waves_root<true, SP_FINAL_MAX / 64>(sh, (uint32_t)B, NG, nw);  // 64 B blocks each
   __syncthreads();
   if (tid == 0) {
     uint32_t z = 0u, bi = 0xffffffffu;

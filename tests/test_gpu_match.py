@@ -143,6 +143,8 @@ VARIANTS = {
     "kld": dict(kld=True),
     "M1": dict(M=1),
     "M1025": dict(M=1025),  # a one-point tail round
+    "M2049": dict(M=2049),  # three 1024-position tiles: the fold joins two pending subtrees (levels 1 and 0)
+    "M3073": dict(M=3073),  # four tiles: the push at tile 3 merges two levels
     "half_object": dict(half=True),  # some pairs outside the gate
 }
 

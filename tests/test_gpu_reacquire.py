@@ -96,6 +96,9 @@ VARIANTS = {
     "leaf_indirect": dict(env={"PFT_LEAF_INDIRECT": "1"}),
     "M1": dict(M=1),
     "M513": dict(M=513),  # two tiles of the 256-thread workgroup and a one-point third
+    "M769": dict(M=769),  # four 256-position tiles: the push at tile 3 merges two levels
+    "M1153": dict(M=1153),  # five tiles: the fold joins levels 2 and 0 across the empty level 1
+    "M1281": dict(M=1281),  # six tiles (five and a one-point sixth): the fold joins levels 2 and 1
     "K1": dict(one=True),
     "kld": dict(kld=True),
 }

@@ -135,6 +135,25 @@ def test_on_a_tree_deeper_than_ten_levels(gpu, orc):
     t.close()
 
 
+def test_pass_zero_has_the_bits_of_the_match_of_the_same_pose(gpu):
+    """the scattered scene of test_gpu_reacquire's test_same_bits_as_the_match_of_the_same_pose: both crops are the whole
+    cloud, so pass 0 from the result pose pairs what pft_match matched -- one search -- and its gated tree over signed
+    terms gives the bits of pft_match's ungated tree over the same non-negative terms at the same positions"""
+    ref, cloud = tgm.scattered(1200, 10.0, 1)
+    t = tgm.make(gpu, reference=ref, trans=np.eye(4, dtype=np.float32))
+    tgm.step(t, cloud)
+    st = t.getMatch()
+    res = t.refine(start=None, pair_distance=float(t._cfg.max_distance), apply=False)
+    tr = t.getRefineTrace()
+    print("match %d / %.17g, refine pass 0 %d / %.17g" % (st.n_matched, st.sum_sq_dist, res.n_pairs_before, tr["sums"][0][15]))
+    assert st.evaluated and st.n_crop == len(cloud) == res.n_crop, "precondition: both crops are the whole cloud"
+    assert tr["transform"][0].tobytes() == st.transform.tobytes(), "precondition: the same pose"
+    assert st.n_matched > 200, "precondition"
+    assert res.n_pairs_before == st.n_matched
+    assert rfm.bits(np.float64(tr["sums"][0][15])) == rfm.bits(np.float64(st.sum_sq_dist))
+    t.close()
+
+
 # ---- 2. a fixed point ----------------------------------------------------------------------------------------------------
 def test_a_fixed_point(gpu, orc):
     """the frame is the model moved by T0 and the start is T0: every pair has distance 0, a == b, the step is exactly zero"""

@@ -130,6 +130,9 @@ def test_match_source_is_part_of_the_build():
     from pcl_tracking_amd import build
 
     assert "pft_match.hip" in build.SOURCES
+    assert "pft_match_search.h" in build.HEADERS and "pft_pair_tree.h" in build.HEADERS
+    for h in ("pft_match_search.h", "pft_pair_tree.h"):
+        assert os.path.exists(os.path.join(build.CSRC, h))
     assert os.path.exists(os.path.join(build.CSRC, "pft_match.hip"))
     internal = open(os.path.join(build.CSRC, "pft_internal.h")).read()
     assert re.search(r"\bvoid pftk_match\(", internal)
