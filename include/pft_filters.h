@@ -59,12 +59,14 @@ int pft_filter_apply_device(pft_filter* f, const pft_point_xyzrgba* device_point
  * without waiting for it.  The host cloud may be reused as soon as the call returns (its upload is the one thing waited
  * for); the device cloud is borrowed until the apply has finished on the device.  The accessors below wait for a pending
  * apply the first time one of them is called after it; pft_set_input_from_filter (pft.h) hands the output to a tracker
- * without any wait.  A VoxelGrid leaf too small for the cloud hands the input through, decided on the device.  n == 0
- * is the empty result, on the host, at once. */
+ * without any wait.  A VoxelGrid leaf too small for the cloud hands the grid's input through (the whole cloud, or what
+ * an enabled PassThrough kept of it), decided on the device.  n == 0 is the empty result, on the host, at once. */
 int pft_filter_apply_async(pft_filter* f, const pft_point_xyzrgba* host_points, size_t n);
 int pft_filter_apply_device_async(pft_filter* f, const pft_point_xyzrgba* device_points, size_t n);
 
-/* n_pass: points that survived PassThrough (all finite-or-not points when it is disabled);
+/* n_pass: points that entered the grid = points that survived PassThrough.  With PassThrough disabled:
+ * ApproximateVoxelGrid takes every point, finite or not (n_pass = n); VoxelGrid skips the non-finite points, so n_pass
+ * counts the finite ones and pft_filter_get_pass_indices lists them.
  * n_out: points of the output cloud */
 int pft_filter_counts(const pft_filter* f, size_t* n_pass, size_t* n_out);
 int pft_filter_output_device(const pft_filter* f, const pft_point_xyzrgba** device_points, size_t* n_out);

@@ -173,7 +173,10 @@ __global__ __launch_bounds__(F_THREADS) void k_f_keys_exact(FParams p, FDev d) {
   const uint32_t i = blockIdx.x * F_THREADS + threadIdx.x;
   if (i >= p.n || !d.passf[i]) return;
   const FHdr* h = d.hdr;
-  if (h->leaf_too_small) return;
+  if (h->leaf_too_small) {  // the grid's input is handed through: one key, so that the stable sort compacts the kept points
+    d.key[0][i] = 0u;
+    return;
+  }
   const float4 q = *reinterpret_cast<const float4*>(d.in + i);
   const int i0 = (int)(floorf(q.x * p.inv[0]) - (float)h->minb[0]);
   const int i1 = (int)(floorf(q.y * p.inv[1]) - (float)h->minb[1]);
@@ -318,7 +321,8 @@ __global__ __launch_bounds__(1024) void k_f_scan_small(FParams p, FDev d, uint32
   uint32_t n_out = n_pass, n_trig = 0, n_present = 0;
   if (p.mode == PFT_VOXEL_EXACT) {
     n_out = scan_array(d.tile_head, ntiles, scr);
-    if (d.hdr->leaf_too_small) n_out = p.n;  // the input is handed through (k_f_emit_exact copies it)
+    // the grid's input is handed through (k_f_emit_exact copies it): what PassThrough kept, or the whole cloud
+    if (d.hdr->leaf_too_small) n_out = p.pass_enable ? n_pass : p.n;
   }
   if (threadIdx.x == 0) {
     d.hdr->n_pass = n_pass;
@@ -762,11 +766,13 @@ __global__ __launch_bounds__(FE_THREADS) void k_f_emit_exact(FParams p, FDev d, 
   const uint32_t nv = d.hdr->n_pass;
   if (d.hdr->leaf_too_small) {
     // PCL warns "Leaf size is too small for the input dataset" and hands the input cloud through unchanged: decided
-    // here, on the device, so that an apply nobody waits for ends with the same output and count
+    // here, on the device, so that an apply nobody waits for ends with the same output and count.  Behind a
+    // PassThrough the grid's input is what that kept: sorted position j < n_pass holds input index sval[j], in order
+    // (k_f_keys_exact gave the kept points one key)
     for (uint32_t k = 0; k < FE_TILE / FE_THREADS; k++) {
       const uint32_t i = base + k * FE_THREADS + tid;
-      if (i < p.n) {
-        const float4* q = reinterpret_cast<const float4*>(d.in + i);
+      if (i < (p.pass_enable ? nv : p.n)) {
+        const float4* q = reinterpret_cast<const float4*>(d.in + (p.pass_enable ? sval[i] : i));
         float4* o = reinterpret_cast<float4*>(d.out + i);
         o[0] = q[0];
         o[1] = q[1];

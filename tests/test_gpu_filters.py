@@ -1,7 +1,12 @@
 """GPU parity tests of the input filters (include/pft_filters.h) against the CPU oracle, through the C ABI:
-PassThrough, ApproximateVoxelGrid (history-table flush order included) and VoxelGrid outputs are compared
-BIT FOR BIT (x, y, z, data[3], rgba, padding; point order; counts) -- the device pipeline sums every voxel
-in arrival order like the sequential algorithm, so there is no tolerance anywhere in this file.
+PassThrough, ApproximateVoxelGrid and VoxelGrid outputs are compared BIT FOR BIT (x, y, z, data[3], rgba,
+padding; point order; counts) -- the device pipeline sums every voxel in arrival order like the sequential
+algorithm, so there is no tolerance anywhere in this file.
+This file holds the ordinary clouds: the depth frame, uniform clouds of ragged sizes (a voxel holds a point or
+two), consecutive runs in the approximate grid at table sizes 64, 512, 1024 and 2048.  The edges -- long voxels
+and a shuffled input in VoxelGrid, cell faces, cell indices past 2^24, the INT32_MAX cell limit, infinite
+coordinates, PassThrough limits hit exactly, every table size, PassThrough fused with either grid, handle reuse --
+are in tests/test_gpu_filters_edges.py.
 PARITY UNPINNED: the oracle restates PCL 1.8.0, which is not available here (oracle/pft_oracle.h)."""
 import numpy as np
 import pytest
