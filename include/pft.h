@@ -553,9 +553,16 @@ int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4]);
 /* the ancestor table of the fast descent for the last tree built: info10 = {usable (filled for this tree), level L,
  * window first cell x, y, z, log2 of the window's cells bx, by, bz (level-L cells), tree build epoch, epoch the table was
  * filled for}; table (nullable) receives min(cap, 2^(bx+by+bz)) entries, entry [x | y << bx | z << (bx + by)] =
- * (a << 27) | node: node is the deepest existing ancestor of window cell (x, y, z) at a level a <= L.
+ * (a << 27) | node: node is the deepest existing ancestor of window cell (x, y, z) at a level a <= L; L is the tree's
+ * depth - 1 or depth - 2 (pft_debug_get_ancestor_level).
  * PFT_ANCESTOR_TABLE=0 at pft_create: no table, info10[0] = info10[1] = 0 */
 int pft_debug_get_ancestor_table(pft_tracker* t, uint32_t info10[10], uint32_t* table, size_t cap);
+/* the level of the ancestor table, chosen per build (synchronises the stream): out5 = {the pinned status word of the last
+ * build -- 0x80000000 | log2 cells of the window at depth - 1 | the same at depth - 2 << 8, 0xff: no window --, the level
+ * the last build was asked for as depth - out5[1] (0: no table; 0xffffffff: no build yet), the ANC_UP of the last
+ * likelihood instance launched, how often the request changed from one build to the next, graph instantiations of a
+ * PFT_GRAPH=1 handle}.  PFT_ANC_UP_FORCE=0|1|2 at pft_create fixes the request */
+int pft_debug_get_ancestor_level(pft_tracker* t, uint32_t out5[5]);
 /* host-only (no device needed): the positions of the reference points the bounding box of the particles' transformed
  * clouds is taken over (A3: calcBoundingBox of the tracker that /root/reference/src/auto_tracking.cpp:691-693 runs) -- the
  * convex hull's vertices plus the shell the float evaluation can reach; `keep` has room for n indices (ascending),

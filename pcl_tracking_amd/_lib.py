@@ -219,6 +219,7 @@ SYMBOLS = [
     ("pft_debug_get_descent_stats", C.c_int, [_vp, _vp]),
     ("pft_debug_get_likelihood_layout", C.c_int, [_vp, _vp]),
     ("pft_debug_get_ancestor_table", C.c_int, [_vp, _vp, _vp, _sz]),
+    ("pft_debug_get_ancestor_level", C.c_int, [_vp, _vp]),
     ("pft_debug_get_hard_steps", C.c_int, [_vp, _vp]),
     ("pft_debug_aabb_support_subset", C.c_int, [_vp, C.c_size_t, _vp, _vp]),
     ("pft_debug_likelihood_occupancy", C.c_int, []),

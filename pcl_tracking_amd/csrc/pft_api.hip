@@ -202,6 +202,11 @@ struct pft_tracker {
   bool use_graph = false;
   hipGraphExec_t graph_exec = nullptr;
   uint32_t graph_frames = 0, graph_rebuilds = 0;
+  // ancestor table level: what the last build was asked for, the ANC_UP of the last likelihood instance
+  // launched, how often the request changed from one build to the next, and the instance the replayed graph holds
+  int anc_up_last = -1, lik_up_last = -1, graph_lik_up = -1;
+  uint32_t anc_up_changes = 0;
+  uint32_t anc_fit_streak = 0;  // consecutive builds whose look at the status word found a D - 1 window that fits
 
   // profiling
   bool prof = false;
@@ -603,6 +608,8 @@ PftSwitches pft_read_switches() {
   w.crop_two_pass = on("PFT_CROP_TWO_PASS");
   w.generic_descent = is1("PFT_GENERIC_DESCENT");
   w.ancestor_table = !on("PFT_ANCESTOR_TABLE") || is1("PFT_ANCESTOR_TABLE");
+  w.anc_up_force = -1;
+  if (const char* u = getenv("PFT_ANC_UP_FORCE")) w.anc_up_force = (u[0] >= '0' && u[0] <= '2' && !u[1]) ? u[0] - '0' : -1;
   w.exact_path = on("PFT_EXACT_SHELLS_ONLY") ? PftExactPath::shells : on("PFT_EXACT_PER_QUERY") ? PftExactPath::per_query : PftExactPath::sorted;
 #ifdef PFT_DIAG
   if (const char* a = getenv("PFT_ABLATE")) w.ablate = atoi(a);  // bit0 generic levels, bit1 leaf scan, bit2 coherence
@@ -726,7 +733,8 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
     A(dalloc(&t->d_kld_bins, (size_t)6 * p.kld_max));
   }
   A(hipHostMalloc(reinterpret_cast<void**>(&t->h_stat), 8 * sizeof(uint32_t), hipHostMallocMapped));
-  if (t->h_stat) for (int i = 0; i < 8; i++) t->h_stat[i] = 0;  // [0..3]: pft_debug_get_host_stat; [4]: exact-NN pool demand
+  // [0..3]: pft_debug_get_host_stat; [4]: exact-NN pool demand; [5]: ancestor table window sizes (pft_anc_window)
+  if (t->h_stat) for (int i = 0; i < 8; i++) t->h_stat[i] = 0;
   A(dalloc(&t->d_hdr, 1));
   A(dalloc(&t->d_dbg_hdr, 1));
   if (e == hipSuccess) e = hipMemsetAsync(t->d_hdr, 0, sizeof(PftHeader), t->stream);
@@ -1083,9 +1091,32 @@ static void stage_resample_aabb(pft_tracker* t, bool finalize) {
 // A4, A5, A6+A7
 __global__ void k_inject_error(PftHeader* hdr, uint32_t bits) { hdr->error |= bits; }
 
+// The ancestor table's level for the next build, depth - anc_up: 1 when the D - 1 window of the PREVIOUS
+// build fitted the table, else 2 when its D - 2 window did, else 0 -- read from the pinned status block without
+// synchronising, like the builder choice; a wrong guess costs time (the builder fills nothing when the window does not fit,
+// and the likelihood instance runs table-less on a tree whose table is not at its level, ~15 us dearer than either table),
+// never the result.  So D - 1 is asked for only after PFT_ANC_UP_CONFIRM builds in a row have seen a fitting D - 1 window:
+// a window that hovers at the cap (the free-running filter's does, from frame to frame) stays at D - 2.  Before the
+// first build's word has arrived: D - 2.  own_population false (pft_eval_weights): never D - 1 unless forced -- its
+// DEBUG_NN form has the level D - 2 code only, and the two forms of one evaluation walk the same table.
+#define PFT_ANC_UP_CONFIRM 8u
+static int pick_anc_up(pft_tracker* t, bool own_population, bool gather) {
+  // (gather false: the builder copies the few leaf records itself and no launch behind it fills a table)
+  if (!t->d_anc || !t->sw.ancestor_table || t->leaf_indirect || !gather) return 0;
+  if (t->sw.anc_up_force >= 0) return t->sw.anc_up_force;
+  const volatile uint32_t* hs = t->h_stat;
+  const uint32_t w = hs ? hs[5] : 0u;
+  if (!(w & 0x80000000u)) return 2;
+  if (own_population) {
+    t->anc_fit_streak = (w & 0xffu) <= PFT_ANC_CAP_BITS ? t->anc_fit_streak + 1u : 0u;
+    if (t->anc_fit_streak >= PFT_ANC_UP_CONFIRM) return 1;
+  }
+  return ((w >> 8) & 0xffu) <= PFT_ANC_CAP_BITS ? 2 : 0;
+}
+
 static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32_t np, bool debug_nn,
                                          bool bbox_from_partials, bool keep_point_keys = false,
-                                         bool likelihood = true) {
+                                         bool likelihood = true, bool own_population = true) {
   {
     ProfScope ps(t, PFT_K_CROP);
     if (++t->crop_epoch == 0) t->crop_epoch = 1;
@@ -1179,6 +1210,7 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
     pftk_likelihood_exact(t->stream, t->prm, dq, np, debug_nn, t->num_cus, t->sw.exact_path);
     return;
   }
+  int anc_up = 0;  // the ancestor table's level asked of this build (pick_anc_up), and the likelihood instance with it
   {
     ProfScope ps(t, PFT_K_OCTREE);
     PftDev db = d;
@@ -1212,14 +1244,17 @@ static void stage_crop_octree_likelihood(pft_tracker* t, const PftDev& d, uint32
       // there (5.4 us at 8 192 x 2 048), -3 us per build and one launch less here: pays below ~9 million queries (the
       // reference's own 400-500 particles: 0.202 -> 0.196 ms per frame)
       t->leaf_indirect = t->sw.leaf_indirect >= 0 ? t->sw.leaf_indirect == 1 : (unsigned long long)np * t->prm.M <= 8000000ull;
-      pftk_octree(t->stream, t->prm, db, last_n, t->leaf_indirect);
+      anc_up = pick_anc_up(t, own_population, last_n > PFT_GATHER_MIN);
+      pftk_octree(t->stream, t->prm, db, last_n, t->leaf_indirect, anc_up);
     }
+    if (t->anc_up_last >= 0 && anc_up != t->anc_up_last) t->anc_up_changes++;
+    t->anc_up_last = anc_up;
   }
   if (!likelihood) return;  // pft_reacquire: crop and tree only, its own kernel reads the tree
   {
     ProfScope ps(t, PFT_K_LIKELIHOOD);
     const int flags = (t->sw.generic_descent ? 0 : 1) | (t->sw.ancestor_table ? 2 : 0) | (t->sw.ablate << 8);
-    pftk_likelihood(t->stream, t->prm, d, np, debug_nn, t->num_cus, t->leaf_indirect, flags);
+    t->lik_up_last = pftk_likelihood(t->stream, t->prm, d, np, debug_nn, t->num_cus, t->leaf_indirect, flags, anc_up);
   }
 }
 
@@ -1261,12 +1296,15 @@ extern "C" int pft_compute(pft_tracker* t) {
   // arrays grow with np * M inside the stage) is never captured, and a capture that fails for any other reason -- a
   // builder or rescue kernel whose attribute is set on first use, say -- switches the handle back to direct launches
   // and runs THIS frame directly: the host-side state the recorded pass advanced is put back first.
+  int lik_sig = 0;  // the likelihood instances of this frame's iterations (ANC_UP + 1, two bits each)
   auto run_iterations = [&]() {
+    lik_sig = 0;
     for (int it = 0; it < t->cfg.iteration_num; it++) {
       stage_resample_aabb(t, false);
       // KLD variant: launches are sized for the capacity, the kernels take particle_num_ from PftHeader::p_active
       const uint32_t np = t->prm.kld ? t->Pcap : t->prm.P_local;
       stage_crop_octree_likelihood(t, t->dev, np, false, true);
+      lik_sig = ((lik_sig << 2) | (t->lik_up_last + 1)) & 0xffffff;
       if (t->inject_error & 16u) {  // test hook: a population barrier that timed out in some workgroup
         hipLaunchKernelGGL(k_inject_error, dim3(1), dim3(1), 0, t->stream, t->d_hdr, 16u);
         t->inject_error &= ~16u;
@@ -1300,6 +1338,13 @@ extern "C" int pft_compute(pft_tracker* t) {
     }
     if (ge == hipSuccess && g) {
       bool ready = false;
+      // another likelihood instance than the instantiated graph holds (the ancestor table's level changed): a change of
+      // the node sequence like the builder's -- instantiated anew, not updated in place
+      if (t->graph_exec && t->graph_lik_up != lik_sig) {
+        hipGraphExecDestroy(t->graph_exec);
+        t->graph_exec = nullptr;
+      }
+      t->graph_lik_up = lik_sig;
       if (t->graph_exec) {
         hipGraphNode_t bad = nullptr;
         hipGraphExecUpdateResult res;
@@ -1645,7 +1690,7 @@ extern "C" int pft_eval_weights(pft_tracker* t, const pft_particle* particles, s
   HIPCHK(t, hipMemsetAsync(t->d_hdr->dbg_hard, 0, sizeof(t->d_hdr->dbg_hard) + sizeof(t->d_hdr->lik_layout), t->stream));
   pftk_pose_to_matrix(t->stream, t->d_dbg_part, (uint32_t)P, t->d_mats);
   stage_aabb(t, d, (uint32_t)P, false);
-  stage_crop_octree_likelihood(t, d, (uint32_t)P, want_nn, true, true);
+  stage_crop_octree_likelihood(t, d, (uint32_t)P, want_nn, true, true, true, false);
   pftk_finalize_raw(t->stream, t->prm, d, (uint32_t)P, t->d_dbg_f, nullptr);
   if (raw_w) HIPCHK(t, hipMemcpyAsync(raw_w, t->d_dbg_f, P * sizeof(float), hipMemcpyDeviceToHost, t->stream));
   if (nn_idx) HIPCHK(t, hipMemcpyAsync(nn_idx, t->d_nn_idx, pairs * sizeof(int32_t), hipMemcpyDeviceToHost, t->stream));
@@ -1811,6 +1856,17 @@ extern "C" int pft_debug_get_likelihood_layout(pft_tracker* t, uint32_t out4[4])
   int r = read_hdr(t, &h);
   if (r != PFT_OK) return r;
   memcpy(out4, h.lik_layout, sizeof(h.lik_layout));
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_get_ancestor_level(pft_tracker* t, uint32_t out5[5]) {
+  if (!t || !out5 || !t->h_stat) return PFT_ERR_INVALID_ARG;
+  HIPCHK(t, hipStreamSynchronize(t->stream));  // (the builder's status word of the last build has arrived)
+  out5[0] = ((volatile uint32_t*)t->h_stat)[5];
+  out5[1] = (uint32_t)t->anc_up_last;
+  out5[2] = (uint32_t)t->lik_up_last;
+  out5[3] = t->anc_up_changes;
+  out5[4] = t->graph_rebuilds;
   return PFT_OK;
 }
 

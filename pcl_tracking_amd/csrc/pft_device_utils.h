@@ -240,33 +240,43 @@ __device__ __forceinline__ void xform(const float* T, float x, float y, float z,
 #include "pft_alias.h"
 
 // Window of the ancestor table (PftHeader::anc_*), written by the builders (one thread) for the tree of depth D and box
-// minimum mn: the level-L cells, L = D - PFT_ANC_UP, of the crop box by the likelihood kernel's key formula, rounded up to a
+// minimum mn: the level-L cells, L = D - anc_up, of the crop box by the likelihood kernel's key formula, rounded up to a
 // power of two per axis (the kernel's window test and index are shifts and ors) and kept inside the tree's box.  The window
-// only decides which queries may use the table (the others take the jump + loop); it does not decide any result.  No table
-// (anc_level 0) when `on` is false, the handle has no table buffer or the window holds more than PFT_ANC_CAP cells.  Every
-// build bumps build_epoch: a table filled for an earlier tree is not used.
-__device__ inline void pft_anc_window(PftHeader* hdr, const PftDev& d, int D, bool on, const double mn[3], double res) {
-  const int L = D - PFT_ANC_UP;
-  on = on && d.anc != nullptr && L >= 1;
+// only decides which queries may use the table (the others take the jump + loop); it does not decide any result.
+// anc_up is the host's request for this build (0: no table, 1: L = D - 1, 2: L = D - 2).  The window is formed in level
+// D - 2 cells; the D - 1 window is that window's eight children per cell -- whole parent cells, first cell even on every
+// axis: the fill derives the eight entries under a parent from one descent and stores x-adjacent pairs with 8-byte stores.
+// No table (anc_level 0) when `on` (a tree with centre tables) or `fill` (a launch behind the build fills it) is false or
+// anc_up is 0, the handle has no table buffer or the window at the requested level holds more than PFT_ANC_CAP cells.  The
+// window's log2 size at both levels goes to the pinned status block whoever fills (host_stat[5]: 0x80000000 | bits at
+// D - 1 | bits at D - 2 << 8, 0xff: no window at that level), from which the host picks the next build's level.  Every build
+// bumps build_epoch: a table filled for an earlier tree is not used.
+__device__ inline void pft_anc_window(PftHeader* hdr, const PftDev& d, int D, bool on, bool fill, const double mn[3],
+                                      double res, int anc_up) {
+  const int L2 = D - 2;  // (D == 2: the one level-0 cell, whose children are the level D - 1 window)
+  on = on && d.anc != nullptr && L2 >= 0;
   const float inv = (float)(1.0 / res);
   uint32_t lo[3] = {0u, 0u, 0u}, bits[3] = {0u, 0u, 0u};
   for (int a = 0; a < 3 && on; a++) {
     const float om = (float)mn[a];
     const float f0 = fmaxf(floorf((hdr->bbox[2 * a] - om) * inv), 0.0f);
     const float f1 = fmaxf(floorf((hdr->bbox[2 * a + 1] - om) * inv), 0.0f);
-    const uint32_t top = (1u << L) - 1u;
-    const uint32_t c0 = min(f0 < 2147483648.0f ? (uint32_t)f0 >> PFT_ANC_UP : top, top);
-    const uint32_t c1 = min(f1 < 2147483648.0f ? (uint32_t)f1 >> PFT_ANC_UP : top, top);
+    const uint32_t top = (1u << L2) - 1u;
+    const uint32_t c0 = min(f0 < 2147483648.0f ? (uint32_t)f0 >> 2 : top, top);
+    const uint32_t c1 = min(f1 < 2147483648.0f ? (uint32_t)f1 >> 2 : top, top);
     on = c1 >= c0;
     const uint32_t n = c1 - c0 + 1u;
-    bits[a] = n > 1u ? 32u - (uint32_t)__clz((int)(n - 1u)) : 0u;  // 2^bits >= n; <= L since n <= 2^L
-    lo[a] = min(c0, (1u << L) - (1u << bits[a]));
+    bits[a] = n > 1u ? 32u - (uint32_t)__clz((int)(n - 1u)) : 0u;  // 2^bits >= n; <= L2 since n <= 2^L2
+    lo[a] = min(c0, (1u << L2) - (1u << bits[a]));
   }
-  on = on && bits[0] + bits[1] + bits[2] <= PFT_ANC_CAP_BITS;
-  hdr->anc_level = on ? L : 0;
+  const uint32_t tb2 = bits[0] + bits[1] + bits[2], tb1 = tb2 + 3u;
+  if (d.host_stat) d.host_stat[5] = 0x80000000u | (on ? tb1 : 0xffu) | ((on && L2 >= 1 ? tb2 : 0xffu) << 8);
+  const bool deeper = anc_up == 1;
+  on = on && fill && (deeper ? tb1 <= PFT_ANC_CAP_BITS : (anc_up == 2 && L2 >= 1 && tb2 <= PFT_ANC_CAP_BITS));
+  hdr->anc_level = on ? D - anc_up : 0;
   for (int a = 0; a < 3; a++) {
-    hdr->anc_lo[a] = on ? lo[a] : 0u;
-    hdr->anc_bits[a] = on ? bits[a] : 0u;
+    hdr->anc_lo[a] = on ? (deeper ? 2u * lo[a] : lo[a]) : 0u;
+    hdr->anc_bits[a] = on ? (deeper ? bits[a] + 1u : bits[a]) : 0u;
   }
   hdr->build_epoch = hdr->build_epoch + 1u;
 }

@@ -30,9 +30,6 @@
 #define PFT_ANC_CAP_BITS 18      // ancestor table: log2 of the entries per handle (1 MiB); a larger window has no table
 #endif
 #define PFT_ANC_CAP (1u << PFT_ANC_CAP_BITS)
-#ifndef PFT_ANC_UP
-#define PFT_ANC_UP 2             // ancestor table level L = depth - PFT_ANC_UP (1 measured slower)
-#endif
 #define PFT_REF_CHUNK 256        // reference points per likelihood work item (upper limit; PftParams::ref_chunk)
 #ifndef PFT_BUILD_THREADS
 #define PFT_BUILD_THREADS 1024
@@ -50,6 +47,7 @@
 #define PFT_LIK_WGS_PER_CU 2    // resident likelihood workgroups per CU (each gets 1/N of the LDS)
 #endif
 #define PFT_POP_THREADS 1024
+#define PFT_GATHER_MIN 5000u       // cropped points (last iteration) up to which the single-workgroup builder copies the leaf records itself
 #define PFT_SORTED_BUILD_MIN 18000  // cropped points (last iteration) above which the sorted builder is used
 #define PFT_EG_CAP (1u << 21)     // exact-NN mode: grid cells (8 MB of cell starts)
 #define PFT_EC_SLOTS (1u << 19)  // exact-NN mode: candidate lists per iteration (cells hit by queries)
@@ -118,7 +116,7 @@ struct PftHeader {  // lives in HBM; written by kernels, read by later kernels (
   // ancestor table of the fast descent (PftDev::anc): entry (a << 27) | node for every level-anc_level cell c of the window
   // anc_lo + [0, 2^anc_bits) (index cx | cy << bx | cz << (bx + by)): node is the deepest existing ancestor of c at a level
   // a <= anc_level.  Written by the builders (window) and the fill (entries); used only while anc_epoch == build_epoch
-  int32_t anc_level;     // L = depth - PFT_ANC_UP (0: no table for this tree)
+  int32_t anc_level;     // L = depth - 1 or depth - 2, as the host asked and the window allowed (0: no table for this tree)
   uint32_t anc_lo[3], anc_bits[3];
   uint32_t build_epoch;  // bumped by every tree build
   uint32_t anc_epoch;    // the build_epoch the entries were filled for
@@ -225,7 +223,8 @@ struct PftDev {  // device pointers (host-side struct, passed by value)
   uint32_t* host_stat;  // pinned host memory, device-visible: [0] last n_crop, [1] last octree depth (read by the
                         // host WITHOUT synchronising, to pick the builder for the next iteration: a wrong guess costs
                         // time, never correctness), [2] error flags of the last failed iteration, [3] error flags
-                        // accumulated since the host last looked (checked and cleared at the host's sync points)
+                        // accumulated since the host last looked (checked and cleared at the host's sync points),
+                        // [4] exact-NN pool demand, [5] ancestor table window sizes of the last build (pft_anc_window)
   int32_t* nn_idx;      // debug only
   float* nn_d2;
   // change detection (pft_change.hip): &PftChangeState::gate while pft_compute drives a handle whose detector has ever been
@@ -322,6 +321,7 @@ struct PftSwitches {
   bool crop_two_pass;     // PFT_CROP_TWO_PASS: the crop as a count + a scatter launch instead of the one-pass kernel
   bool generic_descent;   // PFT_GENERIC_DESCENT=1: every octree level by the exact 8-way selection
   bool ancestor_table;    // PFT_ANCESTOR_TABLE (default 1): the fast descent starts from the ancestor table
+  int anc_up_force;       // PFT_ANC_UP_FORCE=0|1|2: the table's level D - 1 / D - 2 or none, whatever the last window's size (-1: by it)
   PftExactPath exact_path;  // PFT_EXACT_SHELLS_ONLY, else PFT_EXACT_PER_QUERY, else the cell-sorted search
   int ablate;             // diagnostic build only: PFT_ABLATE, or pft_debug_set_ablate (results are wrong while set)
   bool skip_octree;       // diagnostic build only: PFT_DEBUG_SKIP_OCTREE (results are wrong while set)
@@ -420,7 +420,8 @@ void pftk_resample_kld(hipStream_t s, const PftParams& p, const PftDev& d, uint3
 void pftk_crop(hipStream_t s, const PftParams& p, const PftDev& d, bool bbox_from_partials, uint32_t epoch,
                const pft_point_xyzrgba* raw, bool two_pass, const uint32_t* n_src = nullptr);
 // the single-workgroup builder; indirect: no leaf_pts copies, the likelihood kernel follows leaf_order (its INDIRECT form)
-void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect);
+// anc_up: the ancestor table's level for this tree, depth - anc_up (1 or 2; 0: none), where its window fits
+void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect, int anc_up);
 // no-op launch unless the sorted builder flagged "radix passes too few" (error bit 3): then the single-workgroup build
 void pftk_octree_rescue(hipStream_t s, const PftParams& p, const PftDev& d);
 struct SortBufs {
@@ -435,9 +436,10 @@ struct SortBufs {
 void pftk_octree_sorted(hipStream_t s, const PftParams& p, const PftDev& d, const SortBufs& sb, uint32_t n_pad,
                         int npass);
 // flags (k_likelihood's argument): bit 0 fast descent allowed, bit 1 ancestor table allowed, bits 8+ the stage ablation
-// mask of the diagnostic build
-void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
-                     int num_cus, bool leaf_indirect, int flags);
+// mask of the diagnostic build; anc_up: what the tree's builder was asked for -- picks the product instance, whose ANC_UP
+// is returned
+int pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
+                    int num_cus, bool leaf_indirect, int flags, int anc_up);
 // shard (nullable): sharded handles -- the particles with their raw weights also go into the all-gather's send buffer
 void pftk_finalize_raw(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles,
                        float* raw_out /*nullable*/, pft_particle* shard /*nullable*/);

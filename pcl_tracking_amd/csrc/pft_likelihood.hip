@@ -42,7 +42,7 @@ struct LikCtx {
   int J;
   uint32_t lvlJ_start;
   const uint32_t* anc;     // ancestor table (global memory, L2-resident), or null
-  // its window at level D - PFT_ANC_UP, packed (two scalar registers instead of six: the kernel is at 64 VGPRs, and more
+  // its window at level D - ANC_UP, packed (two scalar registers instead of six: the kernel is at 64 VGPRs, and more
   // live scalars spill into vector lanes): first cell x | y << 10 | z << 20, log2 of the cells per axis bx | by << 8 | bz << 16
   uint32_t alo, abits;
   float margin, near_thr, ominx, ominy, ominz, inv_res, ncell;
@@ -93,7 +93,9 @@ __device__ __forceinline__ int near_face_level(uint32_t k, bool low, bool high) 
 // INDIRECT (PftHeader::leaf_indirect; compile-time here -- as a run-time flag the branch in the leaf scan cost 4 us per launch
 // at the headline size): the builder left the point records where the crop put them, a candidate is
 // crop_pts[leaf_order[pos]] and bpos carries the record's index in crop_pts
-template <bool USE_TAB, bool FAST, bool DEBUG_NN, int LEAF, bool INDIRECT, typename WordPtr>
+// ANC_UP: the ancestor table's level is D - ANC_UP (1 or 2; compile-time: the kernel has no register left for a second
+// run-time path); 0 compiles no table code at all
+template <bool USE_TAB, bool FAST, bool DEBUG_NN, int LEAF, bool INDIRECT, int ANC_UP, typename WordPtr>
 __device__ __forceinline__ void likelihood_items(const PftParams& prm, const PftDev& d, const LikCtx& cx, WordPtr W,
                                                  uint32_t n_particles, int D, uint32_t n_crop,
                                                  const double omin[3], int abl) {
@@ -192,32 +194,41 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
         }
         V = inside ? V : 31;
         int lim = min(D, D - 1 - V);  // fast levels are those with lvl < lim
-        // Ancestor table: the fast descent's result is the deepest existing ancestor of the query's leaf cell at a level
-        // <= lim, an integer fact about the tree: one 4-byte gather of the entry of the query's level-L cell (a query
-        // outside the window reads entry 0 and does not use it; a query outside the box has key 0 and lim < 0: neither).
-        // (Issued right after the key, its live range pushed the kernel past 64 VGPRs into scratch.)
-        bool inw = false;
-        uint32_t ae = 0u;
-        if (!INDIRECT && LEAF == 1 && cx.anc) {  // (wave-uniform; which instances: see k_likelihood)
-          const uint32_t bx = cx.abits & 0xffu, by = (cx.abits >> 8) & 0xffu, bz = cx.abits >> 16;
-          const uint32_t ux = (kx >> PFT_ANC_UP) - (cx.alo & 1023u), uy = (ky >> PFT_ANC_UP) - ((cx.alo >> 10) & 1023u),
-                         uz = (kz >> PFT_ANC_UP) - (cx.alo >> 20);
-          inw = ((ux >> bx) | (uy >> by) | (uz >> bz)) == 0u;
-          ae = cx.anc[inw ? ux | (uy << bx) | (uz << (bx + by)) : 0u];
-        }
-        // the entry (a, node): a < L -- the descent ends at (node, a), no trip; a == L -- the loop goes on from there
-        // (at most D - L = PFT_ANC_UP trips); a > lim (near a face) or outside the window: the jump + loop below
-        const int a = (int)(ae >> 27);
-        const bool hit = inw & (a <= lim);
-        node = hit ? (ae & 0x7ffffffu) : 0u;
-        lvl = hit ? a : 0;
-        lim = (hit & (a < D - PFT_ANC_UP)) ? a : lim;
-        if (cx.J > 0 && __builtin_amdgcn_ballot_w64(!hit)) {  // (wave-uniform) the jump lands on level J: its cell spans
-          const int sh = D - cx.J;                              // 2^(D-J) leaf cells, D-J > V
+        if constexpr (ANC_UP > 0 && !INDIRECT && LEAF == 1) {  // (which instances: see k_likelihood)
+          // Ancestor table: the fast descent's result is the deepest existing ancestor of the query's leaf cell at a level
+          // <= lim, an integer fact about the tree: one 4-byte gather of the entry of the query's level-L cell (a query
+          // outside the window reads entry 0 and does not use it; a query outside the box has key 0 and lim < 0: neither).
+          // (Issued right after the key, its live range pushed the kernel past 64 VGPRs into scratch.)
+          bool inw = false;
+          uint32_t ae = 0u;
+          if (cx.anc) {  // (wave-uniform)
+            const uint32_t bx = cx.abits & 0xffu, by = (cx.abits >> 8) & 0xffu, bz = cx.abits >> 16;
+            const uint32_t ux = (kx >> ANC_UP) - (cx.alo & 1023u), uy = (ky >> ANC_UP) - ((cx.alo >> 10) & 1023u),
+                           uz = (kz >> ANC_UP) - (cx.alo >> 20);
+            inw = ((ux >> bx) | (uy >> by) | (uz >> bz)) == 0u;
+            ae = cx.anc[inw ? ux | (uy << bx) | (uz << (bx + by)) : 0u];
+          }
+          // the entry (a, node): a < L -- the descent ends at (node, a), no trip; a == L -- the loop goes on from there
+          // (at most D - L = ANC_UP trips); a > lim (near a face) or outside the window: the jump + loop below
+          const int a = (int)(ae >> 27);
+          const bool hit = inw & (a <= lim);
+          node = hit ? (ae & 0x7ffffffu) : 0u;
+          lvl = hit ? a : 0;
+          lim = (hit & (a < D - ANC_UP)) ? a : lim;
+          if (cx.J > 0 && __builtin_amdgcn_ballot_w64(!hit)) {  // (wave-uniform) the jump lands on level J: its cell spans
+            const int sh = D - cx.J;                              // 2^(D-J) leaf cells, D-J > V
+            const uint32_t e = cx.jump[(kx >> sh) | ((ky >> sh) << cx.J) | ((kz >> sh) << (2 * cx.J))];
+            const bool take = !hit & (cx.J <= lim) & (e != 0u);  // all ancestors of an existing node exist and contain the query
+            node = take ? cx.lvlJ_start + e - 1u : node;
+            lvl = take ? cx.J : lvl;
+            if (DEBUG_NN) dbg_jump = take ? 1 : 0;
+          }
+        } else if (cx.J > 0) {  // (wave-uniform) the jump lands on level J: its cell spans 2^(D-J) leaf cells, D-J > V
+          const int sh = D - cx.J;
           const uint32_t e = cx.jump[(kx >> sh) | ((ky >> sh) << cx.J) | ((kz >> sh) << (2 * cx.J))];
-          const bool take = !hit & (cx.J <= lim) & (e != 0u);  // all ancestors of an existing node exist and contain the query
-          node = take ? cx.lvlJ_start + e - 1u : node;
-          lvl = take ? cx.J : lvl;
+          const bool take = (cx.J <= lim) & (e != 0u);  // all ancestors of an existing node exist and contain the query
+          node = take ? cx.lvlJ_start + e - 1u : 0u;
+          lvl = take ? cx.J : 0;
           if (DEBUG_NN) dbg_jump = take ? 1 : 0;
         }
         // fast levels: follow the key while the child containing the query exists (a divergent loop: a version
@@ -457,9 +468,11 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
 // INDIRECT is a parameter of the KERNEL (the host decides the leaf-record form once per build and passes it to the builder
 // and to this launch): both forms inside one kernel doubled its code and its scalar-register spills (76 -> 136) and
 // cost the headline launch 2 %
-#define PFT_LIK_RUN(UT, FA, LF) likelihood_items<UT, FA, DEBUG_NN, LF, INDIRECT>(prm, d, cx, W, n_particles, D, n_crop, omin, abl)
+#define PFT_LIK_RUN(UT, FA, LF) likelihood_items<UT, FA, DEBUG_NN, LF, INDIRECT, ANC_UP>(prm, d, cx, W, n_particles, D, n_crop, omin, abl)
 
-template <bool DEBUG_NN, bool INDIRECT, bool GATED>
+// ANC_UP (likelihood_items): the host launches the instance of the level it asked the builder for; the INDIRECT instances
+// have no table code (0), the DEBUG_NN instance of the direct form keeps level D - 2
+template <bool DEBUG_NN, bool INDIRECT, bool GATED, int ANC_UP>
 __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * PFT_LIK_WGS_PER_CU) / 256) void k_likelihood(PftParams prm, PftDev d, uint32_t n_particles,
                                                                 uint32_t lds_bytes, int flags) {
   const int allow_fast = flags & 1;
@@ -584,7 +597,9 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
   // the direct form only: the trees of the other layouts come from the sorted builder (crops above PFT_SORTED_BUILD_MIN) and
   // the indirect form from small launches, neither of which fills a table, and every inlined copy costs registers (the
   // kernel is at 63 of its 64 VGPRs with this one)
-  const bool anc_on = fast && (flags & 2) && d.anc && hdr->anc_level > 0 && hdr->anc_epoch == hdr->build_epoch;
+  // (a table of another level than this instance's -- the host's guess was wrong for this tree -- is not used either)
+  const bool anc_on = ANC_UP > 0 && fast && (flags & 2) && d.anc && hdr->anc_level > 0 && D - hdr->anc_level == ANC_UP &&
+                      hdr->anc_epoch == hdr->build_epoch;
   cx.anc = anc_on ? d.anc : nullptr;
   static_assert(PFT_TABLE_MAX_DEPTH <= 10, "ancestor table window coordinates are packed in 10 bits");  // (fast: use_tab)
   cx.alo = hdr->anc_lo[0] | (hdr->anc_lo[1] << 10) | (hdr->anc_lo[2] << 20);
@@ -639,27 +654,31 @@ __global__ __launch_bounds__(PFT_LIK_THREADS, DEBUG_NN ? 1 : (PFT_LIK_THREADS * 
 extern "C" int pft_debug_likelihood_occupancy(void) {
   int nb = -1;
   uint32_t lds = ((uint32_t)pftk_max_lds_bytes() / (uint32_t)PFT_LIK_WGS_PER_CU) & ~255u;
-  hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_likelihood<false, false, false>), PFT_LIK_THREADS, lds) != hipSuccess) return -1;
+  hipFuncSetAttribute(reinterpret_cast<const void*>(&k_likelihood<false, false, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_likelihood<false, false, false, 2>), PFT_LIK_THREADS, lds) != hipSuccess) return -1;
   return nb;
 }
 
-void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
-                     int num_cus, bool leaf_indirect, int flags) {
+// anc_up: the table level the host asked this tree's builder for (0: none).  The instance launched is the product
+// instance of that level; the INDIRECT instances have no table code, and the DEBUG_NN instance of the direct form has
+// level D - 2's only (it runs table-less on any other tree).  Returns the ANC_UP of the instance launched.
+int pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t n_particles, bool debug_nn,
+                    int num_cus, bool leaf_indirect, int flags, int anc_up) {
   static bool attr_set[PFT_MAX_DEVICES];
   // half of the CU's LDS per workgroup: two 1024-thread workgroups (32 waves, 8 per SIMD) are resident per CU
   uint32_t lds = ((uint32_t)pftk_max_lds_bytes() / (uint32_t)PFT_LIK_WGS_PER_CU) & ~255u;
   const int dev = pftk_cur_device();
+#define PFT_LIK_FN(DN, IND, GA, UP) reinterpret_cast<const void*>(&k_likelihood<DN, IND, GA, UP>)
   if (!attr_set[dev]) {
-    const void* fns[8] = {
-        reinterpret_cast<const void*>(&k_likelihood<false, false, false>), reinterpret_cast<const void*>(&k_likelihood<true, false, false>),
-        reinterpret_cast<const void*>(&k_likelihood<false, true, false>), reinterpret_cast<const void*>(&k_likelihood<true, true, false>),
-        reinterpret_cast<const void*>(&k_likelihood<false, false, true>), reinterpret_cast<const void*>(&k_likelihood<true, false, true>),
-        reinterpret_cast<const void*>(&k_likelihood<false, true, true>), reinterpret_cast<const void*>(&k_likelihood<true, true, true>)};
+    const void* fns[12] = {PFT_LIK_FN(false, false, false, 0), PFT_LIK_FN(false, false, false, 1), PFT_LIK_FN(false, false, false, 2),
+                           PFT_LIK_FN(false, false, true, 0),  PFT_LIK_FN(false, false, true, 1),  PFT_LIK_FN(false, false, true, 2),
+                           PFT_LIK_FN(true, false, false, 2),  PFT_LIK_FN(true, false, true, 2),   PFT_LIK_FN(false, true, false, 0),
+                           PFT_LIK_FN(false, true, true, 0),   PFT_LIK_FN(true, true, false, 0),   PFT_LIK_FN(true, true, true, 0)};
     bool ok = true;
-    for (int k = 0; k < 8; k++) ok = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess && ok;
+    for (int k = 0; k < 12; k++) ok = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess && ok;
     attr_set[dev] = ok;
   }
+#undef PFT_LIK_FN
   // (fewer workgroups at small particle counts -- less staging traffic -- was measured: 400 particles 52.2 us per frame with
   // the full grid, 54.9 / 56.2 / 84.2 with 384 / 256 / 128 workgroups)
   uint32_t items = n_particles * p.nchunk;
@@ -668,22 +687,27 @@ void pftk_likelihood(hipStream_t s, const PftParams& p, const PftDev& d, uint32_
   if (need == 0) need = 1;
   if (grid > need) grid = need;
   // (GATED: pft_compute on a handle with a change detector; the default path launches the instances without the test)
-#define PFT_LIK_LAUNCH(DN, IND)                                                                                          \
-  do {                                                                                                                   \
-    if (d.gate)                                                                                                          \
-      hipLaunchKernelGGL((k_likelihood<DN, IND, true>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
-                         flags);                                                                                         \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((k_likelihood<DN, IND, false>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
-                         flags);                                                                                         \
+#define PFT_LIK_LAUNCH(DN, IND, UP)                                                                                          \
+  do {                                                                                                                       \
+    if (d.gate)                                                                                                              \
+      hipLaunchKernelGGL((k_likelihood<DN, IND, true, UP>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
+                         flags);                                                                                             \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((k_likelihood<DN, IND, false, UP>), dim3(grid), dim3(PFT_LIK_THREADS), lds, s, p, d, n_particles, lds, \
+                         flags);                                                                                             \
+    return UP;                                                                                                               \
   } while (0)
   if (debug_nn && leaf_indirect)
-    PFT_LIK_LAUNCH(true, true);
+    PFT_LIK_LAUNCH(true, true, 0);
   else if (debug_nn)
-    PFT_LIK_LAUNCH(true, false);
+    PFT_LIK_LAUNCH(true, false, 2);
   else if (leaf_indirect)
-    PFT_LIK_LAUNCH(false, true);
+    PFT_LIK_LAUNCH(false, true, 0);
+  else if (anc_up == 1)
+    PFT_LIK_LAUNCH(false, false, 1);
+  else if (anc_up == 2)
+    PFT_LIK_LAUNCH(false, false, 2);
   else
-    PFT_LIK_LAUNCH(false, false);
+    PFT_LIK_LAUNCH(false, false, 0);
 #undef PFT_LIK_LAUNCH
 }

@@ -548,7 +548,7 @@ __device__ __forceinline__ void build_regs(const PftParams& prm, const PftDev& d
 // the other one, whose code is the builder's without the test
 template <bool GATED>
 __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams prm, PftDev d, uint32_t lds_bytes,
-                                                                    int copy_leaf_pts, int rescue) {
+                                                                    int copy_leaf_pts, int rescue, int anc_up) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ BuildSh S;
   PftHeader* hdr = d.hdr;
@@ -648,7 +648,7 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
   }
   if (tid == 128) hdr->inv_res = (float)(1.0 / prm.res);
   // the ancestor table is filled by k_leaf_gather, i.e. in mode 0 only (the other modes have no launch to carry it: no table)
-  if (tid == 320) pft_anc_window(hdr, d, D, ok && use_table && copy_leaf_pts == 0, S.mn, prm.res);
+  if (tid == 320) pft_anc_window(hdr, d, D, ok && use_table, copy_leaf_pts == 0, S.mn, prm.res, anc_up);
   if (tid >= 192 && tid < 195) {
     const int a = (int)tid - 192;
     hdr->ominf[a] = (float)S.mn[a];
@@ -661,32 +661,59 @@ __global__ __launch_bounds__(PFT_BUILD_THREADS) void k_octree_build(PftParams pr
 // The ancestor table of the tree just built (PftHeader::anc_*): for every cell of the window, the walk of the likelihood
 // kernel's fast descent along the cell's key down to level L -- from the jump table's level-J node when there is one -- and
 // the deepest node it reaches.  An integer fact about the tree: no float decision is involved.
+// A table at level D - 1 (eight times the cells of the D - 2 window) is filled from the parent level: one descent per
+// level-(L - 1) cell, as many as the D - 2 fill makes, then the eight entries under that cell from one more node word,
+// written as four x-adjacent pairs (pft_anc_window: the window starts on an even cell and spans whole parent cells).
 __device__ __forceinline__ void anc_fill(const PftDev& d, uint32_t gid, uint32_t stride) {
   const PftHeader* hdr = d.hdr;
   const int L = hdr->anc_level;
   if (L <= 0) return;
-  const uint32_t bx = hdr->anc_bits[0], by = hdr->anc_bits[1], n = 1u << (bx + by + hdr->anc_bits[2]);
-  const uint32_t x0 = hdr->anc_lo[0], y0 = hdr->anc_lo[1], z0 = hdr->anc_lo[2];
-  const int J = hdr->jump_level <= L ? hdr->jump_level : 0;
+  const bool deeper = hdr->depth - L == 1;  // (uniform) walk the parents of the window's cells
+  const int Lw = deeper ? L - 1 : L;        // the level the descents run to
+  const uint32_t bx = hdr->anc_bits[0], by = hdr->anc_bits[1], bz = hdr->anc_bits[2];
+  // the walked cells: the window itself, or its parents (one bit less per axis, half the first cell)
+  const uint32_t wbx = deeper ? bx - 1u : bx, wby = deeper ? by - 1u : by, wbz = deeper ? bz - 1u : bz;
+  const uint32_t n = 1u << (wbx + wby + wbz);
+  const uint32_t x0 = hdr->anc_lo[0] >> (deeper ? 1 : 0), y0 = hdr->anc_lo[1] >> (deeper ? 1 : 0),
+                 z0 = hdr->anc_lo[2] >> (deeper ? 1 : 0);
+  const int J = hdr->jump_level <= Lw ? hdr->jump_level : 0;
   const uint32_t lvlJ = J > 0 ? hdr->lvl_start[J] : 0u;
   for (uint32_t c = gid; c < n; c += stride) {
-    const uint32_t x = x0 + (c & ((1u << bx) - 1u)), y = y0 + ((c >> bx) & ((1u << by) - 1u)), z = z0 + (c >> (bx + by));
+    const uint32_t ux = c & ((1u << wbx) - 1u), uy = (c >> wbx) & ((1u << wby) - 1u), uz = c >> (wbx + wby);
+    const uint32_t x = x0 + ux, y = y0 + uy, z = z0 + uz;
     uint32_t node = 0;
     int lvl = 0;
     if (J > 0) {
-      const int sh = L - J;
+      const int sh = Lw - J;
       const uint32_t e = d.jump[(x >> sh) | ((y >> sh) << J) | ((z >> sh) << (2 * J))];
       node = e ? lvlJ + e - 1u : 0u;
       lvl = e ? J : 0;
     }
-    for (; lvl < L; lvl++) {
-      const int sh = L - lvl - 1;
+    for (; lvl < Lw; lvl++) {
+      const int sh = Lw - lvl - 1;
       const uint32_t ch = (((x >> sh) & 1u) << 2) | (((y >> sh) & 1u) << 1) | ((z >> sh) & 1u);
       const uint32_t wv = d.words[node];
       if (!((wv >> ch) & 1u)) break;
       node = (wv >> 8) + __popc(wv & 0xffu & ((1u << ch) - 1u));
     }
-    d.anc[c] = ((uint32_t)lvl << 27) | node;
+    const uint32_t own = ((uint32_t)lvl << 27) | node;
+    if (!deeper) {
+      d.anc[c] = own;
+    } else {
+      // the parent cell does not exist (lvl < L - 1): its ancestor is the children's; it exists: an existing child is its
+      // own entry at level L, an absent one keeps the parent
+      const uint32_t wv = lvl == Lw ? d.words[node] : 0u;
+      const uint32_t mask = wv & 0xffu, base = wv >> 8;
+#pragma unroll
+      for (uint32_t yz = 0; yz < 4u; yz++) {  // child index: x << 2 | y << 1 | z
+        const uint32_t c0 = yz, c1 = 4u | yz;
+        uint2 e;
+        e.x = (mask >> c0) & 1u ? ((uint32_t)L << 27) | (base + __popc(mask & ((1u << c0) - 1u))) : own;
+        e.y = (mask >> c1) & 1u ? ((uint32_t)L << 27) | (base + __popc(mask & ((1u << c1) - 1u))) : own;
+        const uint32_t idx = (2u * ux) | ((2u * uy + (yz >> 1)) << bx) | ((2u * uz + (yz & 1u)) << (bx + by));
+        *reinterpret_cast<uint2*>(d.anc + idx) = e;  // (idx even: 8-byte aligned; idx + 1 < 2^(bx + by + bz) <= PFT_ANC_CAP)
+      }
+    }
   }
   if (gid == 0) d.hdr->anc_epoch = hdr->build_epoch;  // (read by the next launch on the stream: after every entry)
 }
@@ -706,7 +733,7 @@ __global__ __launch_bounds__(256) void k_leaf_gather(PftDev d) {
 #ifndef PFT_OCTREE_GATED_TU
 // The GATED instances live in pft_octree_gated.hip: instantiated here beside the default ones, they changed the default
 // builder's code (the box routines gained a second caller), and the default path must stay as it was
-extern template __global__ void k_octree_build<true>(PftParams, PftDev, uint32_t, int, int);
+extern template __global__ void k_octree_build<true>(PftParams, PftDev, uint32_t, int, int, int);
 extern template __global__ void k_leaf_gather<true>(PftDev);
 
 static void pftk_octree_set_attr() {
@@ -720,7 +747,7 @@ static void pftk_octree_set_attr() {
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
 }
 
-void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect) {
+void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t expected_points, bool indirect, int anc_up) {
   // static LDS of the kernel (BuildSh ~2.6 KB, the dense top-level arrays 5 KB): leave 10 KB out of the dynamic request
   const uint32_t lds = ((uint32_t)pftk_max_lds_bytes() - 10240u) & ~15u;
   pftk_octree_set_attr();
@@ -730,13 +757,13 @@ void pftk_octree(hipStream_t s, const PftParams& p, const PftDev& d, uint32_t ex
   //      (4.6 us) or scattered stores by the one builder workgroup; the caller chooses it when the launch is small
   //   1  the builder itself (crops of at most 5 000 points, by the previous iteration's size)
   //   0  k_leaf_gather, a launch of many workgroups
-  const int mode = indirect ? 2 : (expected_points <= 5000u ? 1 : 0);
+  const int mode = indirect ? 2 : (expected_points <= PFT_GATHER_MIN ? 1 : 0);
   const dim3 gg((d.N + 255u) / 256u ? (d.N + 255u) / 256u : 1u);
   if (d.gate) {
-    hipLaunchKernelGGL(k_octree_build<true>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0);
+    hipLaunchKernelGGL(k_octree_build<true>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0, anc_up);
     if (mode == 0) hipLaunchKernelGGL(k_leaf_gather<true>, gg, dim3(256), 0, s, d);
   } else {
-    hipLaunchKernelGGL(k_octree_build<false>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0);
+    hipLaunchKernelGGL(k_octree_build<false>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, mode, 0, anc_up);
     // at most PFT_SORTED_BUILD_MIN-ish points reach this builder in practice, but any crop (<= N) is legal
     if (mode == 0) hipLaunchKernelGGL(k_leaf_gather<false>, gg, dim3(256), 0, s, d);
   }
@@ -747,8 +774,8 @@ void pftk_octree_rescue(hipStream_t s, const PftParams& p, const PftDev& d) {
   pftk_octree_set_attr();
   const uint32_t lds = ((uint32_t)pftk_max_lds_bytes() - 10240u) & ~15u;
   if (d.gate)
-    hipLaunchKernelGGL(k_octree_build<true>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1);
+    hipLaunchKernelGGL(k_octree_build<true>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1, 0);
   else
-    hipLaunchKernelGGL(k_octree_build<false>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1);
+    hipLaunchKernelGGL(k_octree_build<false>, dim3(1), dim3(PFT_BUILD_THREADS), lds, s, p, d, lds, 1, 1, 0);
 }
 #endif  // PFT_OCTREE_GATED_TU

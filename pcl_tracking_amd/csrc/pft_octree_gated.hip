@@ -4,5 +4,5 @@
 #define PFT_OCTREE_GATED_TU
 #include "pft_octree.hip"
 
-template __global__ void k_octree_build<true>(PftParams, PftDev, uint32_t, int, int);
+template __global__ void k_octree_build<true>(PftParams, PftDev, uint32_t, int, int, int);
 template __global__ void k_leaf_gather<true>(PftDev);

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(1024) void k_so_replay(PftParams prm, PftDev d, con
       hdr->omax[a] = n > 0 ? S.mx[a] : 0.0;
     }
     hdr->inv_res = (float)(1.0 / res);
-    pft_anc_window(hdr, d, D, false, S.mn, res);  // (no table for this builder's trees: the epoch moves on)
+    pft_anc_window(hdr, d, D, false, false, S.mn, res, 0);  // (no table for this builder's trees: the epoch moves on)
     if (!ok) {
       hdr->n_words = 0;
       hdr->n_leaves = 0;

@@ -860,6 +860,19 @@ class ParticleFilterTracker:
         self._check(self._L.pft_debug_get_host_stat(self._h, _ptr(out)))
         return out
 
+    def debugAncestorLevel(self):
+        """the ancestor table's level choice (pft_debug_get_ancestor_level): dict(status -- the pinned word of the last build --,
+        bits_d1 / bits_d2 -- log2 cells of its window at depth - 1 / depth - 2, None: no window --, anc_up -- the level asked of
+        the last build as depth - anc_up, 0: none --, instance -- ANC_UP of the last likelihood instance --, changes, graph_builds)"""
+        self._ensure()
+        o = np.zeros(5, np.uint32)
+        self._check(self._L.pft_debug_get_ancestor_level(self._h, _ptr(o)))
+        st = int(o[0])
+        b1, b2 = st & 0xFF, (st >> 8) & 0xFF
+        valid = bool(st >> 31)
+        return dict(status=st, bits_d1=b1 if valid and b1 != 0xFF else None, bits_d2=b2 if valid and b2 != 0xFF else None,
+                    anc_up=int(np.int32(o[1])), instance=int(np.int32(o[2])), changes=int(o[3]), graph_builds=int(o[4]))
+
     def debugNormalize(self, w):
         self._ensure()
         w = np.array(w, np.float32, copy=True)
