@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "pft_devbuf.h"
 #include "pft_device_utils.h"
 #include "../../include/pft_filters.h"
 
@@ -912,15 +913,6 @@ __global__ __launch_bounds__(F_THREADS) void k_f_pass_indices(FParams p, FDev d)
 
 // ---------------------------------------------------------------------------------------------------
 // host side
-#define FCHK(f, call)                                                  \
-  do {                                                                 \
-    hipError_t e_ = (call);                                            \
-    if (e_ != hipSuccess) {                                            \
-      (f)->err = std::string(#call) + ": " + hipGetErrorString(e_);    \
-      return PFT_ERR_HIP;                                              \
-    }                                                                  \
-  } while (0)
-
 struct pft_filter {
   pft_filter_config cfg;
   hipStream_t stream = nullptr;
@@ -942,21 +934,11 @@ struct pft_filter {
   double last_ms = 0.0;
 };
 
-template <typename T>
-static hipError_t falloc(T** p, size_t n) {
-  return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
-}
-template <typename T>
-static void ffree(T*& p) {
-  if (p) hipFree((void*)p);
-  p = nullptr;
-}
-
 static void free_buffers(pft_filter* f) {
   FDev& d = f->d;
-  ffree(f->d_in_own); ffree(d.out); ffree(d.key[0]); ffree(d.key[1]); ffree(d.val[0]); ffree(d.val[1]);
-  ffree(d.key16); ffree(d.spt); ffree(d.trig_bits); ffree(d.word_pref); ffree(d.passf); ffree(d.head); ffree(d.hist);
-  ffree(d.tile_trig); ffree(d.tile_pass); ffree(d.tile_head); ffree(d.bpart); ffree(d.pass_idx);
+  pft_dfree(f->d_in_own); pft_dfree(d.out); pft_dfree(d.key[0]); pft_dfree(d.key[1]); pft_dfree(d.val[0]); pft_dfree(d.val[1]);
+  pft_dfree(d.key16); pft_dfree(d.spt); pft_dfree(d.trig_bits); pft_dfree(d.word_pref); pft_dfree(d.passf); pft_dfree(d.head); pft_dfree(d.hist);
+  pft_dfree(d.tile_trig); pft_dfree(d.tile_pass); pft_dfree(d.tile_head); pft_dfree(d.bpart); pft_dfree(d.pass_idx);
   f->cap = 0;
 }
 
@@ -986,31 +968,31 @@ static void settle_borrows(pft_filter* f, bool host_wait) {
 
 static int ensure_capacity(pft_filter* f, size_t n) {
   if (n <= f->cap) return PFT_OK;
-  if (f->stream) FCHK(f, hipStreamSynchronize(f->stream));
+  if (f->stream) PFT_HIPCHK(f, hipStreamSynchronize(f->stream));
   settle_borrows(f, true);
   free_buffers(f);
   size_t cap = n < 1024 ? 1024 : n;
   cap = (cap + 1023) / 1024 * 1024;
   const uint32_t nt = (uint32_t)(cap / 1024);
   FDev& d = f->d;
-  FCHK(f, falloc(&f->d_in_own, cap));
-  FCHK(f, falloc(&d.out, cap));
+  PFT_HIPCHK(f, pft_dalloc(&f->d_in_own, cap));
+  PFT_HIPCHK(f, pft_dalloc(&d.out, cap));
   for (int k = 0; k < 2; k++) {
-    FCHK(f, falloc(&d.key[k], cap));
-    FCHK(f, falloc(&d.val[k], cap));
+    PFT_HIPCHK(f, pft_dalloc(&d.key[k], cap));
+    PFT_HIPCHK(f, pft_dalloc(&d.val[k], cap));
   }
-  FCHK(f, falloc(&d.key16, cap));
-  FCHK(f, falloc(&d.spt, cap + 8));
-  FCHK(f, falloc(&d.trig_bits, cap / 32));
-  FCHK(f, falloc(&d.word_pref, cap / 32));
-  FCHK(f, falloc(&d.passf, cap));
-  FCHK(f, falloc(&d.head, cap + 8));
-  FCHK(f, falloc(&d.hist, (size_t)F_MAX_HIST * nt + F_MAX_HIST));
-  FCHK(f, falloc(&d.tile_trig, nt));
-  FCHK(f, falloc(&d.tile_pass, nt));
-  FCHK(f, falloc(&d.tile_head, nt));
-  FCHK(f, falloc(&d.bpart, (size_t)nt * 6));
-  FCHK(f, falloc(&d.pass_idx, cap));
+  PFT_HIPCHK(f, pft_dalloc(&d.key16, cap));
+  PFT_HIPCHK(f, pft_dalloc(&d.spt, cap + 8));
+  PFT_HIPCHK(f, pft_dalloc(&d.trig_bits, cap / 32));
+  PFT_HIPCHK(f, pft_dalloc(&d.word_pref, cap / 32));
+  PFT_HIPCHK(f, pft_dalloc(&d.passf, cap));
+  PFT_HIPCHK(f, pft_dalloc(&d.head, cap + 8));
+  PFT_HIPCHK(f, pft_dalloc(&d.hist, (size_t)F_MAX_HIST * nt + F_MAX_HIST));
+  PFT_HIPCHK(f, pft_dalloc(&d.tile_trig, nt));
+  PFT_HIPCHK(f, pft_dalloc(&d.tile_pass, nt));
+  PFT_HIPCHK(f, pft_dalloc(&d.tile_head, nt));
+  PFT_HIPCHK(f, pft_dalloc(&d.bpart, (size_t)nt * 6));
+  PFT_HIPCHK(f, pft_dalloc(&d.pass_idx, cap));
   f->cap = cap;
   return PFT_OK;
 }
@@ -1057,7 +1039,7 @@ extern "C" int pft_filter_create(const pft_filter_config* cfg, pft_filter** out)
   }
   bool ok = hipEventCreate(&f->ev0) == hipSuccess && hipEventCreate(&f->ev1) == hipSuccess &&
             hipEventCreateWithFlags(&f->ev_copy, hipEventDisableTiming) == hipSuccess &&
-            falloc(&f->d.bucket, F_MAX_HIST + 1) == hipSuccess && falloc(&f->d.hdr, 1) == hipSuccess &&
+            pft_dalloc(&f->d.bucket, F_MAX_HIST + 1) == hipSuccess && pft_dalloc(&f->d.hdr, 1) == hipSuccess &&
             hipHostMalloc(reinterpret_cast<void**>(&f->d.host_stat), 4 * sizeof(uint32_t), hipHostMallocMapped) == hipSuccess;
   if (ok) ok = hipMemset(f->d.hdr, 0, sizeof(FHdr)) == hipSuccess;
   if (ok) ok = ensure_capacity(f, cfg->max_points ? cfg->max_points : 1024) == PFT_OK;
@@ -1080,8 +1062,8 @@ extern "C" void pft_filter_destroy(pft_filter* f) {
   }
   f->borrows.clear();
   free_buffers(f);
-  ffree(f->d.bucket);
-  ffree(f->d.hdr);
+  pft_dfree(f->d.bucket);
+  pft_dfree(f->d.hdr);
   if (f->d.host_stat) hipHostFree(f->d.host_stat);
   if (f->ev0) hipEventDestroy(f->ev0);
   if (f->ev1) hipEventDestroy(f->ev1);
@@ -1111,7 +1093,7 @@ static int run_pipeline(pft_filter* f, const pft_point_xyzrgba* d_in, size_t n) 
   const uint32_t ntiles = (uint32_t)((n + F_TILE - 1) / F_TILE);
   const uint32_t nblk = (uint32_t)((n + F_THREADS - 1) / F_THREADS);
   f->ntiles = ntiles;
-  FCHK(f, hipEventRecord(f->ev0, s));
+  PFT_HIPCHK(f, hipEventRecord(f->ev0, s));
   if (p.mode == PFT_VOXEL_APPROX) {
     const uint32_t nb = p.hist_mask + 1u;
     int bits = 0;
@@ -1147,8 +1129,8 @@ static int run_pipeline(pft_filter* f, const pft_point_xyzrgba* d_in, size_t n) 
     }
     f->tile_pass_scanned = true;
   }
-  FCHK(f, hipEventRecord(f->ev1, s));
-  FCHK(f, hipGetLastError());
+  PFT_HIPCHK(f, hipEventRecord(f->ev1, s));
+  PFT_HIPCHK(f, hipGetLastError());
   f->n_in = n;
   f->pending = true;
   f->applied = true;
@@ -1158,11 +1140,11 @@ static int run_pipeline(pft_filter* f, const pft_point_xyzrgba* d_in, size_t n) 
 // the one host wait of an apply: the stream drains, the counts come out of the pinned status words
 static int wait_pending(pft_filter* f) {
   if (!f->pending) return PFT_OK;
-  FCHK(f, hipSetDevice(f->cfg.device_id));
-  FCHK(f, hipStreamSynchronize(f->stream));
+  PFT_HIPCHK(f, hipSetDevice(f->cfg.device_id));
+  PFT_HIPCHK(f, hipStreamSynchronize(f->stream));
   f->pending = false;
   float ms = 0.0f;
-  FCHK(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
+  PFT_HIPCHK(f, hipEventElapsedTime(&ms, f->ev0, f->ev1));
   f->last_ms = ms;
   f->n_pass = f->d.host_stat[0];
   f->n_out = f->d.host_stat[1];  // (a leaf size too small for the cloud: the input's count, decided by k_f_scan_small)
@@ -1179,11 +1161,11 @@ static int apply_common(pft_filter* f, const pft_point_xyzrgba* pts, size_t n, b
   if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
   f->have_result = false;
   f->pending = false;  // (a pending apply nobody asked about is superseded in stream order)
-  FCHK(f, hipSetDevice(f->cfg.device_id));
+  PFT_HIPCHK(f, hipSetDevice(f->cfg.device_id));
   if (n == 0) {  // empty input cloud: empty output
     settle_borrows(f, false);
-    FCHK(f, hipMemsetAsync(&f->d.hdr->n_out, 0, sizeof(uint32_t), f->stream));  // the count a tracker would read on the device
-    FCHK(f, hipEventRecord(f->ev1, f->stream));
+    PFT_HIPCHK(f, hipMemsetAsync(&f->d.hdr->n_out, 0, sizeof(uint32_t), f->stream));  // the count a tracker would read on the device
+    PFT_HIPCHK(f, hipEventRecord(f->ev1, f->stream));
     f->n_in = f->n_pass = f->n_out = 0;
     f->leaf_too_small = 0;
     f->last_ms = 0.0;
@@ -1196,14 +1178,14 @@ static int apply_common(pft_filter* f, const pft_point_xyzrgba* pts, size_t n, b
   settle_borrows(f, false);  // the output is about to be overwritten
   const pft_point_xyzrgba* d_in = pts;
   if (!on_device) {
-    FCHK(f, hipMemcpyAsync(f->d_in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, f->stream));
-    FCHK(f, hipEventRecord(f->ev_copy, f->stream));
+    PFT_HIPCHK(f, hipMemcpyAsync(f->d_in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, f->stream));
+    PFT_HIPCHK(f, hipEventRecord(f->ev_copy, f->stream));
     d_in = f->d_in_own;
   }
   r = run_pipeline(f, d_in, n);
   if (r != PFT_OK) return r;
   if (wait) return wait_pending(f);
-  if (!on_device) FCHK(f, hipEventSynchronize(f->ev_copy));  // the caller's buffer is only borrowed for this call
+  if (!on_device) PFT_HIPCHK(f, hipEventSynchronize(f->ev_copy));  // the caller's buffer is only borrowed for this call
   return PFT_OK;
 }
 
@@ -1267,8 +1249,8 @@ extern "C" int pft_filter_get_output(pft_filter* f, pft_point_xyzrgba* host_out,
   if (f->n_out > capacity) return PFT_ERR_CAPACITY;
   if (f->n_out) {
     if (!host_out) return PFT_ERR_INVALID_ARG;
-    FCHK(f, hipMemcpyAsync(host_out, f->d.out, f->n_out * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, f->stream));
-    FCHK(f, hipStreamSynchronize(f->stream));
+    PFT_HIPCHK(f, hipMemcpyAsync(host_out, f->d.out, f->n_out * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, f->stream));
+    PFT_HIPCHK(f, hipStreamSynchronize(f->stream));
   }
   return PFT_OK;
 }
@@ -1289,8 +1271,8 @@ extern "C" int pft_filter_get_pass_indices(pft_filter* f, int32_t* host_idx, siz
       f->tile_pass_scanned = true;
     }
     hipLaunchKernelGGL(k_f_pass_indices, dim3(f->ntiles), dim3(F_THREADS), 0, f->stream, p, f->d);
-    FCHK(f, hipMemcpyAsync(host_idx, f->d.pass_idx, f->n_pass * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
-    FCHK(f, hipStreamSynchronize(f->stream));
+    PFT_HIPCHK(f, hipMemcpyAsync(host_idx, f->d.pass_idx, f->n_pass * sizeof(int32_t), hipMemcpyDeviceToHost, f->stream));
+    PFT_HIPCHK(f, hipStreamSynchronize(f->stream));
   }
   return PFT_OK;
 }

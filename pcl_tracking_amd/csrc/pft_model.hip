@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "pft_devbuf.h"
 #include "pft_device_utils.h"
 #include "../../include/pft_filters.h"
 #include "../../include/pft_model.h"
@@ -96,15 +97,6 @@ __global__ __launch_bounds__(MD_THREADS) void k_md_recentre(MdHdr* __restrict__ 
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
-#define MCHK(m, call)                                                  \
-  do {                                                                 \
-    hipError_t e_ = (call);                                            \
-    if (e_ != hipSuccess) {                                            \
-      (m)->err = std::string(#call) + ": " + hipGetErrorString(e_);    \
-      return PFT_ERR_HIP;                                              \
-    }                                                                  \
-  } while (0)
-
 enum { MD_NEV = PFT_MODEL_STAGES };  // events: start, after removeZeroPoints, after the centroid, after the re-centring
 
 struct pft_model {
@@ -132,34 +124,24 @@ struct pft_model {
   double stage_ms[PFT_MODEL_STAGES] = {};
 };
 
-template <typename T>
-static hipError_t malloc_n(T** p, size_t n) {
-  return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
-}
-template <typename T>
-static void free_p(T*& p) {
-  if (p) hipFree((void*)p);
-  p = nullptr;
-}
-
 static void free_buffers(pft_model* m) {
-  free_p(m->in_own); free_p(m->xyz); free_p(m->flag); free_p(m->tile); free_p(m->keep); free_p(m->keep_xyz);
-  free_p(m->recentred);
+  pft_dfree(m->in_own); pft_dfree(m->xyz); pft_dfree(m->flag); pft_dfree(m->tile); pft_dfree(m->keep); pft_dfree(m->keep_xyz);
+  pft_dfree(m->recentred);
   m->cap = 0;
 }
 
 static int ensure_capacity(pft_model* m, size_t n) {
   if (n <= m->cap) return PFT_OK;
-  MCHK(m, hipStreamSynchronize(m->stream));
+  PFT_HIPCHK(m, hipStreamSynchronize(m->stream));
   free_buffers(m);
   const size_t cap = (n + MD_TILE - 1) / MD_TILE * MD_TILE;
-  MCHK(m, malloc_n(&m->in_own, cap));
-  MCHK(m, malloc_n(&m->xyz, cap));
-  MCHK(m, malloc_n(&m->flag, cap));
-  MCHK(m, malloc_n(&m->tile, cap / MD_TILE));
-  MCHK(m, malloc_n(&m->keep, cap));
-  MCHK(m, malloc_n(&m->keep_xyz, cap));
-  MCHK(m, malloc_n(&m->recentred, cap));
+  PFT_HIPCHK(m, pft_dalloc(&m->in_own, cap));
+  PFT_HIPCHK(m, pft_dalloc(&m->xyz, cap));
+  PFT_HIPCHK(m, pft_dalloc(&m->flag, cap));
+  PFT_HIPCHK(m, pft_dalloc(&m->tile, cap / MD_TILE));
+  PFT_HIPCHK(m, pft_dalloc(&m->keep, cap));
+  PFT_HIPCHK(m, pft_dalloc(&m->keep_xyz, cap));
+  PFT_HIPCHK(m, pft_dalloc(&m->recentred, cap));
   m->cap = cap;
   return PFT_OK;
 }
@@ -177,7 +159,7 @@ extern "C" int pft_model_create(int device_id, pft_model** out) {
   if (!ok) m->stream = nullptr;
   for (int k = 0; ok && k < MD_NEV; k++) ok = hipEventCreate(&m->ev[k]) == hipSuccess;
   if (ok)
-    ok = malloc_n(&m->hdr, 1) == hipSuccess &&
+    ok = pft_dalloc(&m->hdr, 1) == hipSuccess &&
          hipHostMalloc(reinterpret_cast<void**>(&m->host_hdr), sizeof(MdHdr), hipHostMallocDefault) == hipSuccess;
   if (ok) ok = ensure_capacity(m, 25000) == PFT_OK;  // the largest cluster the reference keeps
   if (!ok) {
@@ -194,7 +176,7 @@ extern "C" void pft_model_destroy(pft_model* m) {
   if (m->stream) hipStreamSynchronize(m->stream);
   if (m->grid) pft_filter_destroy(m->grid);  // (before the stream it runs on)
   free_buffers(m);
-  free_p(m->hdr);
+  pft_dfree(m->hdr);
   if (m->host_hdr) hipHostFree(m->host_hdr);
   for (hipEvent_t e : m->ev)
     if (e) hipEventDestroy(e);
@@ -236,33 +218,33 @@ static int prepare_common(pft_model* m, const pft_point_xyzrgba* pts, size_t n, 
     m->err = "model preparation: no point left after removeZeroPoints (stage 1): the input cloud is empty";
     return PFT_ERR_NO_INPUT;
   }
-  MCHK(m, hipSetDevice(m->device_id));
+  PFT_HIPCHK(m, hipSetDevice(m->device_id));
   int r = ensure_capacity(m, n);
   if (r != PFT_OK) return r;
   hipStream_t st = m->stream;
   const pft_point_xyzrgba* d_in = pts;
   if (!on_device) {
-    MCHK(m, hipMemcpyAsync(m->in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, st));
+    PFT_HIPCHK(m, hipMemcpyAsync(m->in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, st));
     d_in = m->in_own;
   }
   MdHdr h0 = {};
   h0.first_nonfinite = 0xFFFFFFFFu;
-  MCHK(m, hipMemcpyAsync(m->hdr, &h0, sizeof(MdHdr), hipMemcpyHostToDevice, st));
-  MCHK(m, hipEventRecord(m->ev[0], st));
+  PFT_HIPCHK(m, hipMemcpyAsync(m->hdr, &h0, sizeof(MdHdr), hipMemcpyHostToDevice, st));
+  PFT_HIPCHK(m, hipEventRecord(m->ev[0], st));
   // 1. removeZeroPoints
   pftk_remove_zero_points(st, d_in, (uint32_t)n, m->xyz, m->flag, m->tile, m->keep, m->keep_xyz, &m->hdr->n_nonzero);
-  MCHK(m, hipEventRecord(m->ev[1], st));
+  PFT_HIPCHK(m, hipEventRecord(m->ev[1], st));
   // 2. compute3DCentroid, trans
   hipLaunchKernelGGL(k_md_centroid, dim3(1), dim3(MD_CEN_THREADS), 0, st, m->hdr, (const float4*)m->keep_xyz);
-  MCHK(m, hipEventRecord(m->ev[2], st));
+  PFT_HIPCHK(m, hipEventRecord(m->ev[2], st));
   // 3. transformPointCloud by trans.inverse()
   hipLaunchKernelGGL(k_md_recentre, dim3((uint32_t)((n + MD_THREADS - 1) / MD_THREADS)), dim3(MD_THREADS), 0, st, m->hdr,
                      d_in, (const uint32_t*)m->keep, m->recentred);
-  MCHK(m, hipEventRecord(m->ev[3], st));
-  MCHK(m, hipGetLastError());
-  MCHK(m, hipMemcpyAsync(m->host_hdr, m->hdr, sizeof(MdHdr), hipMemcpyDeviceToHost, st));
-  MCHK(m, hipStreamSynchronize(st));  // the kept count sizes stage 4
-  MCHK(m, hipGetLastError());
+  PFT_HIPCHK(m, hipEventRecord(m->ev[3], st));
+  PFT_HIPCHK(m, hipGetLastError());
+  PFT_HIPCHK(m, hipMemcpyAsync(m->host_hdr, m->hdr, sizeof(MdHdr), hipMemcpyDeviceToHost, st));
+  PFT_HIPCHK(m, hipStreamSynchronize(st));  // the kept count sizes stage 4
+  PFT_HIPCHK(m, hipGetLastError());
   m->res = *m->host_hdr;
   const size_t nz = m->res.n_nonzero;
   if (nz == 0) {
@@ -271,7 +253,7 @@ static int prepare_common(pft_model* m, const pft_point_xyzrgba* pts, size_t n, 
   }
   for (int k = 0; k < 3; k++) {
     float ms = 0.0f;
-    MCHK(m, hipEventElapsedTime(&ms, m->ev[k], m->ev[k + 1]));
+    PFT_HIPCHK(m, hipEventElapsedTime(&ms, m->ev[k], m->ev[k + 1]));
     m->stage_ms[k] = ms;
   }
   m->stage_ms[3] = 0.0;
@@ -355,9 +337,9 @@ static int get_cloud(pft_model* m, const pft_point_xyzrgba* src, size_t cnt, pft
   *n = cnt;
   if (cnt > capacity) return PFT_ERR_CAPACITY;
   if (!host_out) return PFT_ERR_INVALID_ARG;
-  MCHK(m, hipSetDevice(m->device_id));
-  MCHK(m, hipMemcpyAsync(host_out, src, cnt * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, m->stream));
-  MCHK(m, hipStreamSynchronize(m->stream));
+  PFT_HIPCHK(m, hipSetDevice(m->device_id));
+  PFT_HIPCHK(m, hipMemcpyAsync(host_out, src, cnt * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, m->stream));
+  PFT_HIPCHK(m, hipStreamSynchronize(m->stream));
   return PFT_OK;
 }
 

@@ -1,7 +1,7 @@
 // pft_reacquire.hip -- re-acquisition of a lost object (pft_reacquire): K candidate poses -- every
 // centre with every orientation of a lattice -- scored against the frame in the search pft_match uses, and the best one
 // selected, all on the device.  The crop and the tree between k_reacquire_candidates and k_reacquire_score are the handle's
-// own launches (pftk_aabb, pftk_crop, pftk_octree / pftk_octree_sorted), driven by pft_api.hip as pft_eval_weights drives them.
+// own launches (pftk_aabb, pftk_crop, pftk_octree / pftk_octree_sorted), driven by pft_api_features.hip as pft_eval_weights drives them.
 //
 //   k_reacquire_centroids   compute3DCentroid of every cluster of a segmenter (PCL's three serial float chains, the chain of
 //                           k_md_centroid), one workgroup per cluster: the centres of pft_reacquire_from_segmenter

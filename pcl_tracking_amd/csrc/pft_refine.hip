@@ -1,6 +1,6 @@
 // pft_refine.hip -- refinement of a pose against the frame (pft_refine): point-to-point ICP with the
 // search of pft_match as the pairing.  The crop and the tree are built once per call by the handle's own launches
-// (pftk_aabb, pftk_crop, pftk_octree / pftk_octree_sorted), driven by pft_api.hip as pft_reacquire drives them.
+// (pftk_aabb, pftk_crop, pftk_octree / pftk_octree_sorted), driven by pft_api_features.hip as pft_reacquire drives them.
 //
 //   k_refine_init    one lane: the start matrix (the argument, or pose_to_matrix of PftHeader::rep), the state (Q, t) of
 //                    it, the eight shifted copies the box is taken over, the control words

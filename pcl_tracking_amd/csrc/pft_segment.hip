@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "pft_devbuf.h"
 #include "pft_device_utils.h"
 #include "../../include/pft_segment.h"
 
@@ -1074,15 +1075,6 @@ __global__ __launch_bounds__(SG_THREADS) void k_sg_output(uint32_t total, const 
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
-#define SCHK(s, call)                                                \
-  do {                                                               \
-    hipError_t e_ = (call);                                          \
-    if (e_ != hipSuccess) {                                          \
-      (s)->err = std::string(#call) + ": " + hipGetErrorString(e_);  \
-      return PFT_ERR_HIP;                                            \
-    }                                                                \
-  } while (0)
-
 #define SG_NEV 96
 
 struct SgBufs {
@@ -1151,70 +1143,60 @@ struct pft_segment {
   double last_ms = 0.0, stage_ms[PFT_SEGMENT_STAGES] = {};
 };
 
-template <typename T>
-static hipError_t salloc(T** p, size_t n) {
-  return hipMalloc(reinterpret_cast<void**>(p), (n ? n : 1) * sizeof(T));
-}
-template <typename T>
-static void sfree(T*& p) {
-  if (p) hipFree((void*)p);
-  p = nullptr;
-}
-
 static void free_buffers(pft_segment* s) {
   SgBufs& b = s->b;
-  sfree(b.in_own); sfree(b.tx); sfree(b.flag); sfree(b.flag2); sfree(b.tile); sfree(b.tile2); sfree(b.comp_idx);
-  sfree(b.comp_pts); sfree(b.inl_idx); sfree(b.fin_idx); sfree(b.surv_in); sfree(b.spts);
+  pft_dfree(b.in_own); pft_dfree(b.tx); pft_dfree(b.flag); pft_dfree(b.flag2); pft_dfree(b.tile); pft_dfree(b.tile2); pft_dfree(b.comp_idx);
+  pft_dfree(b.comp_pts); pft_dfree(b.inl_idx); pft_dfree(b.fin_idx); pft_dfree(b.surv_in); pft_dfree(b.spts);
   for (int k = 0; k < 2; k++) {
-    sfree(b.key[k]);
-    sfree(b.val[k]);
+    pft_dfree(b.key[k]);
+    pft_dfree(b.val[k]);
   }
-  sfree(b.hist); sfree(b.sorted); sfree(b.cell_start); sfree(b.cell_key); sfree(b.cell_of); sfree(b.parent);
-  sfree(b.label); sfree(b.csize); sfree(b.roots); sfree(b.crank); sfree(b.sizes); sfree(b.bpart); sfree(b.out_idx);
-  sfree(b.out_pts); sfree(b.rnd); sfree(b.refit_part);
+  pft_dfree(b.hist); pft_dfree(b.sorted); pft_dfree(b.cell_start); pft_dfree(b.cell_key); pft_dfree(b.cell_of); pft_dfree(b.parent);
+  pft_dfree(b.label); pft_dfree(b.csize); pft_dfree(b.roots); pft_dfree(b.crank); pft_dfree(b.sizes); pft_dfree(b.bpart); pft_dfree(b.out_idx);
+  pft_dfree(b.out_pts); pft_dfree(b.rnd); pft_dfree(b.refit_part);
   s->cap = 0;
 }
 
 static int ensure_capacity(pft_segment* s, size_t n) {
   if (n <= s->cap) return PFT_OK;
-  if (s->stream) SCHK(s, hipStreamSynchronize(s->stream));
+  if (s->stream) PFT_HIPCHK(s, hipStreamSynchronize(s->stream));
   free_buffers(s);
   size_t cap = n < SG_TILE ? SG_TILE : n;
   cap = (cap + SG_TILE - 1) / SG_TILE * SG_TILE;
   const size_t nt = cap / SG_TILE;
   SgBufs& b = s->b;
-  SCHK(s, salloc(&b.in_own, cap));
-  SCHK(s, salloc(&b.tx, cap));
-  SCHK(s, salloc(&b.flag, cap));
-  SCHK(s, salloc(&b.flag2, cap));
-  SCHK(s, salloc(&b.tile, nt));
-  SCHK(s, salloc(&b.tile2, nt));
-  SCHK(s, salloc(&b.comp_idx, cap));
-  SCHK(s, salloc(&b.comp_pts, cap));
-  SCHK(s, salloc(&b.inl_idx, cap));
-  SCHK(s, salloc(&b.fin_idx, cap));
-  SCHK(s, salloc(&b.surv_in, cap));
-  SCHK(s, salloc(&b.spts, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.in_own, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.tx, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.flag, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.flag2, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.tile, nt));
+  PFT_HIPCHK(s, pft_dalloc(&b.tile2, nt));
+  PFT_HIPCHK(s, pft_dalloc(&b.comp_idx, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.comp_pts, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.inl_idx, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.fin_idx, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.surv_in, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.spts, cap));
   for (int k = 0; k < 2; k++) {
-    SCHK(s, salloc(&b.key[k], cap));
-    SCHK(s, salloc(&b.val[k], cap));
+    PFT_HIPCHK(s, pft_dalloc(&b.key[k], cap));
+    PFT_HIPCHK(s, pft_dalloc(&b.val[k], cap));
   }
-  SCHK(s, salloc(&b.hist, 256 * nt + 256));
-  SCHK(s, salloc(&b.sorted, cap));
-  SCHK(s, salloc(&b.cell_start, cap));
-  SCHK(s, salloc(&b.cell_key, cap));
-  SCHK(s, salloc(&b.cell_of, cap));
-  SCHK(s, salloc(&b.parent, cap));
-  SCHK(s, salloc(&b.label, cap));
-  SCHK(s, salloc(&b.csize, cap));
-  SCHK(s, salloc(&b.roots, cap));
-  SCHK(s, salloc(&b.crank, cap));
-  SCHK(s, salloc(&b.sizes, cap));
-  SCHK(s, salloc(&b.bpart, 6 * 1024));
-  SCHK(s, salloc(&b.out_idx, cap));
-  SCHK(s, salloc(&b.out_pts, cap));
-  SCHK(s, salloc(&b.rnd, cap));
-  SCHK(s, salloc(&b.refit_part, 9 * (cap / SG_RT_TILE + 1)));
+  PFT_HIPCHK(s, pft_dalloc(&b.hist, 256 * nt + 256));
+  PFT_HIPCHK(s, pft_dalloc(&b.sorted, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.cell_start, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.cell_key, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.cell_of, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.parent, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.label, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.csize, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.roots, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.crank, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.sizes, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.bpart, 6 * 1024));
+  PFT_HIPCHK(s, pft_dalloc(&b.out_idx, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.out_pts, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.rnd, cap));
+  PFT_HIPCHK(s, pft_dalloc(&b.refit_part, 9 * (cap / SG_RT_TILE + 1)));
   s->cap = cap;
   return PFT_OK;
 }
@@ -1266,11 +1248,11 @@ extern "C" int pft_segment_create(const pft_segment_config* cfg, pft_segment** o
   if (const char* g = getenv("PFT_SEGMENT_REFIT_GRID")) s->refit_grid = (uint32_t)std::max(0, atoi(g));
   s->hmax = ((uint32_t)cfg->max_iterations + 1u + SG_BATCH - 1u) / SG_BATCH * SG_BATCH;
   if (ok)
-    ok = salloc(&s->hdr, 1) == hipSuccess &&
+    ok = pft_dalloc(&s->hdr, 1) == hipSuccess &&
          hipHostMalloc(reinterpret_cast<void**>(&s->host_hdr), sizeof(SgHdr), hipHostMallocDefault) == hipSuccess &&
-         salloc(&s->smp.mt, MT_N) == hipSuccess && salloc(&s->smp.mk, SG_MAPCAP) == hipSuccess &&
-         salloc(&s->smp.mv, SG_MAPCAP) == hipSuccess && salloc(&s->hyp.sample, 3 * (size_t)s->hmax) == hipSuccess &&
-         salloc(&s->hyp.coef, s->hmax) == hipSuccess && salloc(&s->hyp.count, s->hmax) == hipSuccess;
+         pft_dalloc(&s->smp.mt, MT_N) == hipSuccess && pft_dalloc(&s->smp.mk, SG_MAPCAP) == hipSuccess &&
+         pft_dalloc(&s->smp.mv, SG_MAPCAP) == hipSuccess && pft_dalloc(&s->hyp.sample, 3 * (size_t)s->hmax) == hipSuccess &&
+         pft_dalloc(&s->hyp.coef, s->hmax) == hipSuccess && pft_dalloc(&s->hyp.count, s->hmax) == hipSuccess;
   if (ok) ok = ensure_capacity(s, cfg->max_points ? cfg->max_points : SG_TILE) == PFT_OK;
   if (!ok) {
     pft_segment_destroy(s);
@@ -1284,10 +1266,10 @@ extern "C" void pft_segment_destroy(pft_segment* s) {
   if (!s) return;
   if (s->stream) hipStreamSynchronize(s->stream);
   free_buffers(s);
-  sfree(s->hdr);
+  pft_dfree(s->hdr);
   if (s->host_hdr) hipHostFree(s->host_hdr);
-  sfree(s->smp.mt); sfree(s->smp.mk); sfree(s->smp.mv);
-  sfree(s->hyp.sample); sfree(s->hyp.coef); sfree(s->hyp.count);
+  pft_dfree(s->smp.mt); pft_dfree(s->smp.mk); pft_dfree(s->smp.mv);
+  pft_dfree(s->hyp.sample); pft_dfree(s->hyp.coef); pft_dfree(s->hyp.count);
   for (hipEvent_t e : s->ev)
     if (e) hipEventDestroy(e);
   if (s->own_stream && s->stream) hipStreamDestroy(s->stream);
@@ -1301,11 +1283,11 @@ extern "C" const char* pft_segment_last_error_string(const pft_segment* s) { ret
 static int mark(pft_segment* s, int stage) {
   if (s->nev >= (int)s->ev.size()) {  // (plane rounds only: one apply of the single plane needs at most 3 per batch + 16)
     hipEvent_t e = nullptr;
-    SCHK(s, hipEventCreate(&e));
+    PFT_HIPCHK(s, hipEventCreate(&e));
     s->ev.push_back(e);
     s->ev_stage.push_back(0);
   }
-  SCHK(s, hipEventRecord(s->ev[s->nev], s->stream));
+  PFT_HIPCHK(s, hipEventRecord(s->ev[s->nev], s->stream));
   s->ev_stage[s->nev] = stage;
   s->nev++;
   return PFT_OK;
@@ -1319,9 +1301,9 @@ static int mark(pft_segment* s, int stage) {
 enum { ST_COMPACT = 0, ST_SAMPLE, ST_SCORE, ST_REPLAY, ST_REFIT, ST_CLUSTER, ST_OUTPUT };
 
 static int read_hdr(pft_segment* s) {
-  SCHK(s, hipMemcpyAsync(s->host_hdr, s->hdr, sizeof(SgHdr), hipMemcpyDeviceToHost, s->stream));
-  SCHK(s, hipStreamSynchronize(s->stream));
-  SCHK(s, hipGetLastError());
+  PFT_HIPCHK(s, hipMemcpyAsync(s->host_hdr, s->hdr, sizeof(SgHdr), hipMemcpyDeviceToHost, s->stream));
+  PFT_HIPCHK(s, hipStreamSynchronize(s->stream));
+  PFT_HIPCHK(s, hipGetLastError());
   return PFT_OK;
 }
 
@@ -1334,7 +1316,7 @@ static int plane_stage(pft_segment* s, const SgParams& p, const SgHyp& hyp, cons
   SgBufs& b = s->b;
   const uint32_t* n_valid = &s->hdr->n_valid;
   // every launch after the deciding batch returns at once
-  SCHK(s, hipMemsetAsync(hyp.count, 0, s->hmax * sizeof(uint32_t), st));
+  PFT_HIPCHK(s, hipMemsetAsync(hyp.count, 0, s->hmax * sizeof(uint32_t), st));
   const uint32_t nscore = (n_max + SG_THREADS * SG_SCORE_PTS - 1) / (SG_THREADS * SG_SCORE_PTS);
   for (uint32_t bt = 0; bt * SG_BATCH < s->hmax; bt++) {
     hipLaunchKernelGGL(k_sg_sample, dim3(1), dim3(SG_THREADS), 0, st, p, s->hdr, s->smp, hyp, pts, bt);
@@ -1471,7 +1453,7 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
   h0.best_count = -INT32_MAX;
   h0.best_h = -1;
   s->nev = 0;
-  SCHK(s, hipMemcpyAsync(s->hdr, &h0, sizeof(SgHdr), hipMemcpyHostToDevice, st));
+  PFT_HIPCHK(s, hipMemcpyAsync(s->hdr, &h0, sizeof(SgHdr), hipMemcpyHostToDevice, st));
   MARK(ST_COMPACT);
   // 1 + 2: transform, removeZeroPoints, compaction (indices into the input, transformed points)
   hipLaunchKernelGGL(k_sg_zero, dim3(ntiles), dim3(SG_THREADS), 0, st, p, d_in, b.tx, b.flag, b.tile);
@@ -1563,7 +1545,7 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
     hipLaunchKernelGGL(k_sg_link, dim3(nlink), dim3(SG_THREADS), 0, st, p, (const SgHdr*)s->hdr,
                        (const uint32_t*)b.cell_start, (const uint32_t*)b.cell_key, sval, (const float4*)b.sorted, m,
                        b.parent);
-    SCHK(s, hipMemsetAsync(b.csize, 0, m * sizeof(uint32_t), st));
+    PFT_HIPCHK(s, hipMemsetAsync(b.csize, 0, m * sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_sg_label, dim3(mb), dim3(SG_THREADS), 0, st, m, b.parent, b.label, b.csize);
     hipLaunchKernelGGL(k_sg_roots, dim3(mt), dim3(SG_THREADS), 0, st, p, m, (const uint32_t*)b.label,
                        (const uint32_t*)b.csize, b.flag, b.tile);
@@ -1582,7 +1564,7 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
       int kbits = 0;
       while (kbits < 32 && (1ull << kbits) <= (uint64_t)(p.max_size - std::min(p.min_size, p.max_size))) kbits++;
       cur = pftk_radix_sort_pairs(st, b.key, b.val, nc, kbits, b.hist);
-      SCHK(s, hipMemsetAsync(b.crank, 0xFF, m * sizeof(uint32_t), st));
+      PFT_HIPCHK(s, hipMemsetAsync(b.crank, 0xFF, m * sizeof(uint32_t), st));
       hipLaunchKernelGGL(k_sg_rank, dim3(nb), dim3(SG_THREADS), 0, st, nc, (const uint32_t*)b.val[cur],
                          (const uint32_t*)b.csize, b.crank, b.sizes);
       hipLaunchKernelGGL(k_sg_member_keys, dim3(mb), dim3(SG_THREADS), 0, st, m, nc, (const uint32_t*)b.label,
@@ -1592,8 +1574,8 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
       cur = pftk_radix_sort_pairs(st, b.key, b.val, m, rbits, b.hist);
       MARK(ST_CLUSTER);
       s->sizes.resize(nc);
-      SCHK(s, hipMemcpyAsync(s->sizes.data(), b.sizes, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      SCHK(s, hipStreamSynchronize(st));
+      PFT_HIPCHK(s, hipMemcpyAsync(s->sizes.data(), b.sizes, nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+      PFT_HIPCHK(s, hipStreamSynchronize(st));
       MARK(-1);
       for (uint32_t k = 0; k < nc; k++) total += s->sizes[k];
       hipLaunchKernelGGL(k_sg_output, dim3((total + SG_THREADS - 1) / SG_THREADS), dim3(SG_THREADS), 0, st, total,
@@ -1601,7 +1583,7 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
       MARK(ST_OUTPUT);
     }
   }
-  SCHK(s, hipGetLastError());
+  PFT_HIPCHK(s, hipGetLastError());
   r = read_hdr(s);
   if (r != PFT_OK) return r;
   s->res = *H;
@@ -1626,7 +1608,7 @@ static int run_pipeline(pft_segment* s, const pft_point_xyzrgba* d_in, uint32_t 
   for (int k = 0; k < PFT_SEGMENT_STAGES; k++) s->stage_ms[k] = 0.0;
   for (int e = 1; e < s->nev; e++) {
     float ms = 0.0f;
-    SCHK(s, hipEventElapsedTime(&ms, s->ev[e - 1], s->ev[e]));
+    PFT_HIPCHK(s, hipEventElapsedTime(&ms, s->ev[e - 1], s->ev[e]));
     if (s->ev_stage[e] < 0) continue;  // the gap spans a host synchronisation
     s->stage_ms[s->ev_stage[e]] += ms;
     s->last_ms += ms;
@@ -1638,7 +1620,7 @@ static int apply_common(pft_segment* s, const pft_point_xyzrgba* pts, size_t n, 
   if (!s || (!pts && n)) return PFT_ERR_INVALID_ARG;
   if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
   s->have_result = false;
-  SCHK(s, hipSetDevice(s->cfg.device_id));
+  PFT_HIPCHK(s, hipSetDevice(s->cfg.device_id));
   if (n == 0) {  // empty input cloud: no plane, no clusters
     s->res = SgHdr();
     s->res.best_h = -1;
@@ -1657,7 +1639,7 @@ static int apply_common(pft_segment* s, const pft_point_xyzrgba* pts, size_t n, 
   if (r != PFT_OK) return r;
   const pft_point_xyzrgba* d_in = pts;
   if (!on_device) {
-    if (n) SCHK(s, hipMemcpyAsync(s->b.in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, s->stream));
+    if (n) PFT_HIPCHK(s, hipMemcpyAsync(s->b.in_own, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, s->stream));
     d_in = s->b.in_own;
   }
   r = run_pipeline(s, d_in, (uint32_t)n);
@@ -1752,17 +1734,17 @@ extern "C" int pft_segment_get_plane_round_inliers(pft_segment* s, size_t round,
     hipLaunchKernelGGL(k_sg_emit, dim3(nt), dim3(SG_THREADS), 0, s->stream, (const uint8_t*)s->b.flag, nin,
                        (const uint32_t*)nullptr, (const uint32_t*)s->b.tile, (const uint32_t*)nullptr,
                        reinterpret_cast<uint32_t*>(tmp), (const float4*)nullptr, (float4*)nullptr);
-    SCHK(s, hipGetLastError());
+    PFT_HIPCHK(s, hipGetLastError());
     src = tmp;
   } else if (which == 1) {  // crank is scratch once an apply has finished
     int32_t* tmp = reinterpret_cast<int32_t*>(s->b.crank);
     hipLaunchKernelGGL(k_sg_map_idx, dim3((cnt + 255) / 256), dim3(256), 0, s->stream, cnt,
                        (const uint32_t*)s->b.inl_idx, (const uint32_t*)s->b.comp_idx, tmp);
-    SCHK(s, hipGetLastError());
+    PFT_HIPCHK(s, hipGetLastError());
     src = tmp;
   }
-  SCHK(s, hipMemcpyAsync(host_idx, src, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-  SCHK(s, hipStreamSynchronize(s->stream));
+  PFT_HIPCHK(s, hipMemcpyAsync(host_idx, src, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  PFT_HIPCHK(s, hipStreamSynchronize(s->stream));
   return PFT_OK;
 }
 
@@ -1781,17 +1763,17 @@ extern "C" int pft_segment_set_plane_rounds(pft_segment* s, int max_planes, doub
     return PFT_ERR_INVALID_ARG;
   }
   if ((uint32_t)max_planes > s->hyp_rounds) {  // one set of hypothesis buffers per round
-    SCHK(s, hipSetDevice(s->cfg.device_id));
-    SCHK(s, hipStreamSynchronize(s->stream));
+    PFT_HIPCHK(s, hipSetDevice(s->cfg.device_id));
+    PFT_HIPCHK(s, hipStreamSynchronize(s->stream));
     SgHyp nh = {};
     const size_t cnt = (size_t)s->hmax * (size_t)max_planes;
-    if (salloc(&nh.sample, 3 * cnt) != hipSuccess || salloc(&nh.coef, cnt) != hipSuccess ||
-        salloc(&nh.count, cnt) != hipSuccess) {
-      sfree(nh.sample); sfree(nh.coef); sfree(nh.count);
+    if (pft_dalloc(&nh.sample, 3 * cnt) != hipSuccess || pft_dalloc(&nh.coef, cnt) != hipSuccess ||
+        pft_dalloc(&nh.count, cnt) != hipSuccess) {
+      pft_dfree(nh.sample); pft_dfree(nh.coef); pft_dfree(nh.count);
       s->err = "pft_segment_set_plane_rounds: hipMalloc of the rounds' hypothesis buffers failed";
       return PFT_ERR_HIP;
     }
-    sfree(s->hyp.sample); sfree(s->hyp.coef); sfree(s->hyp.count);
+    pft_dfree(s->hyp.sample); pft_dfree(s->hyp.coef); pft_dfree(s->hyp.count);
     s->hyp = nh;
     s->hyp_rounds = (uint32_t)max_planes;
     s->have_result = false;  // the last apply's hypotheses went with the old buffers
@@ -1851,8 +1833,8 @@ extern "C" int pft_segment_get_cluster_indices(pft_segment* s, int32_t* host_idx
   if (s->res.n_total > capacity) return PFT_ERR_CAPACITY;
   if (!s->res.n_total) return PFT_OK;
   if (!host_idx) return PFT_ERR_INVALID_ARG;
-  SCHK(s, hipMemcpyAsync(host_idx, s->b.out_idx, s->res.n_total * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-  SCHK(s, hipStreamSynchronize(s->stream));
+  PFT_HIPCHK(s, hipMemcpyAsync(host_idx, s->b.out_idx, s->res.n_total * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  PFT_HIPCHK(s, hipStreamSynchronize(s->stream));
   return PFT_OK;
 }
 
@@ -1864,9 +1846,9 @@ extern "C" int pft_segment_get_cluster_points(pft_segment* s, pft_point_xyzrgba*
   if (s->res.n_total > capacity) return PFT_ERR_CAPACITY;
   if (!s->res.n_total) return PFT_OK;
   if (!host_pts) return PFT_ERR_INVALID_ARG;
-  SCHK(s, hipMemcpyAsync(host_pts, s->b.out_pts, s->res.n_total * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost,
+  PFT_HIPCHK(s, hipMemcpyAsync(host_pts, s->b.out_pts, s->res.n_total * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost,
                          s->stream));
-  SCHK(s, hipStreamSynchronize(s->stream));
+  PFT_HIPCHK(s, hipStreamSynchronize(s->stream));
   return PFT_OK;
 }
 
@@ -1904,7 +1886,7 @@ extern "C" int pft_debug_segment_round_hypotheses(pft_segment* s, size_t round, 
   if (cnt > capacity) return PFT_ERR_CAPACITY;
   if (!cnt) return PFT_OK;
   if (!samples || !counts) return PFT_ERR_INVALID_ARG;
-  SCHK(s, hipMemcpy(samples, s->hyp.sample + 3 * off, 3 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
-  SCHK(s, hipMemcpy(counts, s->hyp.count + off, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  PFT_HIPCHK(s, hipMemcpy(samples, s->hyp.sample + 3 * off, 3 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
+  PFT_HIPCHK(s, hipMemcpy(counts, s->hyp.count + off, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return PFT_OK;
 }

@@ -1,4 +1,4 @@
-"""The level of k_likelihood's ancestor table, chosen per build (pcl_tracking_amd/csrc/pft_api.hip pick_anc_up).
+"""The level of k_likelihood's ancestor table, chosen per build (pcl_tracking_amd/csrc/pft_frame.hip pick_anc_up).
 
 The table of a tree of depth D lies at level D - 1 where that window fits its 2^18 entries, else at D - 2, else there is none;
 the host picks the level from the window sizes the PREVIOUS build published, hands it to the builder and launches the
