@@ -593,6 +593,10 @@ int pft_debug_resample_prefix(pft_tracker* t, const pft_particle* old, size_t n_
                               uint32_t epoch, uint32_t id_offset, size_t n_local, int instance, pft_particle* out,
                               float* mats12);
 int pft_debug_pose_to_matrix(pft_tracker* t, const pft_particle* p, size_t n, float* m12);
+/* the reference side's colour conversion alone: the kernel pft_set_reference packs its cloud with, in the handle's
+ * hsv_pcl180_argorder, on buffers of its own (the handle's reference cloud stays as it is; no hull is taken).
+ * hsv_out receives n float4 records {h / 180.0f, s / 255.0f, v / 255.0f, 0} */
+int pft_debug_pack_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, float* hsv_out);
 /* KLD resample alone: n_old particles + their explicit alias table (a, q) + motion -> the new particle set
  * (capacity maximum_particle_num), their 6-D bins, the new count and the number of distinct bins.  a == NULL and
  * q == NULL: no table -- the prefix-sum form is built from old's weights as given and the product instance is launched */

@@ -66,6 +66,8 @@ def lib():
     L.orc_rgb2hsv_int.argtypes = [C.c_int] * 3 + [P(C.c_int)] * 3
     L.orc_hsv_coherence.argtypes = [P(Config), u32, u32]
     L.orc_hsv_coherence.restype = f64
+    L.orc_hsv_pack_many.argtypes = [P(Config), vp, sz, vp]
+    L.orc_hsv_floats_many.argtypes = [P(Config), vp, sz, vp]
     L.orc_distance_coherence.argtypes = [P(Config), vp, vp]
     L.orc_distance_coherence.restype = f64
     L.orc_octree_build.argtypes = [vp, sz, f64, C.c_int]
@@ -183,6 +185,22 @@ def rgb2hsv_int(r, g, b):
 
 def hsv_coherence(cfg, src_rgba, tgt_rgba):
     return lib().orc_hsv_coherence(C.byref(cfg), int(src_rgba), int(tgt_rgba))
+
+
+def hsv_pack_many(cfg, rgba):
+    """h | s << 8 | v << 16 of the integer RGB2HSV for every colour, in cfg's argument order (the alpha byte is ignored)"""
+    rgba = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+    out = np.zeros(len(rgba), np.uint32)
+    lib().orc_hsv_pack_many(C.byref(cfg), _ptr(rgba), len(rgba), _ptr(out))
+    return out
+
+
+def hsv_floats_many(cfg, rgba):
+    """(n, 3) float32: h / 180.0f, s / 255.0f, v / 255.0f as HSVColorCoherence compares them"""
+    rgba = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+    out = np.zeros((len(rgba), 3), np.float32)
+    lib().orc_hsv_floats_many(C.byref(cfg), _ptr(rgba), len(rgba), _ptr(out))
+    return out
 
 
 def distance_coherence(cfg, s, t):

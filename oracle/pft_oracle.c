@@ -157,6 +157,23 @@ static inline void hsv_of_rgba(const orc_config_t* c, uint32_t rgba, float* h, f
     orc_rgb2hsv(Red, Green, Blue, h, s, v);
 }
 
+/* bulk forms for sweeps over many colours: the routines above in a loop, the argument order as hsv_of_rgba */
+void orc_hsv_pack_many(const orc_config_t* c, const uint32_t* rgba, size_t n, uint32_t* out) {
+  for (size_t i = 0; i < n; i++) {
+    int Blue = (int)(rgba[i] & 0xff), Green = (int)((rgba[i] >> 8) & 0xff), Red = (int)((rgba[i] >> 16) & 0xff);
+    int h, s, v;
+    if (c->hsv_pcl180_argorder)
+      orc_rgb2hsv_int(Red, Blue, Green, &h, &s, &v);
+    else
+      orc_rgb2hsv_int(Red, Green, Blue, &h, &s, &v);
+    out[i] = (uint32_t)h | (uint32_t)s << 8 | (uint32_t)v << 16;
+  }
+}
+
+void orc_hsv_floats_many(const orc_config_t* c, const uint32_t* rgba, size_t n, float* out3) {
+  for (size_t i = 0; i < n; i++) hsv_of_rgba(c, rgba[i], &out3[3 * i], &out3[3 * i + 1], &out3[3 * i + 2]);
+}
+
 double orc_hsv_coherence(const orc_config_t* c, uint32_t src_rgba, uint32_t tgt_rgba) {
   float source_h, source_s, source_v, target_h, target_s, target_v;
   hsv_of_rgba(c, src_rgba, &source_h, &source_s, &source_v);

@@ -83,6 +83,11 @@ void orc_rgb2hsv(int r, int g, int b, float* fh, float* fs, float* fv);
 /* integer h (0..179), s (0..255), v (0..255) of the same routine, for packing tests */
 void orc_rgb2hsv_int(int r, int g, int b, int* h, int* s, int* v);
 double orc_hsv_coherence(const orc_config_t* c, uint32_t src_rgba, uint32_t tgt_rgba);
+/* the same conversion over n colours (c->hsv_pcl180_argorder as in orc_hsv_coherence): out[i] = h | s << 8 | v << 16 of
+ * orc_rgb2hsv_int, and out3[3 * i ..] = the floats h / 180.0f, s / 255.0f, v / 255.0f of orc_rgb2hsv; the alpha byte is
+ * ignored */
+void orc_hsv_pack_many(const orc_config_t* c, const uint32_t* rgba, size_t n, uint32_t* out);
+void orc_hsv_floats_many(const orc_config_t* c, const uint32_t* rgba, size_t n, float* out3);
 /* ---- A7a: DistanceCoherence (tracking/impl/distance_coherence.hpp) ---- */
 double orc_distance_coherence(const orc_config_t* c, const orc_point_t* s, const orc_point_t* t);
 

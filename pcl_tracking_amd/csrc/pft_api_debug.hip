@@ -578,6 +578,26 @@ extern "C" int pft_debug_pose_to_matrix(pft_tracker* t, const pft_particle* p, s
   return PFT_OK;
 }
 
+// k_pack_reference (the reference side's RGB2HSV and its float triples) on buffers of its own: the handle's reference cloud
+// is not touched and no hull is taken
+extern "C" int pft_debug_pack_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, float* hsv_out) {
+  if (!t || !pts || !n || !hsv_out) return PFT_ERR_INVALID_ARG;
+  if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
+  hipSetDevice(t->cfg.device_id);
+  DevBuf<pft_point_xyzrgba> d_pts;
+  DevBuf<float4> d_xyz, d_hsv;
+  PFTT_GROW(t, d_pts.alloc(n) && d_xyz.alloc(n) && d_hsv.alloc(n));
+  hipError_t e = hipMemcpyAsync(d_pts, pts, n * sizeof(pft_point_xyzrgba), hipMemcpyHostToDevice, t->stream);
+  if (e == hipSuccess) {
+    pftk_pack_reference(t->stream, d_pts, (uint32_t)n, t->prm.hsv_argorder, d_xyz, d_hsv);
+    e = hipMemcpyAsync(hsv_out, d_hsv, n * sizeof(float4), hipMemcpyDeviceToHost, t->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
+  if (e == hipSuccess) e = hipGetLastError();
+  PFT_HIPCHK(t, e);
+  return PFT_OK;
+}
+
 extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a,
                                       const double* q, const pft_particle* motion, uint32_t epoch, pft_particle* out,
                                       int32_t* bins6, uint32_t* n_out, uint32_t* k_out) {

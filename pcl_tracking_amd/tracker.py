@@ -935,6 +935,15 @@ class ParticleFilterTracker:
         self._check(self._L.pft_debug_pose_to_matrix(self._h, _ptr(p), len(p), _ptr(m)))
         return m.reshape(len(p), 3, 4)
 
+    def debugPackReference(self, cloud):
+        """test hook: the reference side's colour conversion (k_pack_reference, the handle's argument order) on an explicit
+        cloud -> (n, 4) float32 records h / 180, s / 255, v / 255, 0.  The handle's reference cloud is not touched"""
+        self._ensure()
+        cloud = np.ascontiguousarray(cloud, POINT_DTYPE)
+        out = np.zeros((len(cloud), 4), np.float32)
+        self._check(self._L.pft_debug_pack_reference(self._h, _ptr(cloud), len(cloud), _ptr(out)))
+        return out
+
     # ---- per-kernel HIP-event timing ----
     def profileEnable(self, on=True):
         self._ensure()

@@ -74,8 +74,21 @@ def other_trans():
     return t
 
 
-def make(gpu, M=300, kld=False, seed=3, iterations=2, trans=None, reference=None, cd=None):
+def make(gpu, M=300, kld=False, seed=3, iterations=2, trans=None, reference=None, cd=None, coherence=None):
+    """coherence: dict(hsv_weight, h_weight, s_weight, v_weight) in place of the reference's 0.1, 1, 1, 0"""
     t = gpu.make_reference_tracker(particle_num=P, seed=seed, kld=kld, change_detector=cd)
+    if coherence:
+        coh = gpu.ApproxNearestPairPointCloudCoherence()
+        coh.addPointCoherence(gpu.DistanceCoherence())
+        hc = gpu.HSVColorCoherence()
+        hc.setWeight(coherence.get("hsv_weight", 0.1))
+        hc.setHWeight(coherence.get("h_weight", 1.0))
+        hc.setSWeight(coherence.get("s_weight", 1.0))
+        hc.setVWeight(coherence.get("v_weight", 0.0))
+        coh.addPointCoherence(hc)
+        coh.setSearchMethod(gpu.OctreeSearch(0.01))
+        coh.setMaximumDistance(0.1)
+        t.setCloudCoherence(coh)
     if kld:
         t.setMaximumParticleNum(100)
     t.setIterationNum(iterations)
@@ -84,8 +97,8 @@ def make(gpu, M=300, kld=False, seed=3, iterations=2, trans=None, reference=None
     return t
 
 
-def oracle_cfg(orc):
-    return orc.default_config(particle_num=P, threads=0, emulate_pcl_alloc=0)
+def oracle_cfg(orc, coherence=None):
+    return orc.default_config(particle_num=P, threads=0, emulate_pcl_alloc=0, **(coherence or {}))
 
 
 def get_bbox(t):
@@ -101,9 +114,9 @@ def step(t, cloud, match=True):
         t.computeMatch()
 
 
-def oracle_stats(orc, t, reference, cloud, st):
+def oracle_stats(orc, t, reference, cloud, st, coherence=None):
     """the oracle's search for the device's own transform and crop box, turned into pft_match's outputs by the model"""
-    cfg = oracle_cfg(orc)
+    cfg = oracle_cfg(orc, coherence)
     o = orc.Tracker(cfg)
     o.set_reference(reference)
     o.set_input(cloud)
@@ -111,10 +124,10 @@ def oracle_stats(orc, t, reference, cloud, st):
     return E, mm.stats(orc, cfg, reference, st.transform, cloud, E["nn_idx"][0], E["nn_d2"][0], E["crop_idx"])
 
 
-def check_against_oracle(orc, t, reference, cloud, label):
+def check_against_oracle(orc, t, reference, cloud, label, coherence=None):
     st = t.getMatch()
     idx, d2 = t.getMatchPairs()
-    E, want = oracle_stats(orc, t, reference, cloud, st)
+    E, want = oracle_stats(orc, t, reference, cloud, st, coherence)
     M = len(reference)
     assert st.evaluated and st.n_reference == M and len(idx) == M and len(d2) == M, label
     assert st.n_crop == want["n_crop"], label
@@ -191,6 +204,30 @@ def test_match_on_a_tree_deeper_than_ten_levels(gpu, orc):
         st, want, E = check_against_oracle(orc, t, ref, cloud, "deep frame %d" % f)
         assert E["octree_depth"] > 10
         assert st.n_crop == len(cloud)
+    t.close()
+
+
+@pytest.mark.parametrize("coherence", [dict(hsv_weight=4.0, v_weight=1.0),
+                                       dict(hsv_weight=4.0, h_weight=0.5, s_weight=2.0, v_weight=1.0)], ids=["hsv111", "hsv0.5_2_1"])
+def test_match_pair_values_on_edge_colours(gpu, orc, coherence):
+    """mt_pair_value (k_match; k_reacquire_score calls the same function) on the colours of tests/colour_cases.py: the
+    reference cycles REFS, the frame holds the same locations coloured by TARGETS, permuted; hsv_weight 4 and v_weight 1
+    make every channel count, and three different channel weights tell the channels apart.  The sums are compared in
+    double, so one wrong term shows"""
+    import colour_cases as cc
+
+    ref, cloud = scattered(256, 2.0, 5)  # (248 of the frame's locations and the corners of their box)
+    rrgba, trgba = cc.refs()[1], cc.targets()[1]
+    ref["rgba"] = rrgba[np.arange(256) % len(rrgba)]
+    cloud["rgba"] = trgba[np.random.default_rng(7).permutation(256)]
+    t = make(gpu, reference=ref, trans=np.eye(4, dtype=np.float32), coherence=coherence)
+    for f in range(2):
+        step(t, cloud)
+        st, want, E = check_against_oracle(orc, t, ref, cloud, "colours frame %d" % f, coherence)
+        print("colours frame %d: %d of 256 matched, coherence %.6f" % (f, st.n_matched, st.coherence))
+        assert st.n_crop == len(cloud) and st.n_matched >= 128
+        # colours that matter: the sum is well below the count of matched pairs
+        assert st.coherence < 0.9 * st.n_matched
     t.close()
 
 
