@@ -577,6 +577,9 @@ void pft_debug_set_ablate(pft_tracker* t, int mask);
 /* diagnostic: resident likelihood workgroups per CU according to the HIP occupancy API */
 int pft_debug_likelihood_occupancy(void);
 int pft_debug_normalize(pft_tracker* t, float* w_inout, size_t n, double* fit_ratio);
+/* normalizeWeight with the raw weights formed in the same launch from n rows of nchunk likelihood partial sums (row-major) */
+int pft_debug_normalize_partials(pft_tracker* t, const double* partial, size_t nchunk, size_t n, float* w_out,
+                                 double* fit_ratio);
 int pft_debug_alias(pft_tracker* t, const float* w, size_t n, int32_t* a, double* q);
 int pft_debug_weighted_mean(pft_tracker* t, const pft_particle* p, size_t n, pft_particle* out);
 int pft_debug_init_particles(pft_tracker* t, const pft_particle* rep, uint32_t id_offset, size_t n_local,

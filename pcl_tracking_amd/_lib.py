@@ -224,6 +224,7 @@ SYMBOLS = [
     ("pft_debug_aabb_support_subset", C.c_int, [_vp, C.c_size_t, _vp, _vp]),
     ("pft_debug_likelihood_occupancy", C.c_int, []),
     ("pft_debug_normalize", C.c_int, [_vp, _vp, _sz, _P(_f64)]),
+    ("pft_debug_normalize_partials", C.c_int, [_vp, _vp, _sz, _sz, _vp, _P(_f64)]),
     ("pft_debug_alias", C.c_int, [_vp, _vp, _sz, _vp, _vp]),
     ("pft_debug_weighted_mean", C.c_int, [_vp, _vp, _sz, _vp]),
     ("pft_debug_init_particles", C.c_int, [_vp, _vp, _u32, _sz, _vp]),

@@ -402,12 +402,18 @@ struct DbgPop {
   DevBuf<int32_t> list;
   DevBuf<double> pref;
   DevBuf<uint32_t> pos;
+  DevBuf<double> rows;
 };
 
+// partial != null: the raw weights are first formed from the n x nchunk likelihood partial sums given (from_partials)
 static int dbg_population(pft_tracker* t, std::vector<pft_particle>& host, int norm, int mean, int alias, DbgPop& b,
-                          PftHeader* hout) {
+                          PftHeader* hout, const double* partial = nullptr, uint32_t nchunk = 0) {
   const size_t n = host.size();
   if (n > PFT_MAX_PARTICLES) return PFT_ERR_CAPACITY;
+  if (partial) {
+    PFTT_GROW(t, b.rows.alloc(n * nchunk));
+    PFT_HIPCHK(t, hipMemcpyAsync(b.rows, partial, n * nchunk * sizeof(double), hipMemcpyHostToDevice, t->stream));
+  }
   PFTT_GROW(t, b.part.alloc(n));
   PFTT_GROW(t, b.a.alloc(n));
   PFTT_GROW(t, b.q.alloc(n));
@@ -424,7 +430,13 @@ static int dbg_population(pft_tracker* t, std::vector<pft_particle>& host, int n
   d.alias_pref = b.pref;
   d.alias_pos = b.pos;
   d.hdr = t->d_dbg_hdr;
-  pftk_population(t->stream, t->prm, d, (uint32_t)n, 0, norm, mean, alias);
+  PftParams prm = t->prm;
+  if (partial) {
+    d.partial = b.rows;
+    d.raw_w = nullptr;
+    prm.nchunk = nchunk;
+  }
+  pftk_population(t->stream, prm, d, (uint32_t)n, partial ? 1 : 0, norm, mean, alias);
   if (alias) pftk_alias_materialize(t->stream, d, (uint32_t)n, b.a, b.q);
   PFT_HIPCHK(t, hipMemcpyAsync(host.data(), b.part, n * sizeof(pft_particle), hipMemcpyDeviceToHost, t->stream));
   if (hout) PFT_HIPCHK(t, hipMemcpyAsync(hout, t->d_dbg_hdr, sizeof(PftHeader), hipMemcpyDeviceToHost, t->stream));
@@ -441,6 +453,20 @@ extern "C" int pft_debug_normalize(pft_tracker* t, float* w, size_t n, double* f
   DbgPop b;
   PftHeader hd;
   int r = dbg_population(t, h, 1, 0, 0, b, &hd);
+  if (r != PFT_OK) return r;
+  for (size_t i = 0; i < n; i++) w[i] = h[i].weight;
+  if (fit_ratio) *fit_ratio = hd.fit_ratio;
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_normalize_partials(pft_tracker* t, const double* partial, size_t nchunk, size_t n, float* w,
+                                            double* fit_ratio) {
+  if (!t || !partial || !nchunk || nchunk > 0xffffu || !w || !n) return PFT_ERR_INVALID_ARG;
+  std::vector<pft_particle> h(n);
+  memset(h.data(), 0, n * sizeof(pft_particle));
+  DbgPop b;
+  PftHeader hd;
+  int r = dbg_population(t, h, 1, 0, 0, b, &hd, partial, (uint32_t)nchunk);
   if (r != PFT_OK) return r;
   for (size_t i = 0; i < n; i++) w[i] = h[i].weight;
   if (fit_ratio) *fit_ratio = hd.fit_ratio;

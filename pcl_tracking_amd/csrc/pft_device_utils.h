@@ -44,6 +44,98 @@ __device__ __forceinline__ double wave_sum_lane63(double v) {
   return v;
 }
 
+// ---- wave reductions and scans with DPP moves for the small latency-bound kernels (population, resample, crop): a
+// __shfl of a double is two trips through the LDS crossbar and each step waits for the last; a DPP move is a VALU
+// instruction.  Steps 1, 2: quad_perm; 4: row_half_mirror (the quads are uniform by then, so the mirrored lane holds the
+// partner quad's value); 8: row_mirror; 16: row_bcast15 into rows 1, 3; 32: row_bcast31 into rows 2, 3.  Every lane of
+// the wave must be active.  The *_lane63 forms are valid in lane 63 ONLY (that lane then writes the wave's LDS slot); the
+// float and integer forms broadcast lane 63 with v_readlane.
+// The adjacent-pair tree of the specification (T(k+1)[i] = Tk[2i] + Tk[2i+1]): partner distance 1, 2, 4, 8,
+// 16, 32 in that order, as the __shfl_xor butterfly it replaces; only the operand order inside an add differs (commutative).
+__device__ __forceinline__ double wave_tree_sum_lane63(double v) {
+  v += dpp_move_f64<0xb1, 0xf>(v);   // quad_perm [1,0,3,2]
+  v += dpp_move_f64<0x4e, 0xf>(v);   // quad_perm [2,3,0,1]
+  v += dpp_move_f64<0x141, 0xf>(v);  // row_half_mirror
+  v += dpp_move_f64<0x140, 0xf>(v);  // row_mirror
+  v += dpp_move_f64<0x142, 0xa>(v);  // row_bcast15 into rows 1 and 3
+  v += dpp_move_f64<0x143, 0xc>(v);  // row_bcast31 into rows 2 and 3
+  return v;
+}
+
+// min / max of a double (fmin / fmax: a NaN operand is ignored, -0 < +0; both commute, so the pairing above gives the
+// butterfly's bits)
+template <bool MAX>
+__device__ __forceinline__ double wave_minmax_lane63(double v) {
+#define PFT_MM_STEP(CTRL, MASK)                     \
+  do {                                              \
+    const double o_ = dpp_move_f64<CTRL, MASK>(v);  \
+    v = MAX ? fmax(v, o_) : fmin(v, o_);            \
+  } while (0)
+  PFT_MM_STEP(0xb1, 0xf);
+  PFT_MM_STEP(0x4e, 0xf);
+  PFT_MM_STEP(0x141, 0xf);
+  PFT_MM_STEP(0x140, 0xf);
+  PFT_MM_STEP(0x142, 0xa);
+  PFT_MM_STEP(0x143, 0xc);
+#undef PFT_MM_STEP
+  return v;
+}
+// min / max of a float in every lane (fminf / fmaxf as wave_min / wave_max below: NaN operands are ignored; the minimum
+// of a set does not depend on the pairing).  Lanes a step does not reach read their own value.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_move_f32(float v) {
+  const int b = (int)__float_as_uint(v);
+  return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(b, b, CTRL, ROW_MASK, 0xf, false));
+}
+// the value of lane L of the caller's quad (quad_perm [L,L,L,L]: __shfl(v, (lane & ~3) + L) without the LDS trip)
+template <int L>
+__device__ __forceinline__ float quad_bcast(float v) { return dpp_move_f32<L * 0x55, 0xf>(v); }
+template <bool MAX>
+__device__ __forceinline__ float wave_minmax_dpp(float v) {
+#define PFT_MM_STEP(CTRL, MASK)                    \
+  do {                                             \
+    const float o_ = dpp_move_f32<CTRL, MASK>(v);  \
+    v = MAX ? fmaxf(v, o_) : fminf(v, o_);         \
+  } while (0)
+  PFT_MM_STEP(0xb1, 0xf);
+  PFT_MM_STEP(0x4e, 0xf);
+  PFT_MM_STEP(0x141, 0xf);
+  PFT_MM_STEP(0x140, 0xf);
+  PFT_MM_STEP(0x142, 0xa);
+  PFT_MM_STEP(0x143, 0xc);
+#undef PFT_MM_STEP
+  return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), 63));
+}
+__device__ __forceinline__ float wave_min_dpp(float v) { return wave_minmax_dpp<false>(v); }
+__device__ __forceinline__ float wave_max_dpp(float v) { return wave_minmax_dpp<true>(v); }
+
+// Inclusive prefix scan of a uint32_t (modular addition: any association gives the same word): Hillis-Steele inside the
+// rows of 16 (row_shr 1, 2, 4, 8; lanes without a source add 0), then the row totals with row_bcast15 / row_bcast31.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_move_or0_u32(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
+  v += dpp_move_or0_u32<0x111, 0xf>(v);  // row_shr 1
+  v += dpp_move_or0_u32<0x112, 0xf>(v);  // row_shr 2
+  v += dpp_move_or0_u32<0x114, 0xf>(v);  // row_shr 4
+  v += dpp_move_or0_u32<0x118, 0xf>(v);  // row_shr 8
+  v += dpp_move_or0_u32<0x142, 0xa>(v);  // row_bcast15 into rows 1 and 3
+  v += dpp_move_or0_u32<0x143, 0xc>(v);  // row_bcast31 into rows 2 and 3
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_dpp(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_dpp(v), 63);
+}
+// inclusive suffix scan (lane i: the sum over lanes i .. 63) = total - prefix + own, exact in modular arithmetic
+__device__ __forceinline__ uint32_t wave_incl_suffix_scan_dpp(uint32_t v) {
+  const uint32_t p = wave_incl_scan_dpp(v);
+  return (uint32_t)__builtin_amdgcn_readlane((int)p, 63) - p + v;
+}
+// (The double scans of the alias prefix sums stay on __shfl_up / __shfl_down: their Hillis-Steele windows cross the rows
+// of 16 from the first step on, which no gfx9 DPP control reproduces, and a row-wise scan associates the additions
+// differently -- other last bits in the stored prefix sums.)
+
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
@@ -67,15 +159,18 @@ __device__ __forceinline__ T wave_incl_scan(T v) {
 }
 
 // exclusive scan over the workgroup (blockDim.x multiple of 64, <= 1024). scratch: >= 18 elements.
-template <typename T>
+// DPP (uint32_t only): the wave scans as DPP moves (wave_incl_scan_dpp) -- the same words
+template <typename T, bool DPP = false>
 __device__ T block_excl_scan(T v, T* scratch, T* total) {
   const int lane = lane_id(), w = wave_id(), nw = blockDim.x >> 6;
-  T inc = wave_incl_scan(v);
+  T inc;
+  if constexpr (DPP) inc = wave_incl_scan_dpp(v); else inc = wave_incl_scan(v);
   if (lane == WAVE - 1) scratch[w] = inc;
   __syncthreads();
   if (w == 0) {
     T t = lane < nw ? scratch[lane] : T(0);
-    T ti = wave_incl_scan(t);
+    T ti;
+    if constexpr (DPP) ti = wave_incl_scan_dpp(t); else ti = wave_incl_scan(t);
     if (lane < nw) scratch[lane] = ti - t;
     if (lane == nw - 1) scratch[17] = ti;
   }

@@ -187,7 +187,7 @@ __device__ __forceinline__ void aabb_body(const float4* __restrict__ ref, const 
   }
 #pragma unroll
   for (int k = 0; k < 3; k++) {
-    float a = wave_min(mn[k]), b = wave_max(mx[k]);
+    float a = wave_min_dpp(mn[k]), b = wave_max_dpp(mx[k]);
     if (lane == 0) {
       s_red[k][w] = a;
       s_red[3 + k][w] = b;
@@ -199,8 +199,8 @@ __device__ __forceinline__ void aabb_body(const float4* __restrict__ ref, const 
     for (int k = 0; k < 3; k++) {
       float a = lane < nw ? s_red[k][lane] : FLT_MAX;
       float b = lane < nw ? s_red[3 + k][lane] : -FLT_MAX;
-      a = wave_min(a);
-      b = wave_max(b);
+      a = wave_min_dpp(a);
+      b = wave_max_dpp(b);
       if (lane == 0) {
         part[blockIdx.x * 6 + k] = a;
         part[blockIdx.x * 6 + 3 + k] = b;
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void k_resample4(PftParams p, const pft_partic
   v.cE = cE;
   const uint32_t gt = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t li = gt >> 2, role = gt & 3u;
-  const int lane = lane_id(), q0 = lane & ~3;  // first lane of my quad
+  const int lane = lane_id();
   const bool live = li < p.P_local;
   const uint32_t g = p.id_offset + li;
   // change detection: no resample after an unchanged weight() -- the population goes through without noise, and the
@@ -297,20 +297,20 @@ __global__ __launch_bounds__(256) void k_resample4(PftParams p, const pft_partic
   // components 2r - 2, 2r - 1 (x y | z roll | pitch yaw)
   const float n0 = (role && draw) ? (float)(z0 * p.step_sigma[2u * role - 2u] + 0.0) : 0.0f;
   const float n1 = (role && draw) ? (float)(z1 * p.step_sigma[2u * role - 1u] + 0.0) : 0.0f;
-  const float nx = __shfl(n0, q0 + 1), ny = __shfl(n1, q0 + 1), nz = __shfl(n0, q0 + 2), nroll = __shfl(n1, q0 + 2),
-              npitch = __shfl(n0, q0 + 3), nyaw = __shfl(n1, q0 + 3);
+  const float nx = quad_bcast<1>(n0), ny = quad_bcast<1>(n1), nz = quad_bcast<2>(n0), nroll = quad_bcast<2>(n1),
+              npitch = quad_bcast<3>(n0), nyaw = quad_bcast<3>(n1);
   if (role == 0u && draw) {  // (slot 0 of the population is the representative state verbatim: no noise)
     s.x += nx; s.y += ny; s.z += nz;
     s.roll += nroll; s.pitch += npitch; s.yaw += nyaw;
   }
   // A1: lanes 1..3 take one angle each (double cos / sin rounded to float, as pose_to_matrix)
-  const float roll = __shfl(s.roll, q0), pitch = __shfl(s.pitch, q0), yaw = __shfl(s.yaw, q0);
+  const float roll = quad_bcast<0>(s.roll), pitch = quad_bcast<0>(s.pitch), yaw = quad_bcast<0>(s.yaw);
   const float ang = role == 1u ? roll : (role == 2u ? pitch : yaw);
   const float ca = (float)cos((double)ang), sa = (float)sin((double)ang);
-  const float E = __shfl(ca, q0 + 1), F = __shfl(sa, q0 + 1), C = __shfl(ca, q0 + 2), D = __shfl(sa, q0 + 2),
-              A = __shfl(ca, q0 + 3), B = __shfl(sa, q0 + 3);
+  const float E = quad_bcast<1>(ca), F = quad_bcast<1>(sa), C = quad_bcast<2>(ca), D = quad_bcast<2>(sa),
+              A = quad_bcast<3>(ca), B = quad_bcast<3>(sa);
   const float DE = D * E, DF = D * F;
-  const float sx = __shfl(s.x, q0), sy = __shfl(s.y, q0), sz = __shfl(s.z, q0);
+  const float sx = quad_bcast<0>(s.x), sy = quad_bcast<0>(s.y), sz = quad_bcast<0>(s.z);
   float m[12];  // (every lane of the quad forms the matrix: the box below needs it in all four)
   m[0] = A * C;  m[1] = A * DF - B * E;  m[2] = B * F + A * DE;  m[3] = sx;
   m[4] = B * C;  m[5] = A * E + B * DF;  m[6] = B * DE - A * F;  m[7] = sy;
@@ -337,8 +337,8 @@ __global__ __launch_bounds__(256) void k_resample4(PftParams p, const pft_partic
       // the translation once per lane that saw a point (monotone: as after the whole reduction), then quad, wave, workgroup
       float lo = (live && role < p.M_box) ? pmn[k] + m[4 * k + 3] : FLT_MAX;
       float hi = (live && role < p.M_box) ? pmx[k] + m[4 * k + 3] : -FLT_MAX;
-      lo = wave_min(lo);
-      hi = wave_max(hi);
+      lo = wave_min_dpp(lo);
+      hi = wave_max_dpp(hi);
       if (lane == 0) {
         s_red[k][w] = lo;
         s_red[3 + k][w] = hi;
@@ -365,7 +365,7 @@ __device__ __forceinline__ void reduce_partials(const float* __restrict__ part, 
       float x = part[i * 6 + w];
       v = fmaxf(v, w < 3 ? -x : x);
     }
-    v = wave_max(v);
+    v = wave_max_dpp(v);
     if (lane == 0) s6[w] = v;
   }
 }
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(1024) void k_crop_scatter(const float4* __restrict_
   if (wave_id() == 7) {
     uint32_t t = 0;
     for (uint32_t b = lane_id(); b < blockIdx.x; b += WAVE) t += counts[b];
-    t = wave_sum(t);
+    t = wave_sum_dpp(t);
     if (lane_id() == 0) s_base = t;
   }
   __syncthreads();
@@ -466,7 +466,7 @@ __global__ __launch_bounds__(1024) void k_crop_scatter(const float4* __restrict_
     keep = crop_keep(p, s6);
   }
   uint32_t total;
-  uint32_t pos = block_excl_scan<uint32_t>(keep ? 1u : 0u, s_scan, &total);
+  uint32_t pos = block_excl_scan<uint32_t, true>(keep ? 1u : 0u, s_scan, &total);
   if (keep) {
     uint32_t k = hsv_pack_of_rgba(__float_as_uint(p.w), argorder);
     out[s_base + pos] = make_float4(p.x, p.y, p.z, __uint_as_float(k));
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(1024) void k_crop_onepass(const float4* __restrict_
     keep = crop_keep(p, s6);
   }
   uint32_t total;
-  const uint32_t pos = block_excl_scan<uint32_t>(keep ? 1u : 0u, s_scan, &total);
+  const uint32_t pos = block_excl_scan<uint32_t, true>(keep ? 1u : 0u, s_scan, &total);
   if (threadIdx.x == 0) atomicExch(&slots[b], ((unsigned long long)epoch << 32) | total);
   if (wave_id() == 7) {
     uint32_t t = 0;
@@ -562,7 +562,7 @@ __global__ __launch_bounds__(1024) void k_crop_onepass(const float4* __restrict_
       }
       t += (uint32_t)v;
     }
-    t = wave_sum(t);
+    t = wave_sum_dpp(t);
     if (__ballot(failed) && lane_id() == 0) hdr->error |= 4u;
     if (lane_id() == 0) s_base = t;
   }

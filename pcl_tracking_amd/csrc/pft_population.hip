@@ -55,12 +55,9 @@ template <int NV>
 __device__ __forceinline__ void wg_tree_sum(double (&v)[NV], PopcSh& S) {
   const int lane = lane_id(), w = wave_id();
 #pragma unroll
-  for (int k = 0; k < NV; k++) {
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) v[k] += __shfl_xor(v[k], o);
-  }
+  for (int k = 0; k < NV; k++) v[k] = wave_tree_sum_lane63(v[k]);
   __syncthreads();  // (the scratch may still be read from its previous use)
-  if (lane == 0) {
+  if (lane == WAVE - 1) {
 #pragma unroll
     for (int k = 0; k < NV; k++) S.red[k][w] = v[k];
   }
@@ -124,7 +121,8 @@ __device__ __forceinline__ bool grid_barrier(PftHeader* hdr, int k, uint32_t G, 
 // w = -(float) val, val = sum of particle i's per-chunk likelihood partial sums, in chunk order (both summation orders)
 // (the loads go out eight at a time: one load, wait, add per chunk -- what the plain loop compiles to -- is a chain of
 // nchunk cache latencies, 11 at the headline size and 35 with the 64-point items of a 400-particle filter; the additions
-// stay in chunk order, so the value is the same)
+// stay in chunk order, so the value is the same.  All loads of up to 16 chunks in ONE round was measured at the headline
+// size: 0.2 us per launch slower than the rounds of 8 + 3 -- five clamped duplicates per thread)
 __device__ __forceinline__ float pop_raw_weight(const PftParams& prm, const PftDev& d, uint32_t i) {
   double v = 0.0;
   const double* row = d.partial + (size_t)i * prm.nchunk;
@@ -144,6 +142,14 @@ __device__ __forceinline__ float pop_exp_weight(const PftParams& prm, float w, d
   return (float)exp(1.0 - prm.alpha * ((double)w - wmin) / (wmax - wmin));
 }
 
+// x, y, z, roll, pitch, yaw of a particle (two 16-byte loads)
+__device__ __forceinline__ void pop_load_pose(const pft_particle* p, float (&c)[6]) {
+  const float4* q = reinterpret_cast<const float4*>(p);
+  const float4 a = q[0], b = q[1];
+  c[0] = a.x; c[1] = a.y; c[2] = a.z;
+  c[3] = b.x; c[4] = b.y; c[5] = b.z;
+}
+
 template <int K>
 __device__ __forceinline__ void population_body(const PftParams& prm, const PftDev& d, uint32_t n, int from_partials,
                                                 int do_norm, int do_mean, int do_alias, PopcSh& S) {
@@ -156,6 +162,15 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
 
   bool timed_out = false;
   STAMP(0);
+  // the pose components do not depend on the weights: requested before the first barrier and kept in registers (up to
+  // four particles per thread; the wider instances fetch them where they are used)
+  constexpr bool POSE_EARLY = K <= 4;
+  float pose[POSE_EARLY ? K : 1][6];
+  if (POSE_EARLY && do_mean) {
+#pragma unroll
+    for (int j = 0; j < K; j++)
+      if (i0 + j < n) pop_load_pose(P + i0 + j, pose[j]);
+  }
   // ---- phase 0: raw (or given) weights ----
   float wr[K];
 #pragma unroll
@@ -182,12 +197,9 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
         if (x != 0.0 && wmax < x) wmax = x;
       }
     }
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-      wmin = fmin(wmin, __shfl_xor(wmin, o));
-      wmax = fmax(wmax, __shfl_xor(wmax, o));
-    }
-    if (lane == 0) {
+    wmin = wave_minmax_lane63<false>(wmin);
+    wmax = wave_minmax_lane63<true>(wmax);
+    if (lane == WAVE - 1) {
       S.da[w] = wmin;
       S.db[w] = wmax;
     }
@@ -201,12 +213,9 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
     // ---- phase 1: the exponential, the weight sum ----
     wmin = tid < G ? pub_load(&part[tid * 16 + PP_MIN]) : DBL_MAX;
     wmax = tid < G ? pub_load(&part[tid * 16 + PP_MAX]) : -DBL_MAX;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-      wmin = fmin(wmin, __shfl_xor(wmin, o));
-      wmax = fmax(wmax, __shfl_xor(wmax, o));
-    }
-    if (lane == 0) {
+    wmin = wave_minmax_lane63<false>(wmin);
+    wmax = wave_minmax_lane63<true>(wmax);
+    if (lane == WAVE - 1) {
       S.da[w] = wmin;
       S.db[w] = wmax;
     }
@@ -262,7 +271,10 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
 #pragma unroll
         for (int j = 0; j < K; j++) {
           tv[j] = 0.0;
-          if (i0 + j < n) tv[j] = (double)reinterpret_cast<const float*>(P + i0 + j)[comp[k]] * (double)wr[j];
+          if (i0 + j < n) {
+            const float c = POSE_EARLY ? pose[j][k] : reinterpret_cast<const float*>(P + i0 + j)[comp[k]];
+            tv[j] = (double)c * (double)wr[j];
+          }
         }
         tot[k] = thread_tree_sum<K>(tv);
       }
@@ -329,14 +341,13 @@ __device__ __forceinline__ void population_body(const PftParams& prm, const PftD
       double* Dp = d.alias_pref;      // inclusive running deficit over the L list
       double* Ep = d.alias_pref + n;  // inclusive running excess over the H list
       // both lists run from the highest particle index down: inclusive SUFFIX scans over the threads of the workgroup
-      uint32_t iu = cntL;
+      // (the counts as DPP moves; the two double scans keep their shuffles, whose association the stored sums depend on)
+      const uint32_t iu = wave_incl_suffix_scan_dpp(cntL);
       double ia = defs, ib = excs;
 #pragma unroll
       for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t nu = __shfl_down(iu, o);
         const double na = __shfl_down(ia, o), nb = __shfl_down(ib, o);
         if (lane + o < WAVE) {
-          iu += nu;
           ia += na;
           ib += nb;
         }

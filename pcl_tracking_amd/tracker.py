@@ -880,6 +880,17 @@ class ParticleFilterTracker:
         self._check(self._L.pft_debug_normalize(self._h, _ptr(w), len(w), C.byref(fr)))
         return w, fr.value
 
+    def debugNormalizePartials(self, partial):
+        """test hook: normalizeWeight with the raw weights formed in the same launch from the (n, nchunk) likelihood
+        partial sums -> (normalised weights, fit ratio)"""
+        self._ensure()
+        partial = np.ascontiguousarray(partial, np.float64)
+        n, nchunk = partial.shape
+        w = np.zeros(n, np.float32)
+        fr = C.c_double()
+        self._check(self._L.pft_debug_normalize_partials(self._h, _ptr(partial), nchunk, n, _ptr(w), C.byref(fr)))
+        return w, fr.value
+
     def debugAlias(self, w):
         self._ensure()
         w = np.ascontiguousarray(w, np.float32)
