@@ -175,6 +175,16 @@ ROUNDS_STOP_FRACTION, ROUNDS_STOP_NO_PLANE, ROUNDS_STOP_MAX_PLANES = 0, 1, 2
 SEGMENT_STAGES = ("compaction", "sample", "score", "replay", "refit", "cluster", "output")
 MODEL_STAGES = ("remove_zero_points", "centroid", "recentre", "grid_sample")
 
+
+class SubtractConfig(C.Structure):
+    """pft_subtract_config (include/pft_subtract.h)"""
+    _fields_ = [("abi_version", C.c_uint32), ("device_id", C.c_int32), ("radius", C.c_float), ("cloud", C.c_int32)]
+
+
+SUBTRACT_MAX_OBJECTS = 64
+SUBTRACT_MAX_MODEL_POINTS, SUBTRACT_MAX_FRAME_POINTS = 1 << 22, 1 << 26
+SUBTRACT_REFERENCE_CLOUD, SUBTRACT_REPORT_CLOUD = 0, 1
+
 # every symbol include/*.h declare: (name, restype, argtypes)
 _vp, _sz, _i32, _u32, _u64, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint64, C.c_double
 _P = C.POINTER
@@ -315,6 +325,27 @@ SYMBOLS = [
     ("pft_model_output_device", C.c_int, [_vp, _P(_vp), _P(_sz), _P(_vp), _P(_sz)]),
     ("pft_model_last_ms", C.c_int, [_vp, _P(_f64), _vp]),
     ("pft_set_object_from_model", C.c_int, [_vp, _vp, C.c_int]),
+    # include/pft_subtract.h
+    ("pft_subtract_default_config", None, [_P(SubtractConfig)]),
+    ("pft_subtract_create", C.c_int, [_P(SubtractConfig), _P(_vp)]),
+    ("pft_subtract_destroy", None, [_vp]),
+    ("pft_subtract_last_error_string", C.c_char_p, [_vp]),
+    ("pft_subtract_set_object", C.c_int, [_vp, C.c_int, _vp, _sz, _vp]),
+    ("pft_subtract_set_object_matrix", C.c_int, [_vp, C.c_int, _vp]),
+    ("pft_subtract_bind_tracker", C.c_int, [_vp, C.c_int, _vp]),
+    ("pft_subtract_remove_object", C.c_int, [_vp, C.c_int]),
+    ("pft_subtract_clear", C.c_int, [_vp]),
+    ("pft_subtract_apply", C.c_int, [_vp, _vp, _sz]),
+    ("pft_subtract_apply_device", C.c_int, [_vp, _vp, _sz]),
+    ("pft_subtract_counts", C.c_int, [_vp, _P(_sz), _P(_sz), _P(_sz)]),
+    ("pft_subtract_get_owner", C.c_int, [_vp, _vp, _sz]),
+    ("pft_subtract_get_sq_dist", C.c_int, [_vp, _vp, _sz]),
+    ("pft_subtract_get_support", C.c_int, [_vp, _vp, _sz]),
+    ("pft_subtract_get_residual", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_subtract_get_residual_indices", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_subtract_residual_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
+    ("pft_subtract_get_object", C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _P(_sz)]),
+    ("pft_subtract_last_ms", C.c_int, [_vp, _P(_f64)]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

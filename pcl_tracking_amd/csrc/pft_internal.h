@@ -293,6 +293,9 @@ void pftf_attach(pft_filter* f, PftBorrow* b);
 // *n_keep) = the kept input indices, ascending, keep_xyz their {x, y, z, 1}; xyz [n], flag [n], tile [ceil(n / 1024)] scratch
 void pftk_remove_zero_points(hipStream_t s, const pft_point_xyzrgba* in, uint32_t n, float4* xyz, uint8_t* flag,
                              uint32_t* tile, uint32_t* keep_idx, float4* keep_xyz, uint32_t* n_keep);
+// pft_segment.hip: the one-workgroup exclusive scan of the tile / scan / emit compaction (1024-element tiles), in place over
+// tile[0 .. ntiles); the total goes to *out
+void pftk_tile_scan(hipStream_t s, uint32_t* tile, uint32_t ntiles, uint32_t* out);
 struct pft_segment;
 int pftsg_device_id(const pft_segment* s);
 struct pft_model;

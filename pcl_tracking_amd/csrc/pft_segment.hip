@@ -119,6 +119,11 @@ __global__ __launch_bounds__(1024) void k_sg_scan(uint32_t* tile, uint32_t ntile
   if (threadIdx.x == 0) *out = carry;
 }
 
+// the same scan for the other ordered compactions of the library (pft_subtract.hip): tile[0 .. ntiles) in place, the total to *out
+void pftk_tile_scan(hipStream_t st, uint32_t* tile, uint32_t ntiles, uint32_t* out) {
+  hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(1024), 0, st, tile, ntiles, (const uint32_t*)nullptr, out);
+}
+
 // out[pos] = map ? map[i] : i for every flagged i, in order; optional gather of float4 src[i] to dst[pos]
 __global__ __launch_bounds__(SG_THREADS) void k_sg_emit(const uint8_t* __restrict__ flag, uint32_t n_max,
                                                         const uint32_t* n_dev, const uint32_t* __restrict__ tile,

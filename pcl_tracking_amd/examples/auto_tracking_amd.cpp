@@ -6,7 +6,7 @@
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
 //                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
 //                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]]
-//                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]]
+//                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -43,6 +43,15 @@
 // before any result is read) and prints one `spread obj <j>: n_eff ... zero ... pos_sigma ... rpy_sigma ... flagged <0|1>` line
 // per object and frame; the pose is flagged after `after` frames in a row whose largest position sigma exceeded max_pos_sigma
 // or whose effective sample size fell below min_n_eff (the defaults inf,0,1 never flag).
+// --discover[=every[,radius]] (default: every frame, 0.02) finds objects that were not there when the tracking began: after the
+// frame's results, every object that is not lost is bound to a scene subtraction (pft::SceneSubtraction) at its result pose, the
+// frame is subtracted on the device, and the residual goes through the segmenter with the model-creation flags
+// (segment_options.hpp).  Every cluster becomes a new object with the next free id, prepared on the device as --segment
+// prepares its objects, and is tracked from the next frame on: one `discover frame <f>: cluster <c> -> obj <j> (<n> points)`
+// line per new object, and with --match one `support obj <j> <n>` line per subtracted object (the frame points it holds).
+// A frame in which an object is lost discovers nothing: the lost object's own points are unexplained there.
+// --reacquire-residual (with --reacquire): the segmentation that serves the lost objects runs on the frame minus the objects
+// that are not lost, so a lost object is never scored at the cluster of an object that is still tracked.
 #include <cstdlib>
 
 #include "segment_options.hpp"
@@ -140,6 +149,21 @@ int main(int argc, char** argv) {
         opt.rf_pair_distance = pd;
       }
     }
+    else if (!std::strncmp(argv[i], "--discover", 10) && (argv[i][10] == 0 || argv[i][10] == '=')) {
+      opt.discover = true;  // --discover[=every[,radius]]; the defaults 1,0.02
+      if (argv[i][10] == '=') {
+        int every = opt.discover_every;
+        double radius = opt.discover_radius;
+        const int got = std::sscanf(argv[i] + 11, "%d,%lf", &every, &radius);
+        if (got < 1 || every < 1 || !(radius > 0.0)) {
+          std::fprintf(stderr, "--discover=every[,radius] with every >= 1 and radius > 0\n");
+          return 2;
+        }
+        opt.discover_every = every;
+        opt.discover_radius = radius;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--reacquire-residual")) opt.reacquire_residual = true;
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -151,7 +175,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -165,6 +189,10 @@ int main(int argc, char** argv) {
   }
   if (opt.refine && !opt.reacquire) {
     std::fprintf(stderr, "--refine needs --reacquire: it is the re-acquired pose that is refined\n");
+    return 2;
+  }
+  if (opt.reacquire_residual && !opt.reacquire) {
+    std::fprintf(stderr, "--reacquire-residual needs --reacquire: it is the re-acquisition's segmentation that runs on the residual\n");
     return 2;
   }
   if (async && !raw) {
@@ -218,6 +246,11 @@ int main(int argc, char** argv) {
       std::fprintf(stderr, "PointCloud before downsampled: %zu data points.\nPointCloud after downsampled: %zu data points.\n",
                    front_end.passedPoints(), n_down);  // auto_tracking.cpp:682, 684
     }
+    // the frame where the subtraction reads it: the front end's output in HBM (--raw; with --async asked for once the
+    // frame's results are on the host), else the host cloud
+    auto frameOnDevice = [&]() {
+      if (async && !d_cloud) pft_filter_output_device(front_end.nativeHandle(), &d_cloud, &n_down);
+    };
     for (auto& kv : v.tracker_dict) {  // :688-697 -- asynchronous: all objects are in flight before a result is read
       if (async) kv.second->setInputCloudFromFilter(front_end);
       else if (raw) kv.second->setInputCloudDevice(d_cloud, n_down);
@@ -232,10 +265,14 @@ int main(int argc, char** argv) {
       if (opt.spread) kv.second->computeSpread();
     }
     std::vector<int> lost;  // --reacquire: the objects the match reported lost in this frame
+    bool any_lost = false;
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
       if (opt.spread) v.reportSpread(kv.first);
-      if (opt.match && v.reportMatch(f + 1, kv.first, !opt.reacquire) && opt.reacquire) lost.push_back(kv.first);
+      if (opt.match && v.reportMatch(f + 1, kv.first, !opt.reacquire)) {
+        any_lost = true;
+        if (opt.reacquire) lost.push_back(kv.first);
+      }
       if (opt.device_report) {
         const pft_object_report rep = kv.second->getReport();
         printObjectLine(f + 1, kv.first, result, rep.centroid);
@@ -250,12 +287,42 @@ int main(int argc, char** argv) {
       try {
         pft::ModelSegmenter frame_seg;
         pft::VoxelGrid frame_grid;
-        segmentScene(so, cloud, frame_grid, frame_seg);
+        if (opt.reacquire_residual) {  // the frame minus the objects that are still tracked
+          frameOnDevice();
+          const pft_point_xyzrgba* d_res = nullptr;
+          size_t n_res = 0;
+          v.subtractTracked(*cloud, d_cloud, n_down, lost).residualDevice(&d_res, &n_res);
+          if (n_res) segmentDeviceCloud(so, d_res, n_res, frame_grid, frame_seg);
+          else throw std::runtime_error("the tracked objects explain the whole frame");
+        } else {
+          segmentScene(so, cloud, frame_grid, frame_seg);
+        }
         v.reacquireLost(lost, frame_seg);
       } catch (const std::exception& e) {
         std::fprintf(stderr, "reacquire: %s\n", e.what());
         if (opt.reset_on_loss)
           for (const int obj_id : lost) v.tracker_dict[obj_id]->resetTracking();
+      }
+    }
+    if (opt.discover && !any_lost && f % (size_t)opt.discover_every == 0) {
+      try {
+        frameOnDevice();
+        const pft_point_xyzrgba* d_res = nullptr;
+        size_t n_res = 0;
+        pft::SceneSubtraction& sub = v.subtractTracked(*cloud, d_cloud, n_down, lost);
+        sub.residualDevice(&d_res, &n_res);
+        if (opt.match) {
+          const std::vector<uint32_t> support = sub.support();
+          for (size_t k = 0; k < v.boundIds().size(); k++) std::printf("support obj %d %u\n", v.boundIds()[k], support[k]);
+        }
+        if (n_res) {
+          pft::ModelSegmenter res_seg;
+          pft::VoxelGrid res_grid;
+          segmentDeviceCloud(so, d_res, n_res, res_grid, res_seg);
+          v.discoverObjects(f + 1, res_seg, [](ParticleFilter& tr, int) { tr.setThrowOnFailure(false); });
+        }
+      } catch (const std::exception& e) {
+        std::fprintf(stderr, "discover: %s\n", e.what());
       }
     }
     if (async)  // the counts, now that the frame's results are on the host

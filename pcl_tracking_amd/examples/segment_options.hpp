@@ -69,9 +69,8 @@ inline int parseSegmentFlag(SegmentOptions& o, int argc, char** argv, int& i) {
   return 1;
 }
 
-// the scene through the pipeline the flags describe: the optional VoxelGrid first (its output stays on the device, in
-// `grid`, for as long as the segmentation reads it), then the segmenter.  Throws what the two handles throw.
-inline void segmentScene(const SegmentOptions& o, const Cloud::Ptr& cloud, pft::VoxelGrid& grid, pft::ModelSegmenter& seg) {
+// the segmenter configured as the flags describe
+inline void configureSegmenter(const SegmentOptions& o, pft::ModelSegmenter& seg) {
   seg.setPlane(o.plane);
   pft_segment_config& c = seg.config();
   if (!o.plane) c.box_enable[2] = 1;  // create_model.cpp: PassThrough z as well
@@ -90,6 +89,26 @@ inline void segmentScene(const SegmentOptions& o, const Cloud::Ptr& cloud, pft::
   }
   if (o.max_planes > 0) seg.setPlaneRounds(o.max_planes, o.fraction);
   if (o.tree_refit) seg.setRefitOrder(PFT_SUM_TREE);
+}
+
+// a cloud that lies in HBM (a subtraction's residual) through the same pipeline; with --voxel the clusters' indices point
+// into the grid's output.  The cloud must stay valid until the call returns
+inline void segmentDeviceCloud(const SegmentOptions& o, const pft_point_xyzrgba* d_cloud, size_t n, pft::VoxelGrid& grid,
+                               pft::ModelSegmenter& seg) {
+  configureSegmenter(o, seg);
+  if (o.leaf > 0.0f) {
+    grid.setLeafSize(o.leaf, o.leaf, o.leaf);
+    grid.setInputCloudDevice(d_cloud, n);
+    grid.filterDevice(&d_cloud, &n);
+  }
+  seg.setInputCloudDevice(d_cloud, n);
+  seg.apply();
+}
+
+// the scene through the pipeline the flags describe: the optional VoxelGrid first (its output stays on the device, in
+// `grid`, for as long as the segmentation reads it), then the segmenter.  Throws what the two handles throw.
+inline void segmentScene(const SegmentOptions& o, const Cloud::Ptr& cloud, pft::VoxelGrid& grid, pft::ModelSegmenter& seg) {
+  configureSegmenter(o, seg);
   if (o.leaf > 0.0f) {  // cluster_euclid.cpp:40-44: VoxelGrid, then everything else on its output
     grid.setLeafSize(o.leaf, o.leaf, o.leaf);
     grid.setInputCloud(cloud);

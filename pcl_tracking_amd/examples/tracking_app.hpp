@@ -17,6 +17,9 @@
 //   --reacquire          a lost object is looked for among the cluster centroids of a segmentation of the frame
 //                        (reacquire) and restarted where it is found
 //   --refine             the pose found by --reacquire is refined against the frame (refine) before the restart
+//   --discover           the frame minus the objects that are tracked (pft::SceneSubtraction) goes through the segmenter;
+//                        every cluster of that residual becomes a new object
+//   --reacquire-residual the segmentation that serves the lost objects runs on the residual of the objects still tracked
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -32,6 +35,7 @@
 #include "pft/model_preparation.hpp"
 #include "pft/pcd_io.hpp"
 #include "pft/particle_filter_tracker.hpp"
+#include "pft/scene_subtraction.hpp"
 
 namespace app {
 
@@ -69,6 +73,10 @@ struct Options {
   int rq_n_yaw = 8;                     // yaw steps over the full circle around the object's initial orientation
   double rq_accept_ratio = 0.5;         // inliers / model points a candidate needs
   double rq_inlier_distance = 0.02;
+  bool discover = false;                // --discover: clusters of the frame that no tracked object explains become objects
+  int discover_every = 1;               // every n-th frame
+  double discover_radius = 0.02;        // the subtraction's radius (also --reacquire-residual's)
+  bool reacquire_residual = false;      // --reacquire-residual: lost objects are looked for in the residual only
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -123,10 +131,15 @@ class TrackingApp {
   // has no notion of (device, stream, shard) before the handle exists
   template <class F>
   void buildTrackers(int nb_objects, F&& configure) {
+    for (int obj_id = 0; obj_id < nb_objects; obj_id++) addTracker(obj_id, configure);
+  }
+  // one more tracker with the same parameters (--discover adds objects while the frames run)
+  template <class F>
+  void addTracker(int obj_id, F&& configure) {
     std::vector<double> step_cov(6, 0.015 * 0.015);
     for (int k = 3; k < 6; k++) step_cov[k] *= 40.0;
     const std::vector<double> init_cov(6, 0.00001), init_mean(6, 0.0);
-    for (int obj_id = 0; obj_id < nb_objects; obj_id++) {
+    {
       std::shared_ptr<ParticleFilter> tr;
       if (opt_.use_fixed) {
         tr.reset(new ParticleFilterOMPTracker<RefPointType, ParticleT>(opt_.threads));
@@ -335,17 +348,66 @@ class TrackingApp {
     }
   }
 
+  // --discover / --reacquire-residual: the frame (in HBM when d_frame is given, else `frame`) minus every object that is
+  // not in `lost`, bound at its current result pose.  Slot k holds the k-th object bound (boundIds()); at most
+  // PFT_SUBTRACT_MAX_OBJECTS objects are bound.  The residual stays in the subtraction until its next apply
+  pft::SceneSubtraction& subtractTracked(const Cloud& frame, const pft_point_xyzrgba* d_frame, size_t d_n,
+                                         const std::vector<int>& lost) {
+    if (!subtraction_) subtraction_.reset(new pft::SceneSubtraction((float)opt_.discover_radius));
+    subtraction_->clear();
+    bound_ids_.clear();
+    for (auto& kv : tracker_dict) {
+      bool is_lost = false;
+      for (const int id : lost) is_lost = is_lost || id == kv.first;
+      if (is_lost) continue;
+      if ((int)bound_ids_.size() == PFT_SUBTRACT_MAX_OBJECTS) {
+        std::fprintf(stderr, "subtraction: more than %d tracked objects, object %d and later ones are not subtracted\n",
+                     (int)PFT_SUBTRACT_MAX_OBJECTS, kv.first);
+        break;
+      }
+      subtraction_->bindTracker((int)bound_ids_.size(), *kv.second);
+      bound_ids_.push_back(kv.first);
+    }
+    if (d_frame) subtraction_->applyDevice(d_frame, d_n);
+    else subtraction_->apply(frame);
+    return *subtraction_;
+  }
+  const std::vector<int>& boundIds() const { return bound_ids_; }
+
+  // --discover: the clusters of `seg` (a segmentation of the residual) become objects with the next free ids, prepared on
+  // the device from where the clusters lie (the --segment path).  One line per new object
+  template <class F>
+  void discoverObjects(size_t frame, pft::ModelSegmenter& seg, F&& configure) {
+    const std::vector<uint32_t> sizes = seg.clusterSizes();
+    for (size_t c = 0; c < sizes.size(); c++) {
+      const int obj_id = tracker_dict.empty() ? 0 : tracker_dict.rbegin()->first + 1;
+      addTracker(obj_id, configure);
+      if (!prepareOne(obj_id, *tracker_dict[obj_id], &seg, c)) {
+        tracker_dict.erase(obj_id);
+        continue;
+      }
+      std::printf("discover frame %zu: cluster %zu -> obj %d (%u points)\n", frame, c, obj_id, sizes[c]);
+    }
+  }
+
   const Options& options() const { return opt_; }
 
  private:
   Options opt_;
   std::map<int, std::shared_ptr<pft::ModelPreparation>> model_dict_;  // the device-side models, one handle per object
+  std::unique_ptr<pft::SceneSubtraction> subtraction_;                // created by the first subtractTracked()
+  std::vector<int> bound_ids_;                                        // object of every slot of the last subtractTracked()
 
   bool prepareOnDevice(pft::ModelSegmenter* seg) {
-    for (auto& kv : tracker_dict) {
-      const int obj_id = kv.first;
+    for (auto& kv : tracker_dict)
+      if (!prepareOne(kv.first, *kv.second, seg, (size_t)kv.first)) return false;
+    return true;
+  }
+  // one object's model from its model cloud, or from cluster `cluster` of a segmenter's last apply
+  bool prepareOne(int obj_id, ParticleFilter& tracker, pft::ModelSegmenter* seg, size_t cluster) {
+    {
       std::shared_ptr<pft::ModelPreparation> mp(new pft::ModelPreparation());
-      if (seg) mp->setInputFromSegmenter(*seg, (size_t)obj_id);
+      if (seg) mp->setInputFromSegmenter(*seg, cluster);
       else mp->setInputCloud(ref_cloud_dict[obj_id]);
       mp->setLeafSize(opt_.downsampling_grid_size > 0 ? (float)opt_.downsampling_grid_size : 0.0f);
       if (!mp->prepare()) {
@@ -354,10 +416,10 @@ class TrackingApp {
       }
       std::fprintf(stderr, "object %d ref_cloud: %zu data points, nonzero_ref: %zu, downsampled: %zu\n", obj_id,
                    mp->inputPoints(), mp->nonzeroPoints(), mp->referencePoints());
-      if (kv.second->setObjectFromModel(*mp, opt_.device_report) != PFT_OK) return false;
+      if (tracker.setObjectFromModel(*mp, opt_.device_report) != PFT_OK) return false;
       model_dict_[obj_id] = mp;
       reference_dict.erase(obj_id);
-      kv.second->setMinIndices((int)mp->inputPoints() / 2);
+      tracker.setMinIndices((int)mp->inputPoints() / 2);
     }
     return true;
   }
