@@ -73,6 +73,29 @@ class PopulationStatsStruct(C.Structure):
     ]
 
 
+class VisibilityConfig(C.Structure):
+    """pft_visibility_config (include/pft_visibility.h): the pinhole camera and the two depth margins, 48 bytes"""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+        ("cy", C.c_float), ("z_near", C.c_float), ("splat", C.c_int32),
+        ("occlusion_margin", C.c_double), ("self_margin", C.c_double),
+    ]
+
+
+class VisibilityStatsStruct(C.Structure):
+    """pft_visibility_stats (include/pft_visibility.h): the counts of one visibility call and its rule's state, 104 bytes"""
+    _fields_ = [
+        ("transform", C.c_float * 12),
+        ("n_reference", C.c_uint32), ("n_visible", C.c_uint32), ("n_occluded", C.c_uint32), ("n_self", C.c_uint32),
+        ("n_out", C.c_uint32), ("n_frame", C.c_uint32), ("has_match", C.c_uint32), ("n_visible_matched", C.c_uint32),
+        ("hidden", C.c_uint32), ("below", C.c_uint32), ("streak", C.c_uint32), ("lost", C.c_uint32),
+        ("evaluated", C.c_uint32), ("calls", C.c_uint32),
+    ]
+
+
+VIS_VISIBLE, VIS_OCCLUDED, VIS_SELF_OCCLUDED, VIS_OUT_OF_VIEW = range(4)
+
+
 class ReacquireConfig(C.Structure):
     """pft_reacquire_config (include/pft.h): the orientation lattice, the inlier gate and the acceptance rule, 64 bytes"""
     _fields_ = [
@@ -346,6 +369,16 @@ SYMBOLS = [
     ("pft_subtract_residual_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
     ("pft_subtract_get_object", C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _P(_sz)]),
     ("pft_subtract_last_ms", C.c_int, [_vp, _P(_f64)]),
+    # include/pft_visibility.h
+    ("pft_visibility_config_default", None, [_P(VisibilityConfig)]),
+    ("pft_visibility_project", C.c_int, [_P(VisibilityConfig), _vp, _vp]),
+    ("pft_set_visibility_camera", C.c_int, [_vp, _P(VisibilityConfig)]),
+    ("pft_get_visibility_camera", C.c_int, [_vp, _P(VisibilityConfig)]),
+    ("pft_set_visibility_threshold", C.c_int, [_vp, _f64, _f64, C.c_int]),
+    ("pft_get_visibility_threshold", C.c_int, [_vp, _P(_f64), _P(_f64), _P(C.c_int)]),
+    ("pft_visibility", C.c_int, [_vp, _vp]),
+    ("pft_get_visibility", C.c_int, [_vp, _P(VisibilityStatsStruct)]),
+    ("pft_get_visibility_points", C.c_int, [_vp, _vp, _vp, _vp, _sz, _P(_sz)]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

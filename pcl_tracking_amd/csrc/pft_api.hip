@@ -435,6 +435,7 @@ extern "C" int pft_create(const pft_config* cfg, pft_tracker** out) {
   }
   for (int i = 0; i < 16; i++) t->trans[i] = (i % 5 == 0) ? 1.0f : 0.0f;
   t->sw = pft_read_switches();
+  pft_visibility_config_default(&t->vis_cam);
   t->use_graph = t->sw.graph && t->own_stream;
 
   PftParams& p = t->prm;
@@ -578,6 +579,7 @@ extern "C" int pft_synchronize(pft_tracker* t) {
 int pftt_match_clear_streak(pft_tracker* t) {
   if (t->d_match) PFT_HIPCHK(t, hipMemsetAsync(&t->d_match->below, 0, 3 * sizeof(uint32_t), t->stream));
   if (t->d_spread) PFT_HIPCHK(t, hipMemsetAsync(&t->d_spread->uncertain, 0, 3 * sizeof(uint32_t), t->stream));
+  if (t->d_vis) PFT_HIPCHK(t, hipMemsetAsync(&t->d_vis->below, 0, 3 * sizeof(uint32_t), t->stream));  // the visibility rule's
   return PFT_OK;
 }
 
@@ -590,6 +592,7 @@ extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, s
   t->has_ref = false;
   t->tree_of_compute = false;
   t->match_n = 0;
+  t->vis_n = 0;
   if (n > t->ref_cap) {
     hipStreamSynchronize(t->stream);
     t->ref_cap = 0;
@@ -688,6 +691,7 @@ extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, s
   if (t->h_stat) t->h_stat[0] = t->h_stat[1] = 0;  // new scene: forget the builder hints (unknown depth = all radix passes)
   t->tree_of_compute = false;  // the tree on the device was searched for another model
   t->match_n = 0;
+  t->vis_n = 0;
   {
     const int r = pftt_match_clear_streak(t);  // a new object: the lost rule starts over
     if (r != PFT_OK) return r;

@@ -1,7 +1,7 @@
 // pft_api_features.hip -- the optional features of the tracker handle, each with its own buffers and one reserve function:
 // the change detector's settings, the object report, the match statistics with the lost rule and resetTracking, the
-// population statistics with the spread rule, re-acquisition and pose refinement.  The kernels are in pft_change.hip,
-// pft_report.hip, pft_match.hip, pft_spread.hip, pft_reacquire.hip and pft_refine.hip.
+// population statistics with the spread rule, the visibility, re-acquisition and pose refinement.  The kernels are in
+// pft_change.hip, pft_report.hip, pft_match.hip, pft_spread.hip, pft_visibility.hip, pft_reacquire.hip and pft_refine.hip.
 #include <string.h>
 
 #include <cmath>
@@ -256,6 +256,7 @@ extern "C" int pft_match(pft_tracker* t) {
              t->d_match_d2);
   PFT_HIPCHK(t, hipGetLastError());
   t->match_issued = true;
+  t->match_of_compute = true;
   t->match_n = M;
   return PFT_OK;
 }
@@ -359,6 +360,151 @@ extern "C" int pft_get_spread(pft_tracker* t, pft_population_stats* out) {
     return PFT_ERR_STATE;
   }
   PFT_HIPCHK(t, hipMemcpyAsync(out, t->d_spread, sizeof(pft_population_stats), hipMemcpyDeviceToHost, t->stream));
+  PFT_HIPCHK(t, hipStreamSynchronize(t->stream));
+  return pftt_check_device_error(t);
+}
+
+// ---- visibility of the model at a pose and the occlusion-aware lost rule (pft_visibility.hip) ----
+extern "C" int pft_set_visibility_camera(pft_tracker* t, const pft_visibility_config* c) {
+  if (!t || !c) return PFT_ERR_INVALID_ARG;
+  const char* bad = nullptr;
+  if (c->width < 1 || c->width > PFT_VIS_MAX_IMAGE || c->height < 1 || c->height > PFT_VIS_MAX_IMAGE)
+    bad = "width and height must lie in 1 .. 1024";
+  else if (!std::isfinite(c->fx) || !std::isfinite(c->fy) || !(c->fx > 0.0f) || !(c->fy > 0.0f))
+    bad = "fx and fy must be finite and > 0";
+  else if (!std::isfinite(c->cx) || !std::isfinite(c->cy))
+    bad = "cx and cy must be finite";
+  else if (!std::isfinite(c->z_near) || !(c->z_near >= 0.0f))
+    bad = "z_near must be finite and >= 0";
+  else if (c->splat < 0 || c->splat > PFT_VIS_MAX_SPLAT)
+    bad = "splat must lie in 0 .. 4";
+  else if (!std::isfinite(c->occlusion_margin) || !(c->occlusion_margin >= 0.0) || !std::isfinite(c->self_margin) ||
+           !(c->self_margin >= 0.0))
+    bad = "occlusion_margin and self_margin must be finite and >= 0";
+  if (bad) {
+    t->err = std::string("pft_set_visibility_camera: ") + bad;
+    return PFT_ERR_INVALID_ARG;
+  }
+  t->vis_cam = *c;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_visibility_camera(pft_tracker* t, pft_visibility_config* c) {
+  if (!t || !c) return PFT_ERR_INVALID_ARG;
+  *c = t->vis_cam;
+  return PFT_OK;
+}
+
+extern "C" int pft_set_visibility_threshold(pft_tracker* t, double min_visible_ratio, double min_ratio, int lost_after) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!(min_visible_ratio >= 0.0 && min_visible_ratio <= 1.0) || !(min_ratio >= 0.0 && min_ratio <= 1.0) || lost_after < 1) {
+    t->err = "pft_set_visibility_threshold: min_visible_ratio and min_ratio must lie in [0, 1] and lost_after must be at least 1";
+    return PFT_ERR_INVALID_ARG;
+  }
+  t->vis_min_visible_ratio = min_visible_ratio;
+  t->vis_min_ratio = min_ratio;
+  t->vis_lost_after = lost_after;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_visibility_threshold(pft_tracker* t, double* min_visible_ratio, double* min_ratio, int* lost_after) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (min_visible_ratio) *min_visible_ratio = t->vis_min_visible_ratio;
+  if (min_ratio) *min_ratio = t->vis_min_ratio;
+  if (lost_after) *lost_after = t->vis_lost_after;
+  return PFT_OK;
+}
+
+extern "C" int pft_visibility(pft_tracker* t, const float* m12) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (t->cfg.world_size != 1) {
+    t->err = "the visibility is not supported on a sharded handle (world_size > 1)";
+    return PFT_ERR_INVALID_ARG;
+  }
+  if (m12)
+    for (int k = 0; k < 12; k++)
+      if (!std::isfinite(m12[k])) {
+        t->err = "pft_visibility: entry " + std::to_string(k) + " of the matrix is not finite";
+        return PFT_ERR_INVALID_ARG;
+      }
+  const int ready = pftt_check_ready(t);  // no input cloud, no reference cloud: as pft_compute
+  if (ready != PFT_OK) return ready;
+  if (!m12 && !t->initialized) {
+    t->err = "pft_visibility without a matrix before the first pft_compute: there is no result pose yet";
+    return PFT_ERR_STATE;
+  }
+  if (t->n_on_device && t->raw_pending) {
+    t->err = "pft_visibility: the input handed over by pft_set_input_from_filter has not been through a pft_compute yet "
+             "(its count is still the filter's)";
+    return PFT_ERR_STATE;
+  }
+  const uint32_t M = t->prm.M;
+  const PftVisCam cam = pftk_visibility_cam(t->vis_cam);
+  const size_t words = 2u * (size_t)cam.W * (size_t)cam.H;
+  if (!t->d_vis) {
+    PFTT_GROW(t, t->d_vis_ctl.reserve(1));
+    PFTT_GROW(t, t->d_vis.alloc(1));
+    PFT_HIPCHK(t, hipMemsetAsync(t->d_vis, 0, sizeof(pft_visibility_stats), t->stream));
+  }
+  if (words > t->d_vis_z.cap()) {
+    PFT_HIPCHK(t, hipStreamSynchronize(t->stream));  // a call in flight may still write the previous images
+    PFTT_GROW(t, t->d_vis_z.alloc(words));
+  }
+  if (M > t->d_vis_mgap.cap()) {
+    PFT_HIPCHK(t, hipStreamSynchronize(t->stream));
+    t->d_vis_mgap.reset();  // (the capacity of the four: zero until all are there)
+    t->vis_n = 0;
+    PFTT_GROW(t, t->d_vis_q.alloc(M));
+    PFTT_GROW(t, t->d_vis_state.alloc(M));
+    PFTT_GROW(t, t->d_vis_sgap.alloc(M));
+    PFTT_GROW(t, t->d_vis_mgap.alloc(M));
+  }
+  const PftVisBufs b = {t->d_vis_ctl, t->d_vis_z, t->d_vis_q, t->d_vis_state, t->d_vis_sgap, t->d_vis_mgap, t->d_vis};
+  if (t->vis_n != M || !t->vis_issued)  // (pft_set_reference zeroes vis_n: no point of another model survives it)
+    pftk_visibility_clear(t->stream, b, M);
+  PftVisArgs a;
+  memset(&a, 0, sizeof(a));
+  if (m12) memcpy(a.m, m12, sizeof(a.m));
+  a.use_rep = m12 ? 0u : 1u;
+  // (pft_set_reference zeroes match_n: the pairs of another model are not read)
+  a.match_enqueued = !m12 && t->match_of_compute && t->match_issued && t->match_n == M ? 1u : 0u;
+  a.lost_after = (uint32_t)t->vis_lost_after;
+  a.min_visible_ratio = t->vis_min_visible_ratio;
+  a.min_ratio = t->vis_min_ratio;
+  pftt_sync_dev(t);
+  // the frame: the 16-byte records, or PCL's 32-byte layout while the frame's first crop has not formed them yet
+  const float4* pts = t->raw_pending ? reinterpret_cast<const float4*>(t->raw_pending) : t->d_in_pts.get();
+  pftk_visibility(t->stream, t->dev, M, pts, t->raw_pending ? 2u : 1u, t->N, t->dev.n_dev, cam, a, b, t->d_match,
+                  t->d_match_idx, t->num_cus);
+  PFT_HIPCHK(t, hipGetLastError());
+  t->vis_issued = true;
+  t->vis_n = M;
+  return PFT_OK;
+}
+
+extern "C" int pft_get_visibility(pft_tracker* t, pft_visibility_stats* out) {
+  if (!t || !out) return PFT_ERR_INVALID_ARG;
+  if (!t->vis_issued) {
+    t->err = "pft_get_visibility before the first pft_visibility";
+    return PFT_ERR_STATE;
+  }
+  PFT_HIPCHK(t, hipMemcpyAsync(out, t->d_vis, sizeof(pft_visibility_stats), hipMemcpyDeviceToHost, t->stream));
+  PFT_HIPCHK(t, hipStreamSynchronize(t->stream));
+  return pftt_check_device_error(t);
+}
+
+extern "C" int pft_get_visibility_points(pft_tracker* t, uint8_t* state, float* scene_gap, float* self_gap, size_t cap,
+                                         size_t* n) {
+  if (!t) return PFT_ERR_INVALID_ARG;
+  if (!t->vis_issued || !t->vis_n) {
+    t->err = "pft_get_visibility_points: no points (no pft_visibility since the reference cloud was last set)";
+    return PFT_ERR_STATE;
+  }
+  if (n) *n = t->vis_n;
+  const size_t c = cap < t->vis_n ? cap : t->vis_n;
+  if (state && c) PFT_HIPCHK(t, hipMemcpyAsync(state, t->d_vis_state, c, hipMemcpyDeviceToHost, t->stream));
+  if (scene_gap && c) PFT_HIPCHK(t, hipMemcpyAsync(scene_gap, t->d_vis_sgap, c * sizeof(float), hipMemcpyDeviceToHost, t->stream));
+  if (self_gap && c) PFT_HIPCHK(t, hipMemcpyAsync(self_gap, t->d_vis_mgap, c * sizeof(float), hipMemcpyDeviceToHost, t->stream));
   PFT_HIPCHK(t, hipStreamSynchronize(t->stream));
   return pftt_check_device_error(t);
 }

@@ -258,6 +258,7 @@ extern "C" int pft_compute(pft_tracker* t) {
     return PFT_ERR_STATE;
   }
   t->tree_of_compute = false;
+  t->match_of_compute = false;
   if (!t->initialized) stage_init_particles(t);
   if (!t->cd_latched) {  // initCompute() creates the change detector at the resolution in force now
     t->cd_res_latched = t->cd_res;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pft.h"
+#include "../../include/pft_visibility.h"
 
 #define PFT_MAX_DEVICES 64      // per-device caches of one-time kernel attributes
 #define PFT_MAX_DEPTH 30
@@ -346,6 +347,40 @@ void pftk_match(hipStream_t s, const PftParams& p, const PftDev& d, double min_r
 uint32_t pftk_spread_blocks(uint32_t n_max);
 void pftk_spread(hipStream_t s, const PftDev& d, uint32_t n_max, double* part, uint32_t* part_zero, float* part_wmax,
                  uint32_t* part_imax, double max_pos_sigma, double min_n_eff, uint32_t after, pft_population_stats* out);
+// visibility of the reference cloud at a pose (pft_visibility.hip)
+struct PftVisCam {  // pft_visibility_config as the kernels take it (the margins rounded to float once)
+  int W, H, splat;
+  float fx, fy, cx, cy, z_near, occlusion_margin, self_margin;
+};
+struct PftVisArgs {
+  float m[12];               // the explicit matrix (use_rep == 0)
+  uint32_t use_rep;          // T = pose_to_matrix(PftHeader::rep); a failed last iteration is then not evaluated
+  uint32_t match_enqueued;   // use_rep, and a pft_match for this reference cloud was enqueued after the last pft_compute
+  uint32_t lost_after;
+  double min_visible_ratio, min_ratio;
+};
+struct PftVisCtl {  // written by k_vis_model, read by the two launches behind it
+  float T[12];
+  uint32_t run;              // 0: nothing is evaluated
+  int u0, v0, u1, v1;        // pixel rectangle of the in-view model points
+  uint32_t zmax;             // bits of their largest z
+  uint32_t n_in_view;
+};
+struct PftVisBufs {
+  PftVisCtl* ctl;
+  uint32_t* zbuf;            // [2 W H] depth bits: the frame's image, then the model's
+  uint2* q;                  // [M] stored order: {bits of the moved z, pixel or 0xffffffff}
+  uint8_t* state;            // [M] the caller's order, as scene_gap and self_gap
+  float *scene_gap, *self_gap;
+  pft_visibility_stats* out;
+};
+PftVisCam pftk_visibility_cam(const pft_visibility_config& c);
+void pftk_visibility_clear(hipStream_t s, const PftVisBufs& b, uint32_t M);
+// fill, model, frame (pts: N records of stride4 x 16 bytes, or *n_dev of them), classify; match / match_idx: the block and
+// the pairs of pft_match (read only with a.match_enqueued)
+void pftk_visibility(hipStream_t s, const PftDev& d, uint32_t M, const float4* pts, uint32_t stride4, uint32_t N,
+                     const uint32_t* n_dev, const PftVisCam& cam, const PftVisArgs& a, const PftVisBufs& b,
+                     const pft_match_stats* match, const int32_t* match_idx, int num_cus);
 // re-acquisition (pft_reacquire.hip): the orientation lattice, the per-candidate score arrays (K each, owned by the feature)
 struct PftRqLattice {
   uint32_t n[3];             // roll, pitch, yaw steps (>= 1)

@@ -2,7 +2,7 @@
 //   pft_api.hip           names, config, profiling, create / destroy, reference, input, hand-offs, particles, result
 //   pft_frame.hip         the stages of a frame, pft_compute with its graph capture, the pft_dist_* phases
 //   pft_api_debug.hip     pft_eval_weights, the pft_debug_* hooks, the state checkpoint
-//   pft_api_features.hip  change-detector settings, report, match, spread, re-acquisition, refinement
+//   pft_api_features.hip  change-detector settings, report, match, spread, visibility, re-acquisition, refinement
 // Internal: nothing outside csrc/ includes this.
 //
 // Device memory: every buffer the handle owns is a DevBuf (pft_devbuf.h), so deleting the handle frees it and no list of
@@ -174,6 +174,21 @@ struct pft_tracker {
   bool spread_issued = false;    // a pft_spread has been enqueued: d_spread holds (or will hold) its result
   double spread_max_pos_sigma = INFINITY, spread_min_n_eff = 0.0;
   int spread_after = 1;
+
+  // visibility (pft_visibility): the camera, the rule's settings, the result block with the rule's state, the two depth
+  // images (one buffer, sized for the largest camera used), the moved points and the per-point results
+  pft_visibility_config vis_cam;     // (set by pft_create: pft_visibility_config_default)
+  double vis_min_visible_ratio = 0.25, vis_min_ratio = 0.0;
+  int vis_lost_after = 1;
+  DevBuf<pft_visibility_stats> d_vis;
+  DevBuf<PftVisCtl> d_vis_ctl;
+  DevBuf<uint32_t> d_vis_z;
+  DevBuf<uint2> d_vis_q;
+  DevBuf<uint8_t> d_vis_state;
+  DevBuf<float> d_vis_sgap, d_vis_mgap;  // (d_vis_mgap is allocated last of the four: its cap() is the points all have room for)
+  uint32_t vis_n = 0;                // reference points of the last pft_visibility (0: none since the reference was last set)
+  bool vis_issued = false;           // a pft_visibility has been enqueued: d_vis holds (or will hold) its result
+  bool match_of_compute = false;     // a pft_match has been enqueued since the last pft_compute
 
   // re-acquisition (pft_reacquire): buffers of the feature's own, sized for the largest K seen (never the handle's
   // particle_num-sized ones): candidates, their matrices, the scores, the partial boxes of k_aabb, the result block

@@ -7,6 +7,7 @@
 //                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
 //                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]]
 //                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]
+//                     [--visibility[=min_visible_ratio[,occlusion_margin]]]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -50,6 +51,12 @@
 // prepares its objects, and is tracked from the next frame on: one `discover frame <f>: cluster <c> -> obj <j> (<n> points)`
 // line per new object, and with --match one `support obj <j> <n>` line per subtracted object (the frame points it holds).
 // A frame in which an object is lost discovers nothing: the lost object's own points are unexplained there.
+// --visibility[=min_visible_ratio[,occlusion_margin]] enqueues the visibility of every model at its result pose behind the
+// match (pft_visibility: two depth images from the camera at the origin) and prints one `visibility obj <j> visible <n>/<M>
+// occluded <n> self <n> out <n>` line per object and frame.  With --match the occlusion-aware rule decides about a loss: an
+// object of which less than min_visible_ratio is visible is `Object occluded`, never `Object not recognized`, and
+// --reset-on-loss and --reacquire leave it alone; otherwise it is lost after lost_after frames in a row in which fewer than
+// min_ratio of its VISIBLE points were matched.
 // --reacquire-residual (with --reacquire): the segmentation that serves the lost objects runs on the frame minus the objects
 // that are not lost, so a lost object is never scored at the cluster of an object that is still tracked.
 #include <cstdlib>
@@ -164,6 +171,19 @@ int main(int argc, char** argv) {
       }
     }
     else if (!std::strcmp(argv[i], "--reacquire-residual")) opt.reacquire_residual = true;
+    else if (!std::strncmp(argv[i], "--visibility", 12) && (argv[i][12] == 0 || argv[i][12] == '=')) {
+      opt.visibility = true;  // --visibility[=min_visible_ratio[,occlusion_margin]]; the defaults 0.25,0.03
+      if (argv[i][12] == '=') {
+        double ratio = opt.vis_min_visible_ratio, margin = opt.vis_occlusion_margin;
+        const int got = std::sscanf(argv[i] + 13, "%lf,%lf", &ratio, &margin);
+        if (got < 1 || !(ratio >= 0.0 && ratio <= 1.0) || !(margin >= 0.0) || !std::isfinite(margin)) {
+          std::fprintf(stderr, "--visibility=min_visible_ratio[,occlusion_margin] with min_visible_ratio in [0, 1] and occlusion_margin >= 0\n");
+          return 2;
+        }
+        opt.vis_min_visible_ratio = ratio;
+        opt.vis_occlusion_margin = margin;
+      }
+    }
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -175,7 +195,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -262,6 +282,7 @@ int main(int argc, char** argv) {
       }
       if (opt.device_report) kv.second->computeReport();
       if (opt.match) kv.second->computeMatch();
+      if (opt.visibility) kv.second->computeVisibility();  // behind the match: its pairs count the visible matched points
       if (opt.spread) kv.second->computeSpread();
     }
     std::vector<int> lost;  // --reacquire: the objects the match reported lost in this frame
@@ -269,6 +290,7 @@ int main(int argc, char** argv) {
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
       if (opt.spread) v.reportSpread(kv.first);
+      if (opt.visibility) v.reportVisibility(kv.first);
       if (opt.match && v.reportMatch(f + 1, kv.first, !opt.reacquire)) {
         any_lost = true;
         if (opt.reacquire) lost.push_back(kv.first);

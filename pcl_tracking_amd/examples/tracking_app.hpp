@@ -66,6 +66,9 @@ struct Options {
   double spread_max_pos_sigma = HUGE_VAL;  // uncertain after spread_after calls in a row above this position sigma
   double spread_min_n_eff = 0.0;        // or below this effective sample size
   int spread_after = 1;
+  bool visibility = false;              // --visibility: setVisibilityCamera / computeVisibility / getVisibility per frame
+  double vis_min_visible_ratio = 0.25;  // hidden below this visible share of the model
+  double vis_occlusion_margin = 0.03;
   bool reacquire = false;               // a lost object is looked for among the clusters of the frame (pft_reacquire)
   bool refine = false;                  // --refine: the best candidate of a re-acquisition is refined (pft_refine)
   int rf_max_iterations = 16;
@@ -179,6 +182,13 @@ class TrackingApp {
       tr->setCloudCoherence(coherence);
       if (opt_.match) tr->setMatchThreshold(opt_.match_min_ratio, opt_.match_lost_after);
       if (opt_.spread) tr->setSpreadThreshold(opt_.spread_max_pos_sigma, opt_.spread_min_n_eff, opt_.spread_after);
+      if (opt_.visibility) {  // the occlusion-aware rule takes over the match's thresholds
+        pft_visibility_config cam;
+        pft_visibility_config_default(&cam);
+        cam.occlusion_margin = opt_.vis_occlusion_margin;
+        tr->setVisibilityCamera(cam);
+        tr->setVisibilityThreshold(opt_.vis_min_visible_ratio, opt_.match_min_ratio, opt_.match_lost_after);
+      }
       configure(*tr, obj_id);
       tracker_dict[obj_id] = tr;
     }
@@ -258,7 +268,8 @@ class TrackingApp {
 
   // the match hook of one object and frame, after its computeMatch(): prints the `match` line; a lost object gets the
   // reference's message (:695) and, with --reset-on-loss, a resetTracking() -- unless the caller deals with the loss itself
-  // (reset = false: --reacquire).  Returns true when the object is lost
+  // (reset = false: --reacquire).  With --visibility the loss is the occlusion-aware rule's, and a hidden object gets
+  // `Object occluded` instead.  Returns true when the object is lost
   bool reportMatch(size_t frame, int obj_id, bool reset = true) {
     ParticleFilter& tr = *tracker_dict[obj_id];
     const pft_match_stats m = tr.getMatch();
@@ -267,10 +278,26 @@ class TrackingApp {
                 frame, obj_id, m.n_matched, m.n_reference, ratio, m.coherence,
                 m.n_matched ? std::sqrt(m.sum_sq_dist / (double)m.n_matched) : 0.0, m.n_crop, m.evaluated, m.below, m.streak,
                 m.lost);
-    if (!m.lost) return false;
+    bool lost = m.lost != 0;
+    if (opt_.visibility) {  // the occlusion-aware rule decides: a hidden object is not lost, whatever its match says
+      const pft_visibility_stats vis = tr.getVisibility();
+      if (vis.hidden) {
+        std::fprintf(stderr, "frame %zu object %d: Object occluded\n", frame, obj_id);
+        return false;
+      }
+      lost = vis.lost != 0;
+    }
+    if (!lost) return false;
     std::fprintf(stderr, "frame %zu object %d: Object not recognized\n", frame, obj_id);
     if (reset && opt_.reset_on_loss) tr.resetTracking();
     return true;
+  }
+
+  // the visibility hook of one object and frame, after its computeVisibility(): prints the `visibility` line
+  void reportVisibility(int obj_id) {
+    const pft_visibility_stats vis = tracker_dict[obj_id]->getVisibility();
+    std::printf("visibility obj %d visible %u/%u occluded %u self %u out %u\n", obj_id, vis.n_visible, vis.n_reference,
+                vis.n_occluded, vis.n_self, vis.n_out);
   }
 
   // the spread hook of one object and frame, after its computeSpread(): prints the `spread` line (every value round-trips)

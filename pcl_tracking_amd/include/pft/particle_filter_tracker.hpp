@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "pft.h"
+#include "pft_visibility.h"
 
 namespace pft {
 
@@ -448,6 +449,68 @@ class ParticleFilterTracker {
   }
   bool isUncertain() const { return handle_ && getSpread().flagged != 0; }
 
+  // ---- visibility of the model at a pose, the occlusion-aware lost rule (pft_visibility.h) ----
+  // the pinhole camera at the origin, looking along +z, of the computeVisibility() calls that follow; a value outside its
+  // range is reported and not kept
+  int setVisibilityCamera(const pft_visibility_config& cam) {
+    if (handle_) {
+      const int st = check(pft_set_visibility_camera(handle_, &cam), "setVisibilityCamera");
+      if (st != PFT_OK) return st;
+    }
+    vis_cam_ = cam;
+    vis_cam_set_ = true;
+    return PFT_OK;
+  }
+  pft_visibility_config getVisibilityCamera() const {
+    pft_visibility_config c;
+    if (handle_ && pft_get_visibility_camera(handle_, &c) == PFT_OK) return c;
+    if (vis_cam_set_) return vis_cam_;
+    pft_visibility_config_default(&c);
+    return c;
+  }
+  // hidden while fewer than min_visible_ratio * (reference points) are visible; lost after `lost_after` evaluated, matched,
+  // not hidden frames in a row with fewer than min_ratio * (visible points) of the visible points matched
+  int setVisibilityThreshold(double min_visible_ratio, double min_ratio = 0.0, int lost_after = 1) {
+    if (!(min_visible_ratio >= 0.0 && min_visible_ratio <= 1.0) || !(min_ratio >= 0.0 && min_ratio <= 1.0) || lost_after < 1)
+      return check(PFT_ERR_INVALID_ARG, "setVisibilityThreshold");
+    if (handle_) {
+      const int st = check(pft_set_visibility_threshold(handle_, min_visible_ratio, min_ratio, lost_after), "setVisibilityThreshold");
+      if (st != PFT_OK) return st;
+    }
+    vis_min_visible_ratio_ = min_visible_ratio;
+    vis_min_ratio_ = min_ratio;
+    vis_lost_after_ = lost_after;
+    return PFT_OK;
+  }
+  // enqueues the visibility of the reference cloud against the input cloud the handle holds (the one of the last
+  // compute()) on the tracker's stream; nothing waits.  m12: a row-major 3x4 matrix; nullptr: the last result pose
+  int computeVisibility(const float* m12 = nullptr) {
+    if (!handle_) return check(PFT_ERR_STATE, "computeVisibility");
+    return check(pft_visibility(handle_, m12), "computeVisibility");
+  }
+  // waits for the last computeVisibility()
+  pft_visibility_stats getVisibility() const {
+    pft_visibility_stats v;
+    std::memset(&v, 0, sizeof(v));
+    if (handle_) check(pft_get_visibility(handle_, &v), "getVisibility");
+    return v;
+  }
+  // per reference point, in the order of setReferenceCloud: PFT_VIS_* and the two depth gaps
+  void getVisibilityPoints(std::vector<uint8_t>& state, std::vector<float>& scene_gap, std::vector<float>& self_gap) const {
+    state.clear();
+    scene_gap.clear();
+    self_gap.clear();
+    size_t n = 0;
+    if (handle_ && check(pft_get_visibility_points(handle_, nullptr, nullptr, nullptr, 0, &n), "getVisibilityPoints") == PFT_OK && n) {
+      state.resize(n);
+      scene_gap.resize(n);
+      self_gap.resize(n);
+      check(pft_get_visibility_points(handle_, state.data(), scene_gap.data(), self_gap.data(), n, &n), "getVisibilityPoints");
+    }
+  }
+  bool isOccluded() const { return handle_ && getVisibility().hidden != 0; }
+  bool isLostVisible() const { return handle_ && getVisibility().lost != 0; }
+
   // ---- re-acquisition of a lost object (pft.h, pft_reacquire) ----
   // every centre (n_centres x 3 floats) with every orientation of cfg's lattice is scored against the input cloud the handle
   // holds -- the one of the last compute() --; with cfg.apply and an accepted candidate the tracker is restarted at it:
@@ -581,6 +644,9 @@ class ParticleFilterTracker {
       check(pft_set_match_threshold(handle_, match_min_ratio_, match_lost_after_), "setMatchThreshold");
     if (spread_max_pos_sigma_ != HUGE_VAL || spread_min_n_eff_ != 0.0 || spread_after_ != 1)
       check(pft_set_spread_threshold(handle_, spread_max_pos_sigma_, spread_min_n_eff_, spread_after_), "setSpreadThreshold");
+    if (vis_cam_set_) check(pft_set_visibility_camera(handle_, &vis_cam_), "setVisibilityCamera");
+    if (vis_min_visible_ratio_ != 0.25 || vis_min_ratio_ != 0.0 || vis_lost_after_ != 1)
+      check(pft_set_visibility_threshold(handle_, vis_min_visible_ratio_, vis_min_ratio_, vis_lost_after_), "setVisibilityThreshold");
     if (ref_) check(pft_set_reference(handle_, ref_->points.data(), ref_->points.size()), "setReferenceCloud");
     if (report_cloud_)
       check(pft_set_report_cloud(handle_, report_cloud_->points.data(), report_cloud_->points.size()), "setReportCloud");
@@ -604,6 +670,10 @@ class ParticleFilterTracker {
   int match_lost_after_ = 1;
   double spread_max_pos_sigma_ = HUGE_VAL, spread_min_n_eff_ = 0.0;  // setSpreadThreshold
   int spread_after_ = 1;
+  pft_visibility_config vis_cam_ = {};  // setVisibilityCamera
+  bool vis_cam_set_ = false;
+  double vis_min_visible_ratio_ = 0.25, vis_min_ratio_ = 0.0;  // setVisibilityThreshold
+  int vis_lost_after_ = 1;
 };
 
 // the class the reference actually news (auto_tracking.cpp:203-204); the thread count is the OpenMP team

@@ -93,6 +93,37 @@ class MatchStats:
 
 
 @dataclass
+class VisibilityStats:
+    """pft_visibility_stats: how much of the model the camera sees at a pose, and the occlusion-aware lost rule's state"""
+    transform: np.ndarray  # 3x4 float32, the T used
+    n_reference: int
+    n_visible: int
+    n_occluded: int        # covered by the scene: a frame point lies more than occlusion_margin in front
+    n_self: int            # covered by the model itself
+    n_out: int             # behind the near plane or outside the image
+    n_frame: int
+    has_match: bool        # the counts of a computeMatch() of the same frame were at hand
+    n_visible_matched: int
+    hidden: bool           # n_visible < min_visible_ratio * n_reference
+    below: bool            # n_visible_matched < min_ratio * n_visible (never while hidden or without a match)
+    streak: int
+    lost: bool             # streak >= lost_after
+    evaluated: bool
+    calls: int
+
+    @property
+    def visible_ratio(self):
+        return self.n_visible / self.n_reference if self.n_reference else 0.0
+
+    @classmethod
+    def from_struct(cls, r):
+        kw = {f: int(getattr(r, f)) for f in ("n_reference", "n_visible", "n_occluded", "n_self", "n_out", "n_frame",
+                                               "n_visible_matched", "streak", "calls")}
+        kw.update({f: bool(getattr(r, f)) for f in ("has_match", "hidden", "below", "lost", "evaluated")})
+        return cls(transform=np.array(r.transform, dtype=np.float32).reshape(3, 4), **kw)
+
+
+@dataclass
 class PopulationStats:
     """pft_population_stats: how sure the filter is about its pose"""
     sum_w: float           # the 29 tree sums in double: weights, squared weights,
@@ -292,6 +323,8 @@ class ParticleFilterTracker:
         self._cd = [False, 10, 10, 0.01]
         self._match_thr = (0.0, 1)  # pft_set_match_threshold: min_ratio, lost_after
         self._spread_thr = (float("inf"), 0.0, 1)  # pft_set_spread_threshold: max_pos_sigma, min_n_eff, after
+        self._vis_cam = None  # pft_set_visibility_camera: a VisibilityConfig once set (None: the library's default)
+        self._vis_thr = (0.25, 0.0, 1)  # pft_set_visibility_threshold: min_visible_ratio, min_ratio, lost_after
         self._rq_centres = 0  # centres of the last reacquire()
         self.setSumOrder(sum_order)
         self._trans = np.eye(4, dtype=np.float32)
@@ -431,6 +464,10 @@ class ParticleFilterTracker:
                 self._check(self._L.pft_set_match_threshold(self._h, *self._match_thr))
             if self._spread_thr != (float("inf"), 0.0, 1):
                 self._check(self._L.pft_set_spread_threshold(self._h, *self._spread_thr))
+            if self._vis_cam is not None:
+                self._check(self._L.pft_set_visibility_camera(self._h, C.byref(self._vis_cam)))
+            if self._vis_thr != (0.25, 0.0, 1):
+                self._check(self._L.pft_set_visibility_threshold(self._h, *self._vis_thr))
             if self._ref is not None:
                 self._check(self._L.pft_set_reference(self._h, _ptr(self._ref), len(self._ref)))
             if self._report_cloud is not None:
@@ -640,6 +677,91 @@ class ParticleFilterTracker:
     def isUncertain(self):
         """the flag of the spread rule after the last computeSpread() (waits for it)"""
         return self.getSpread().flagged
+
+    # ---- visibility of the model at a pose, the occlusion-aware lost rule ----
+    def setVisibilityCamera(self, width=160, height=90, fx=90.0, fy=90.0, cx=79.5, cy=44.5, z_near=0.05, splat=1,
+                            occlusion_margin=0.03, self_margin=0.03):
+        """the pinhole camera at the origin, looking along +z, that computeVisibility() renders its two depth images with
+        (the default: a Kinect2 qhd camera divided by six), the splat half-width and the two depth margins in metres"""
+        c = _lib.VisibilityConfig(int(width), int(height), float(fx), float(fy), float(cx), float(cy), float(z_near),
+                                  int(splat), float(occlusion_margin), float(self_margin))
+        if self._h is not None:
+            self._check(self._L.pft_set_visibility_camera(self._h, C.byref(c)))
+        else:  # (the library's refusals, before there is a handle to ask)
+            ok = (1 <= c.width <= 1024 and 1 <= c.height <= 1024 and 0 <= c.splat <= 4 and
+                  all(np.isfinite(v) for v in (c.fx, c.fy, c.cx, c.cy, c.z_near, c.occlusion_margin, c.self_margin)) and
+                  c.fx > 0 and c.fy > 0 and c.z_near >= 0 and c.occlusion_margin >= 0 and c.self_margin >= 0)
+            if not ok:
+                raise PftError(1, "setVisibilityCamera: a value outside its range (include/pft_visibility.h)")
+        self._vis_cam = c
+
+    def getVisibilityCamera(self):
+        """the camera in force as a dict of pft_visibility_config's fields"""
+        c = _lib.VisibilityConfig()
+        if self._h is not None:
+            self._check(self._L.pft_get_visibility_camera(self._h, C.byref(c)))
+        elif self._vis_cam is not None:
+            c = self._vis_cam
+        else:
+            self._L.pft_visibility_config_default(C.byref(c))
+        return {f: getattr(c, f) for f, _ in c._fields_}
+
+    def setVisibilityThreshold(self, min_visible_ratio=0.25, min_ratio=0.0, lost_after=1):
+        """the object counts as hidden while fewer than min_visible_ratio * (reference points) are visible, and as lost
+        after `lost_after` evaluated, matched, not hidden frames in a row in which fewer than min_ratio * (visible points)
+        of the visible points were matched; (0.25, 0, 1), the default, never fires.  Callable at any time"""
+        thr = (float(min_visible_ratio), float(min_ratio), int(lost_after))
+        if not (0.0 <= thr[0] <= 1.0) or not (0.0 <= thr[1] <= 1.0) or thr[2] < 1:
+            raise PftError(1, "setVisibilityThreshold: min_visible_ratio and min_ratio in [0, 1], lost_after >= 1")
+        if self._h is not None:
+            self._check(self._L.pft_set_visibility_threshold(self._h, *thr))
+        self._vis_thr = thr
+
+    def getVisibilityThreshold(self):
+        return self._vis_thr
+
+    def computeVisibility(self, matrix=None):
+        """enqueues the visibility of the reference cloud against the current input cloud on the tracker's stream; nothing
+        waits.  matrix: a 3x4 (or 4x4) float transform; None: the result pose of the last compute()"""
+        if matrix is None:
+            if self._h is None:
+                raise PftError(7, "computeVisibility before the first compute()")
+            self._check(self._L.pft_visibility(self._h, None))
+            return
+        self._ensure()
+        m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(-1)[:12])
+        if m.size != 12:
+            raise PftError(1, "computeVisibility: the matrix must have 3x4 or 4x4 entries")
+        self._check(self._L.pft_visibility(self._h, _ptr(m)))
+
+    def getVisibility(self):
+        """waits for the last computeVisibility(); returns VisibilityStats"""
+        if self._h is None:
+            raise PftError(7, "getVisibility before the first computeVisibility()")
+        r = _lib.VisibilityStatsStruct()
+        self._check(self._L.pft_get_visibility(self._h, C.byref(r)))
+        return VisibilityStats.from_struct(r)
+
+    def getVisibilityPoints(self):
+        """per reference point in the order of setReferenceCloud: (state uint8 -- 0 visible, 1 occluded by the scene,
+        2 occluded by the model itself, 3 out of view --, scene_gap float32, self_gap float32)"""
+        if self._h is None:
+            raise PftError(7, "getVisibilityPoints before the first computeVisibility()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_visibility_points(self._h, None, None, None, 0, C.byref(n)))
+        st = np.zeros(n.value, np.uint8)
+        sg = np.zeros(n.value, np.float32)
+        mg = np.zeros(n.value, np.float32)
+        self._check(self._L.pft_get_visibility_points(self._h, _ptr(st), _ptr(sg), _ptr(mg), n.value, C.byref(n)))
+        return st, sg, mg
+
+    def isOccluded(self):
+        """the hidden flag of the last computeVisibility() (waits for it)"""
+        return self.getVisibility().hidden
+
+    def isLostVisible(self):
+        """the lost flag of the occlusion-aware rule after the last computeVisibility() (waits for it)"""
+        return self.getVisibility().lost
 
     # ---- re-acquisition of a lost object ----
     def reacquire(self, centres=None, segmenter=None, n=(1, 1, 8), span=(0.0, 0.0, 2.0 * np.pi), base_rpy=None,
