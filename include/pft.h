@@ -540,6 +540,31 @@ int pft_debug_get_ticks(pft_tracker* t, uint64_t* ticks32);
  * [27..29] zero, [30] reference points the particles' bounding box is taken over (the hull subset), [31] all reference
  * points (the exact-NN mode puts its own bookkeeping into [8..13]) */
 int pft_debug_get_descent_stats(pft_tracker* t, uint64_t* dbg32);
+/* NearestPairPointCloudCoherence handles (exact_nearest; PFT_ERR_INVALID_ARG on others, PFT_ERR_STATE before the first input
+ * cloud): the search structure's state after the last iteration -- which of its capacity fallbacks were taken.
+ * info [PFT_EXACT_STATE_WORDS]: [0] grid cell edge eg_g (float bits), [1..3] eg_dim, [4..6] eg_min (float bits), [7] eg_ncells,
+ * [8] n_crop, [9] ec_nslots (cells hit by queries, may exceed the slot capacity), [10] ec_pool_used (candidate entries asked
+ * for, may exceed the pool), [11] ec_pool_cap of that iteration, [12] queries and [13] 64-query blocks of the cell-sorted
+ * search (the two halves of eq_totals), [14] slot capacity in force, [15] grid cell capacity, [16] per-tile count tables
+ * allocated, [17] capacity of the cell-sorted query array, [18] PFT_EC_SLOTS, [19] PFT_EC_POOL, [20] PFT_EG_CAP,
+ * [21] PFT_EC_POOL_MIN, [22] compute units (the tiles of the LDS-aggregated passes hold ceil(P / CUs) particles, at most 32).
+ * counters [8] (optional), written only by the instantiations that also write the NN arrays, so valid after a
+ * pft_eval_weights call that asked for them (which zeroes them first): words 24..28 of the header's debug block -- [0] queries
+ * k_eq_scatter placed through the probe-window-full branch, [1] queries it answered inline by the shell search, [2] inline
+ * as "empty list", [3] queries k_likelihood_exact sent to the shell search, [4] k_eq_scatter queries outside the grid --
+ * then words 0, 1, 3 of k_likelihood_exact: [5] its queries, [6] those served by a list, [7] those outside the grid.
+ * (Words 0..6 are read by tools/exact_nn_bench.py, 8..13 and 30..31 are overlaid by pft_debug_get_descent_stats, 16..20
+ * belong to -DPFT_EC_TIMING.)
+ * Per-slot arrays ec_cells / ec_count (0xffffffff: no list, the pool was full) / ec_base, each optional, receive
+ * min(slots_cap, ec_nslots, slot capacity) entries; eg_start receives min(eg_start_cap, eg_ncells + 1) cell starts of the
+ * counting sort and leaf_order min(leaf_order_cap, n_crop) crop positions in sorted order. */
+#define PFT_EXACT_STATE_WORDS 32
+int pft_debug_get_exact_state(pft_tracker* t, uint32_t* info, uint64_t* counters, uint32_t* ec_cells, uint32_t* ec_count,
+                              uint32_t* ec_base, size_t slots_cap, uint32_t* eg_start, size_t eg_start_cap,
+                              uint32_t* leaf_order, size_t leaf_order_cap);
+/* exact_nearest handles: the candidate-list slots handed out per iteration, 1 .. PFT_EC_SLOTS (the allocation; above it
+ * PFT_ERR_CAPACITY).  Cells beyond the limit get no list and no segment: their queries take the shell search */
+int pft_debug_set_exact_limits(pft_tracker* t, uint32_t ec_slots);
 /* the same call's queries by number of "hard" generic steps (the per-axis nearest child is absent): 0, 1, 2, 3, >= 4 */
 int pft_debug_get_hard_steps(pft_tracker* t, uint64_t out5[5]);
 /* what the likelihood kernel chose in the last pft_eval_weights call that asked for the NN arrays (zero otherwise):

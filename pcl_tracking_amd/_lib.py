@@ -11,6 +11,7 @@ PFT_ABI_VERSION = 5
 PFT_SUM_TREE, PFT_SUM_PCL = 0, 1  # pft_config::sum_order
 PFT_CD_RING = 32  # decisions kept by the change detector (pft_debug_change_state)
 PFT_TREE_INFO_WORDS = 64  # pft_debug_get_tree's info block
+PFT_EXACT_STATE_WORDS = 32  # pft_debug_get_exact_state's info block
 K_RESAMPLE, K_AABB, K_CROP, K_OCTREE, K_LIKELIHOOD, K_POPULATION, K_PACK, K_COUNT = range(8)
 
 STATUS = {0: "ok", 1: "invalid argument", 2: "no input cloud", 3: "no reference cloud", 4: "no usable HIP device",
@@ -250,6 +251,8 @@ SYMBOLS = [
     ("pft_debug_get_host_stat", C.c_int, [_vp, _vp]),
     ("pft_debug_get_ticks", C.c_int, [_vp, _vp]),
     ("pft_debug_get_descent_stats", C.c_int, [_vp, _vp]),
+    ("pft_debug_get_exact_state", C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz]),
+    ("pft_debug_set_exact_limits", C.c_int, [_vp, _u32]),
     ("pft_debug_get_likelihood_layout", C.c_int, [_vp, _vp]),
     ("pft_debug_get_ancestor_table", C.c_int, [_vp, _vp, _vp, _sz]),
     ("pft_debug_get_ancestor_level", C.c_int, [_vp, _vp]),

@@ -228,6 +228,7 @@ void pftt_sync_dev(pft_tracker* t) {
   d.ec_base = t->d_ec_base;
   d.ec_list = t->d_ec_list;
   d.ec_pool_cap = (uint32_t)t->d_ec_list.cap();
+  d.ec_slots_cap = t->ec_slots_cap;
   d.eq_cellq = t->d_eq_cellq;
   d.eq_nq = t->d_eq_nq;
   d.eq_qbase = t->d_eq_qbase;

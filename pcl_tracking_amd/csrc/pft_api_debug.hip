@@ -21,6 +21,14 @@ extern "C" int pft_debug_set_limits(pft_tracker* t, uint32_t max_words, int sort
   pftt_sync_dev(t);
   return PFT_OK;
 }
+extern "C" int pft_debug_set_exact_limits(pft_tracker* t, uint32_t ec_slots) {
+  if (!t || !t->cfg.exact_nearest || !ec_slots) return PFT_ERR_INVALID_ARG;
+  if (ec_slots > PFT_EC_SLOTS) return PFT_ERR_CAPACITY;  // only ever below the allocation
+  hipStreamSynchronize(t->stream);
+  t->ec_slots_cap = ec_slots;
+  pftt_sync_dev(t);
+  return PFT_OK;
+}
 // ---- checkpoint of the filter state (between frames): the whole population with its weights, the alias prefix form the
 // next resample draws from, the header (representative state, motion, KLD particle count) and the host-side schedule
 // state.  Restoring is ONE kernel on the handle's stream, so a benchmark can replay the same frame again and again.
@@ -330,6 +338,56 @@ extern "C" int pft_debug_get_descent_stats(pft_tracker* t, uint64_t* dbg32) {
     dbg32[12] = h.eg_ncells;
     dbg32[13] = h.n_crop;
   }
+  return PFT_OK;
+}
+
+// The exact-NN mode's state after the last iteration (evaluation or tracked frame): which capacity fallbacks were taken.
+// The route counters are words of PftHeader::dbg that only the DEBUG_NN instantiations write (pft_eval_weights with the
+// NN arrays, which zeroes them first): [24] k_eq_scatter queries placed through the probe-window-full branch, [25] its
+// queries answered inline by the shell search, [26] inline as "empty list", [27] k_likelihood_exact queries sent to the
+// shell search, [28] k_eq_scatter queries outside the grid; k_likelihood_exact keeps [0..6] (tools/exact_nn_bench.py: [0]
+// queries, [1] served by a list, [3] outside the grid), pft_debug_get_descent_stats overlays [8..13] and [30..31] in its
+// copy, -DPFT_EC_TIMING uses [16..20]
+extern "C" int pft_debug_get_exact_state(pft_tracker* t, uint32_t* info, uint64_t* counters, uint32_t* ec_cells,
+                                         uint32_t* ec_count, uint32_t* ec_base, size_t slots_cap, uint32_t* eg_start,
+                                         size_t eg_start_cap, uint32_t* leaf_order, size_t leaf_order_cap) {
+  if (!t || !info || !t->cfg.exact_nearest) return PFT_ERR_INVALID_ARG;
+  if (t->in_cap == 0 || !t->d_eg_start) {
+    t->err = "pft_debug_get_exact_state before the first input cloud: no grid buffers yet";
+    return PFT_ERR_STATE;
+  }
+  hipSetDevice(t->cfg.device_id);
+  PftHeader h;
+  int r = read_hdr(t, &h);  // (synchronises the stream)
+  if (r != PFT_OK) return r;
+  memset(info, 0, PFT_EXACT_STATE_WORDS * sizeof(uint32_t));
+  memcpy(&info[0], &h.eg_g, 4);
+  for (int a = 0; a < 3; a++) {
+    info[1 + a] = (uint32_t)h.eg_dim[a];
+    memcpy(&info[4 + a], &h.eg_min[a], 4);
+  }
+  info[7] = h.eg_ncells; info[8] = h.n_crop; info[9] = h.ec_nslots; info[10] = h.ec_pool_used;
+  info[11] = t->dev.ec_pool_cap; info[12] = (uint32_t)(h.eq_totals & 0xffffffffull); info[13] = (uint32_t)(h.eq_totals >> 32);
+  info[14] = t->dev.ec_slots_cap; info[15] = t->dev.eg_cap; info[16] = t->dev.eq_tiles_cap; info[17] = t->dev.eq_cap;
+  info[18] = PFT_EC_SLOTS; info[19] = PFT_EC_POOL; info[20] = PFT_EG_CAP; info[21] = PFT_EC_POOL_MIN;
+  info[22] = (uint32_t)t->num_cus;
+  if (counters) {
+    const int words[8] = {24, 25, 26, 27, 28, 0, 1, 3};
+    for (int k = 0; k < 8; k++) counters[k] = h.dbg[words[k]];
+  }
+  // (counts are bounded by the allocations whatever the header says)
+  const size_t n_slots = std::min<size_t>(std::min(h.ec_nslots, t->dev.ec_slots_cap), PFT_EC_SLOTS);
+  const size_t n_cells = h.n_crop ? std::min<size_t>(h.eg_ncells, PFT_EG_CAP) + 1u : 0u;
+  const size_t n_pts = std::min<size_t>(h.n_crop, t->in_cap);
+  auto copy = [&](void* dst, const void* src, size_t cap, size_t count, size_t elem) -> hipError_t {
+    const size_t c = std::min(cap, count);
+    return dst && src && c ? hipMemcpy(dst, src, c * elem, hipMemcpyDeviceToHost) : hipSuccess;
+  };
+  PFT_HIPCHK(t, copy(ec_cells, t->d_ec_cells, slots_cap, n_slots, sizeof(uint32_t)));
+  PFT_HIPCHK(t, copy(ec_count, t->d_ec_count, slots_cap, n_slots, sizeof(uint32_t)));
+  PFT_HIPCHK(t, copy(ec_base, t->d_ec_base, slots_cap, n_slots, sizeof(uint32_t)));
+  PFT_HIPCHK(t, copy(eg_start, t->d_eg_start, eg_start_cap, n_cells, sizeof(uint32_t)));
+  PFT_HIPCHK(t, copy(leaf_order, t->d_leaf_order, leaf_order_cap, n_pts, sizeof(uint32_t)));
   return PFT_OK;
 }
 

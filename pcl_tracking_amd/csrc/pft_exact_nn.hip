@@ -166,6 +166,13 @@ void pftk_exact_grid(hipStream_t s, const PftParams& p, const PftDev& d) {
 // only walks its cell's list.  The lists live in one pool (PFT_EC_POOL entries); cells that find it full and queries
 // outside the grid take the shell search below.
 #define EC_NOLIST 0xffffffffu
+// route counters of the DEBUG_NN instantiations, words of PftHeader::dbg (pft_debug_get_exact_state; [0..6] are the list
+// statistics of k_likelihood_exact<true>, [16..20] belong to -DPFT_EC_TIMING)
+#define EQ_DBG_WINDOW_FULL 24   // k_eq_scatter: queries placed in their segment through the probe-window-full branch
+#define EQ_DBG_INLINE_SHELL 25  // k_eq_scatter: queries answered on the spot by the shell search
+#define EQ_DBG_INLINE_EMPTY 26  // k_eq_scatter: queries answered on the spot as "empty list"
+#define EQ_DBG_LIK_SHELL 27     // k_likelihood_exact: queries sent to the shell search
+#define EQ_DBG_OUTSIDE 28       // k_eq_scatter: queries outside the grid (k_likelihood_exact counts them in [3])
 
 // unclamped cell coordinates of a query; false if it lies outside the grid
 __device__ __forceinline__ bool eg_query_cell(const PftHeader* h, float qx, float qy, float qz, int& cx, int& cy, int& cz) {
@@ -284,7 +291,7 @@ __global__ __launch_bounds__(256) void k_ec_slots(PftDev d) {
     if (lane == first) base = atomicAdd(&h->ec_nslots, (uint32_t)__popcll(m));
     base = (uint32_t)__shfl((int)base, first);
     const uint32_t my_slot = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    const bool placed = hit && my_slot < PFT_EC_SLOTS;  // (a cell beyond the slot capacity gets no list and no segment)
+    const bool placed = hit && my_slot < d.ec_slots_cap;  // (a cell beyond the slot capacity gets no list and no segment)
     const uint32_t nb = placed ? (nq + 63u) >> 6 : 0u;
     const unsigned long long mine = ((unsigned long long)nb << 32) | (placed ? nq : 0u);  // (blocks << 32) | queries
     const unsigned long long incl = wave_incl_scan(mine);
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(256) void k_ec_build(PftParams prm, PftDev d) {
   __shared__ float4 stage[4][EC_STAGE];
   __shared__ SegScratch segs[4];
   const PftHeader* h = d.hdr;
-  const uint32_t ns = min(h->ec_nslots, (uint32_t)PFT_EC_SLOTS);
+  const uint32_t ns = min(h->ec_nslots, d.ec_slots_cap);
   const float g = h->eg_g, inv_g = h->eg_inv_g, hh = 0.5f * h->eg_g;
   const int dx_ = h->eg_dim[0], dy_ = h->eg_dim[1], dz_ = h->eg_dim[2];
   const float r = hh * 1.7320508f + 1.0e-4f;  // half diagonal of a cell + slack for the float cell assignment
@@ -696,6 +703,7 @@ __global__ __launch_bounds__(256) void k_likelihood_exact(PftParams prm, PftDev 
             atomicAdd(&d.hdr->dbg[2], (unsigned long long)cnt);
           }
           if (!inside) atomicAdd(&d.hdr->dbg[3], 1ull);
+          if (cnt == EC_NOLIST) atomicAdd(&d.hdr->dbg[EQ_DBG_LIK_SHELL], 1ull);  // sent to the shell search
           int mc = cnt != EC_NOLIST ? (int)cnt : 100000;
           for (int o = 32; o > 0; o >>= 1) mc = max(mc, __shfl_xor(mc, o));
           if (lane == __ffsll((long long)__ballot(1)) - 1) {
@@ -862,8 +870,13 @@ __global__ __launch_bounds__(1024) void k_eq_scatter(PftParams prm, PftDev d, ui
           uint32_t slot = 0;
           route = route_of_cell(c, slot);
           if (!route) pos = d.eq_qbase[slot] + atomicAdd(&d.eq_fill[slot], 1u);
+          if (DEBUG_NN && !route) atomicAdd(&d.hdr->dbg[EQ_DBG_WINDOW_FULL], 1ull);
         }
+      } else if (DEBUG_NN) {
+        atomicAdd(&d.hdr->dbg[EQ_DBG_OUTSIDE], 1ull);
       }
+      if (DEBUG_NN && route >= EQ_INLINE_EMPTY)
+        atomicAdd(&d.hdr->dbg[route == EQ_INLINE_SHELL ? EQ_DBG_INLINE_SHELL : EQ_DBG_INLINE_EMPTY], 1ull);
       if (route < EQ_INLINE_EMPTY) {
         if (pos < d.eq_cap) d.eq_sorted[pos] = make_float4(qx, qy, qz, __uint_as_float(id));
         return;
@@ -895,7 +908,7 @@ __global__ __launch_bounds__(256) void k_eq_search(PftParams prm, PftDev d) {
   for (uint32_t bv = gw; bv < nb; bv += tw) {
     const uint32_t blk = (uint32_t)__builtin_amdgcn_readfirstlane((int)bv);
     const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)d.eq_blk[blk]);
-    if (slot >= PFT_EC_SLOTS) continue;  // (never written by k_ec_slots)
+    if (slot >= d.ec_slots_cap) continue;  // (never written by k_ec_slots)
     const uint32_t j0 = (blk - d.eq_bbase[slot]) * 64u, nq = d.eq_nq[slot];
     const uint32_t n = min(64u, nq - j0);
     const uint32_t cnt = d.ec_count[slot];

@@ -207,6 +207,7 @@ struct PftDev {  // device pointers (host-side struct, passed by value)
   uint32_t* ec_base;         // exact-NN mode: [PFT_EC_SLOTS] first entry of the list in ec_list
   float4* ec_list;           // exact-NN mode: [ec_pool_cap] candidates {x, y, z, position in leaf_pts}
   uint32_t ec_pool_cap;      // entries of ec_list: grows with the demand of the previous iteration, at most PFT_EC_POOL
+  uint32_t ec_slots_cap;     // exact-NN mode: list slots handed out, PFT_EC_SLOTS (the allocation) unless pft_debug_set_exact_limits lowered it
   // exact-NN mode, queries sorted by grid cell (one wave then walks ONE candidate list for 64 queries):
   uint32_t* eq_cellq;        // [eg_cap] queries per grid cell this iteration
   uint32_t* eq_nq;           // [PFT_EC_SLOTS] queries of the slot's cell that are searched through its list

@@ -105,6 +105,7 @@ struct pft_tracker {
   DevBuf<float4> d_eq_sorted;
   DevBuf<double> d_eq_out;
   uint32_t eq_cap = 0, eq_blk_cap = 0, eq_tiles_cap = 0;
+  uint32_t ec_slots_cap = PFT_EC_SLOTS;  // test hook (pft_debug_set_exact_limits): list slots handed out, never above the allocation
   DevBuf<uint32_t> d_kld_table;
   DevBuf<int32_t> d_kld_bins;
   uint32_t dbg_builds = 0;

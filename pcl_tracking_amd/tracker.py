@@ -938,6 +938,40 @@ class ParticleFilterTracker:
         self._ensure()
         self._check(self._L.pft_debug_set_limits(self._h, int(max_words), int(sorted_npass)))
 
+    def debugSetExactLimits(self, ec_slots):
+        """NearestPairPointCloudCoherence handles: lower the candidate-list slots handed out per iteration (never above the
+        allocation); cells beyond the limit take the shell search"""
+        self._ensure()
+        self._check(self._L.pft_debug_set_exact_limits(self._h, int(ec_slots)))
+
+    def debugExactState(self):
+        """the exact-NN search structure after the last iteration (pft_debug_get_exact_state): eg_g, eg_dim, eg_min, eg_ncells,
+        n_crop, ec_nslots, ec_pool_used, ec_pool_cap, eq_queries / eq_blocks (the halves of eq_totals), the capacities in force
+        (ec_slots_cap, eg_cap, eq_tiles_cap, eq_cap) and compiled in (EC_SLOTS, EC_POOL, EG_CAP, EC_POOL_MIN), num_cus; the
+        route counters of the last evalWeights(want_nn=True) (window_full, inline_shell, inline_empty, lik_shell, outside,
+        lik_queries, lik_listed, lik_outside); ec_cells / ec_count / ec_base per placed slot, eg_start [eg_ncells + 1],
+        leaf_order [n_crop]"""
+        self._ensure()
+        info = np.zeros(_lib.PFT_EXACT_STATE_WORDS, np.uint32)
+        ctr = np.zeros(8, np.uint64)
+        self._check(self._L.pft_debug_get_exact_state(self._h, _ptr(info), _ptr(ctr), None, None, None, 0, None, 0, None, 0))
+        n_crop, ncells = int(info[8]), int(info[7])
+        ns = min(int(info[9]), int(info[14]))
+        cells, count, base = (np.zeros(ns, np.uint32) for _ in range(3))
+        start = np.zeros(ncells + 1 if n_crop else 0, np.uint32)
+        order = np.zeros(n_crop, np.uint32)
+        self._check(self._L.pft_debug_get_exact_state(self._h, _ptr(info), None, _ptr(cells), _ptr(count), _ptr(base), ns,
+                                                      _ptr(start), len(start), _ptr(order), n_crop))
+        names = ("window_full", "inline_shell", "inline_empty", "lik_shell", "outside", "lik_queries", "lik_listed", "lik_outside")
+        out = {k: int(v) for k, v in zip(names, ctr)}
+        out.update(eg_g=float(info[0:1].view(np.float32)[0]), eg_dim=info[1:4].astype(np.int64), eg_min=info[4:7].view(np.float32).copy(),
+                   eg_ncells=ncells, n_crop=n_crop, ec_nslots=int(info[9]), ec_pool_used=int(info[10]), ec_pool_cap=int(info[11]),
+                   eq_queries=int(info[12]), eq_blocks=int(info[13]), ec_slots_cap=int(info[14]), eg_cap=int(info[15]),
+                   eq_tiles_cap=int(info[16]), eq_cap=int(info[17]), EC_SLOTS=int(info[18]), EC_POOL=int(info[19]),
+                   EG_CAP=int(info[20]), EC_POOL_MIN=int(info[21]), num_cus=int(info[22]),
+                   ec_cells=cells, ec_count=count, ec_base=base, eg_start=start, leaf_order=order)
+        return out
+
     def debugGetTree(self):
         """the linearised octree of the last build (pft_debug_get_tree): the header fields as ints (margin_cells, inv_res
         and ominf as float bits), lvl_start [depth + 2], words [n_words], leaf_order [n_crop], leaf_pts and crop_pts

@@ -636,9 +636,10 @@ def test_exact_nearest_sorted_and_per_query_paths_agree_bit_for_bit(gpu, data, m
 
 
 def test_exact_nearest_wide_particle_cloud_and_tiny_sizes(gpu, orc, data):
-    """(a) particles spread over half a metre: a tile of 32 particles then touches far more grid cells than the 8 192 entries
-    of the workgroup's LDS count table -- the cells that find their probe window full are counted and placed with global
-    atomics -- and most queries have no neighbour inside the gate; (b) one particle, one to three reference points"""
+    """(a) particles spread over half a metre: most queries have no neighbour inside the gate, and many cells' lists are
+    empty; (b) one particle, one to three reference points.  (Case (a) does NOT overflow the workgroup's LDS count table: a
+    tile holds ceil(P / compute units) particles, one at P = 96, whose 2 048 queries load a quarter of the 8 192 entries.
+    The probe-window-full route is proved by tests/test_gpu_exact_routes.py::test_window_full.)"""
     def pair(model, P):
         o = orc.Tracker(orc.default_config(particle_num=P, threads=0, emulate_pcl_alloc=0, exact_nearest=1, max_distance=0.1))
         g = gpu.ParticleFilterTracker(seed=1)
