@@ -631,6 +631,11 @@ int pft_debug_pack_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_
 int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a, const double* q,
                            const pft_particle* motion, uint32_t epoch, pft_particle* out, int32_t* bins6,
                            uint32_t* n_out, uint32_t* k_out);
+/* the same, and the launch also writes the 3x4 matrix of every candidate (the pose -> matrix step the kernel fuses, as
+ * under pft_compute): mats12 (required, room for maximum_particle_num matrices) receives those of the n_out particles */
+int pft_debug_kld_resample_mats(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a,
+                                const double* q, const pft_particle* motion, uint32_t epoch, pft_particle* out,
+                                int32_t* bins6, uint32_t* n_out, uint32_t* k_out, float* mats12);
 /* host-side KLDAdaptiveParticleFilterTracker::normalQuantile / calcKLBound (what the resample kernel is given) */
 double pft_kld_normal_quantile(double u);
 double pft_kld_bound(int k, double delta, double epsilon);

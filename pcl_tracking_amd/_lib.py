@@ -269,6 +269,7 @@ SYMBOLS = [
     ("pft_debug_pose_to_matrix", C.c_int, [_vp, _vp, _sz, _vp]),
     ("pft_debug_pack_reference", C.c_int, [_vp, _vp, _sz, _vp]),
     ("pft_debug_kld_resample", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _u32, _vp, _vp, _P(_u32), _P(_u32)]),
+    ("pft_debug_kld_resample_mats", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _u32, _vp, _vp, _P(_u32), _P(_u32), _vp]),
     ("pft_set_change_detector", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _f64]),
     ("pft_get_change_detector", C.c_int, [_vp, _P(C.c_int), _P(C.c_int), _P(C.c_int), _P(_f64)]),
     ("pft_debug_change_state", C.c_int, [_vp, C.c_int, _P(_u32), _P(_u32), _vp, _P(_i32), _vp, _P(_u32)]),

@@ -682,9 +682,11 @@ extern "C" int pft_debug_pack_reference(pft_tracker* t, const pft_point_xyzrgba*
   return PFT_OK;
 }
 
-extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a,
-                                      const double* q, const pft_particle* motion, uint32_t epoch, pft_particle* out,
-                                      int32_t* bins6, uint32_t* n_out, uint32_t* k_out) {
+// mats12 != null: the launch also writes the 3x4 matrix of every candidate (the pose -> matrix step the kernel fuses, as
+// in pft_compute); the first n_out of them are returned
+static int dbg_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a, const double* q,
+                            const pft_particle* motion, uint32_t epoch, pft_particle* out, int32_t* bins6,
+                            uint32_t* n_out, uint32_t* k_out, float* mats12) {
   if (!t || !old || !n_old || (!a) != (!q) || !motion || !out || !n_out) return PFT_ERR_INVALID_ARG;
   if (!t->prm.kld) return PFT_ERR_STATE;
   const uint32_t maxn = t->prm.kld_max;
@@ -700,8 +702,10 @@ extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, s
   DevBuf<pft_particle> d_old, d_out;  // (d_old, d_a, d_q stay null without a table)
   DevBuf<int32_t> d_a, d_bins;
   DevBuf<double> d_q;
+  DevBuf<float> d_mats;
   PFTT_GROW(t, d_out.alloc(maxn) && d_bins.alloc((size_t)6 * maxn));
   if (table) PFTT_GROW(t, d_old.alloc(n_old) && d_a.alloc(n_old) && d_q.alloc(n_old));
+  if (mats12) PFTT_GROW(t, d_mats.alloc((size_t)12 * maxn));
   PftHeader* h = new PftHeader();
   memset(h, 0, sizeof(*h));
   h->p_active = (uint32_t)n_old;
@@ -722,7 +726,7 @@ extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, s
     PftDev d = t->dev;
     d.part_all = table ? d_old.get() : b.part.get();
     d.hdr = t->d_dbg_hdr;
-    d.mats = nullptr;
+    d.mats = mats12 ? d_mats.get() : nullptr;
     if (!table) {
       d.gate = nullptr;  // (the ungated instance)
       d.alias_list = b.list;
@@ -738,10 +742,25 @@ extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, s
     if (k_out) *k_out = h->kld_k;
     e = hipMemcpy(out, d_out, (size_t)h->p_active * sizeof(pft_particle), hipMemcpyDeviceToHost);
     if (e == hipSuccess && bins6) e = hipMemcpy(bins6, d_bins, (size_t)h->p_active * 6 * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mats12) e = hipMemcpy(mats12, d_mats, (size_t)h->p_active * 12 * sizeof(float), hipMemcpyDeviceToHost);
   }
   delete h;
   PFT_HIPCHK(t, e);
   return PFT_OK;
+}
+
+extern "C" int pft_debug_kld_resample(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a,
+                                      const double* q, const pft_particle* motion, uint32_t epoch, pft_particle* out,
+                                      int32_t* bins6, uint32_t* n_out, uint32_t* k_out) {
+  return dbg_kld_resample(t, old, n_old, a, q, motion, epoch, out, bins6, n_out, k_out, nullptr);
+}
+
+extern "C" int pft_debug_kld_resample_mats(pft_tracker* t, const pft_particle* old, size_t n_old, const int32_t* a,
+                                           const double* q, const pft_particle* motion, uint32_t epoch,
+                                           pft_particle* out, int32_t* bins6, uint32_t* n_out, uint32_t* k_out,
+                                           float* mats12) {
+  if (!mats12) return PFT_ERR_INVALID_ARG;
+  return dbg_kld_resample(t, old, n_old, a, q, motion, epoch, out, bins6, n_out, k_out, mats12);
 }
 
 // ---- change detection: the hooks (the settings are in pft_api_features.hip) ----

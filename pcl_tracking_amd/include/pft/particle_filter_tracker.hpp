@@ -202,6 +202,9 @@ class ParticleFilterTracker {
   void setResampleLikelihoodThr(double v) { guard(); cfg_.resample_likelihood_thr = v; }
   void setUseNormal(bool b) { guard(); cfg_.use_normal = b ? 1 : 0; }
   void setAlpha(double a) { guard(); cfg_.alpha = a; }
+  // the share of new particles that take the motion step (PCL's ctor default 0.25; read by the KLD resample only)
+  void setMotionRatio(double r) { guard(); cfg_.motion_ratio = r; }
+  double getMotionRatio() const { return cfg_.motion_ratio; }
   void setMinIndices(int) {}  // read only when use_normal_ is true
   void setSeed(uint64_t s) { guard(); cfg_.seed = s; }      // PCL's engines are time(0)-seeded
   // PFT_SUM_TREE (default) or PFT_SUM_PCL: the order of normalizeWeight's and update()'s population sums (pft.h)

@@ -427,6 +427,14 @@ class ParticleFilterTracker:
         self._cfg_guard()
         self._cfg.alpha = float(a)
 
+    def setMotionRatio(self, r):
+        """the share of new particles that take the motion step (PCL's default 0.25; read by the KLD resample only)"""
+        self._cfg_guard()
+        self._cfg.motion_ratio = float(r)
+
+    def getMotionRatio(self):
+        return self._cfg.motion_ratio
+
     def setMinIndices(self, n):
         pass  # only read when use_normal_ is true (auto_tracking.cpp:676)
 
@@ -1157,9 +1165,10 @@ class KLDAdaptiveParticleFilterOMPTracker(ParticleFilterTracker):
         for i in range(6):
             self._cfg.kld_bin_size[i] = float(bin_size[i])
 
-    def debugKldResample(self, old, a, q, motion, epoch):
+    def debugKldResample(self, old, a, q, motion, epoch, want_mats=False):
         """test hook: the KLD resample alone, with an explicit alias table -> (particles, bins (n,6), k); a = q = None:
-        the product instance, on the prefix-sum form built from old's weights as given"""
+        the product instance, on the prefix-sum form built from old's weights as given.  want_mats: the launch also
+        writes the matrices, as under compute() -> (particles, bins, k, matrices (n, 3, 4))"""
         self._ensure()
         old = np.ascontiguousarray(old, PARTICLE_DTYPE)
         if (a is None) != (q is None):
@@ -1172,6 +1181,11 @@ class KLDAdaptiveParticleFilterOMPTracker(ParticleFilterTracker):
         out = np.zeros(cap, PARTICLE_DTYPE)
         bins = np.zeros((cap, 6), np.int32)
         n, k = C.c_uint32(), C.c_uint32()
+        if want_mats:
+            m = np.zeros((cap, 12), np.float32)
+            self._check(self._L.pft_debug_kld_resample_mats(self._h, _ptr(old), len(old), _ptr(a), _ptr(q), _ptr(motion),
+                                                            epoch, _ptr(out), _ptr(bins), C.byref(n), C.byref(k), _ptr(m)))
+            return out[:n.value].copy(), bins[:n.value].copy(), k.value, m[:n.value].reshape(n.value, 3, 4).copy()
         self._check(self._L.pft_debug_kld_resample(self._h, _ptr(old), len(old), _ptr(a), _ptr(q), _ptr(motion), epoch,
                                                    _ptr(out), _ptr(bins), C.byref(n), C.byref(k)))
         return out[:n.value].copy(), bins[:n.value].copy(), k.value
