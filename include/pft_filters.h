@@ -76,6 +76,64 @@ int pft_filter_get_pass_indices(pft_filter* f, int32_t* host_idx, size_t capacit
 /* GPU time of the last apply (HIP events on the handle's stream), milliseconds */
 int pft_filter_last_ms(const pft_filter* f, double* ms);
 
+/* ---- the depth entrance: a registered depth image + colour image instead of the 32-byte records ----
+ * The organised cloud is formed on the device (k_depth_deproject) in the handle's own input buffer and the pipeline above
+ * runs over it unchanged.  For W x H pixels, pixel (c, r) (column, row) becomes record i = r W + c; there are always W H
+ * records, so pft_filter_get_pass_indices lists pixel indices.  All arithmetic is IEEE float, unfused, every operation
+ * rounded once:
+ *     ifx = 1.0f / fx,  ify = 1.0f / fy                      (host, once per call)
+ *     lx = ((float)c - cx) * ifx,  ly = ((float)r - cy) * ify
+ *     PFT_DEPTH_U16: valid iff d != 0;                z = (float)d / depth_divisor   (correctly rounded division)
+ *     PFT_DEPTH_F32: valid iff d is finite and d > 0; z = d                           (metres)
+ *     valid:    {lx * z, ly * z, z, 1.0f}, rgba = 0xff000000 | r << 16 | g << 8 | b (an alpha byte in the image is ignored;
+ *               PFT_COLOR_NONE: 0xff000000), the 12 padding bytes zero
+ *     invalid:  x = y = z = the quiet NaN 0x7fc00000, data[3] = 1.0f, rgba = 0, padding zero
+ * Samples are in host byte order.  A row stride is in bytes; 0 = tightly packed, else >= width x bytes per pixel, any value
+ * (odd ones included); bytes between the end of a row and the next row never influence a result and the last row needs
+ * only its pixels.  1 <= width, height <= PFT_DEPTH_MAX_AXIS. */
+enum { PFT_DEPTH_U16 = 0, PFT_DEPTH_F32 = 1 };
+enum { PFT_COLOR_NONE = 0, PFT_COLOR_BGR8 = 1, PFT_COLOR_RGB8 = 2, PFT_COLOR_BGRA8 = 3, PFT_COLOR_RGBA8 = 4 };
+enum { PFT_DEPTH_MAX_AXIS = 16384, PFT_DEPTH_SLOTS = 2 };
+
+typedef struct pft_depth_frame {
+  uint32_t abi_version;          /* PFT_ABI_VERSION */
+  int32_t width, height;
+  float fx, fy, cx, cy;          /* fx, fy finite and > 0; cx, cy finite */
+  int32_t depth_format;          /* PFT_DEPTH_U16 | PFT_DEPTH_F32 */
+  float depth_divisor;           /* U16 only: finite, > 0 */
+  int32_t color_format;          /* PFT_COLOR_NONE | _BGR8 | _RGB8 | _BGRA8 | _RGBA8 */
+  uint32_t depth_stride, color_stride;
+} pft_depth_frame;
+
+/* Kinect2 qhd: 960 x 540, fx = fy = 540, cx = 479.5, cy = 269.5 (six times the default camera of pft_visibility.h);
+ * U16 / 1000 (millimetres); BGR8; packed */
+void pft_depth_frame_default(pft_depth_frame* d);
+
+/* Errors of the two applies: PFT_ERR_INVALID_ARG with a text that names the field (fx, fy, cx, cy, depth_divisor,
+ * depth_format, color_format, depth_stride, color_stride, width, height, depth, color: a null depth pointer, a colour
+ * pointer that is missing while a format is set); PFT_ERR_CAPACITY above PFT_DEPTH_MAX_AXIS.  An image without a valid
+ * pixel is no error: W H records, an empty output where PassThrough or VoxelGrid drop the NaN records.
+ * pft_filter_apply_depth waits for the counts, like pft_filter_apply.  pft_filter_apply_depth_async only enqueues: caller
+ * memory is borrowed until its upload is done, the one thing waited for, exactly like pft_filter_apply_async.  Depth and
+ * record applies may alternate on one handle in any order. */
+int pft_filter_apply_depth(pft_filter* f, const pft_depth_frame* d, const void* depth, const void* color);
+int pft_filter_apply_depth_async(pft_filter* f, const pft_depth_frame* d, const void* depth, const void* color);
+
+/* PFT_DEPTH_SLOTS slots of pinned host memory, each sized for the description (grown when a larger one is asked for, which
+ * waits for the slot's upload first; *color = NULL with PFT_COLOR_NONE).  An async apply whose depth pointer (and colour
+ * pointer, when a format is set) are a slot's waits for nothing: the slot is then busy until its upload has finished,
+ * which pft_filter_depth_slot_done reports (wait != 0: waits for it), and the caller writes to a slot only when it is
+ * done.  An apply from a slot that is still busy waits for that earlier upload before it enqueues its own. */
+int pft_filter_depth_host_buffers(pft_filter* f, const pft_depth_frame* d, int slot, void** depth, void** color);
+int pft_filter_depth_slot_done(pft_filter* f, int slot, int wait, int* done);
+
+/* the input cloud of the last apply where the handle owns it -- the organised cloud of a depth apply, the upload of a
+ * host record apply -- in HBM, valid until the next apply: what pft_segment_apply_device / pft_subtract_apply_device
+ * take.  Waits for a pending apply.  PFT_ERR_STATE before the first apply and after an apply of a device cloud (the handle
+ * does not own that cloud) */
+int pft_filter_input_device(const pft_filter* f, const pft_point_xyzrgba** device_points, size_t* n);
+int pft_filter_get_input(pft_filter* f, pft_point_xyzrgba* host_out, size_t capacity, size_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -169,6 +169,21 @@ class FilterConfig(C.Structure):
 VOXEL_NONE, VOXEL_APPROX, VOXEL_EXACT = 0, 1, 2
 
 
+class DepthFrame(C.Structure):
+    """pft_depth_frame (include/pft_filters.h): the two images of a depth apply and their pinhole camera, 48 bytes"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("depth_format", C.c_int32), ("depth_divisor", C.c_float), ("color_format", C.c_int32),
+        ("depth_stride", C.c_uint32), ("color_stride", C.c_uint32),
+    ]
+
+
+DEPTH_U16, DEPTH_F32 = 0, 1
+COLOR_NONE, COLOR_BGR8, COLOR_RGB8, COLOR_BGRA8, COLOR_RGBA8 = range(5)
+DEPTH_MAX_AXIS, DEPTH_SLOTS = 16384, 2
+
+
 class SegmentConfig(C.Structure):
     """pft_segment_config (include/pft_segment.h)"""
     _fields_ = [
@@ -315,6 +330,13 @@ SYMBOLS = [
     ("pft_filter_get_output", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_filter_get_pass_indices", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     ("pft_filter_last_ms", C.c_int, [_vp, _P(_f64)]),
+    ("pft_depth_frame_default", None, [_P(DepthFrame)]),
+    ("pft_filter_apply_depth", C.c_int, [_vp, _P(DepthFrame), _vp, _vp]),
+    ("pft_filter_apply_depth_async", C.c_int, [_vp, _P(DepthFrame), _vp, _vp]),
+    ("pft_filter_depth_host_buffers", C.c_int, [_vp, _P(DepthFrame), C.c_int, _P(_vp), _P(_vp)]),
+    ("pft_filter_depth_slot_done", C.c_int, [_vp, C.c_int, C.c_int, _P(C.c_int)]),
+    ("pft_filter_input_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
+    ("pft_filter_get_input", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
     # include/pft_segment.h
     ("pft_segment_default_config", None, [_P(SegmentConfig)]),
     ("pft_segment_create", C.c_int, [_P(SegmentConfig), _P(_vp)]),

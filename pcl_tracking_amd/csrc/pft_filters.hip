@@ -932,6 +932,8 @@ struct pft_filter {
   std::vector<PftBorrow*> borrows;  // trackers that read the output on the device (pft_internal.h)
   bool tile_pass_scanned = false;
   double last_ms = 0.0;
+  bool in_owned = false;  // the last apply's input lies in d_in_own (a host cloud's upload, a depth apply's cloud)
+  PftDepthState* depth = nullptr;  // the depth entrance's images and pinned slots (pft_depth.hip)
 };
 
 static void free_buffers(pft_filter* f) {
@@ -1062,6 +1064,7 @@ extern "C" void pft_filter_destroy(pft_filter* f) {
   }
   f->borrows.clear();
   free_buffers(f);
+  if (f->depth) pftd_destroy(f->depth);
   pft_dfree(f->d.bucket);
   pft_dfree(f->d.hdr);
   if (f->d.host_stat) hipHostFree(f->d.host_stat);
@@ -1171,6 +1174,7 @@ static int apply_common(pft_filter* f, const pft_point_xyzrgba* pts, size_t n, b
     f->last_ms = 0.0;
     f->have_result = true;
     f->applied = true;
+    f->in_owned = !on_device;
     return PFT_OK;
   }
   int r = ensure_capacity(f, n);
@@ -1182,6 +1186,7 @@ static int apply_common(pft_filter* f, const pft_point_xyzrgba* pts, size_t n, b
     PFT_HIPCHK(f, hipEventRecord(f->ev_copy, f->stream));
     d_in = f->d_in_own;
   }
+  f->in_owned = !on_device;
   r = run_pipeline(f, d_in, n);
   if (r != PFT_OK) return r;
   if (wait) return wait_pending(f);
@@ -1203,6 +1208,51 @@ extern "C" int pft_filter_apply_async(pft_filter* f, const pft_point_xyzrgba* ho
 
 extern "C" int pft_filter_apply_device_async(pft_filter* f, const pft_point_xyzrgba* device_points, size_t n) {
   return apply_common(f, device_points, n, true, false);
+}
+
+PftFilterAccess pftf_access(pft_filter* f) { return PftFilterAccess{f->stream, f->cfg.device_id, &f->depth, f->err}; }
+
+int pftf_begin_own_input(pft_filter* f, size_t n, pft_point_xyzrgba** d_in) {
+  if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
+  f->have_result = false;
+  f->pending = false;  // (a pending apply nobody asked about is superseded in stream order)
+  const int r = ensure_capacity(f, n);
+  if (r != PFT_OK) return r;
+  settle_borrows(f, false);  // the output is about to be overwritten
+  *d_in = f->d_in_own;
+  return PFT_OK;
+}
+
+int pftf_run_own_input(pft_filter* f, size_t n, bool wait) {
+  f->in_owned = true;
+  const int r = run_pipeline(f, f->d_in_own, n);
+  if (r != PFT_OK) return r;
+  return wait ? wait_pending(f) : PFT_OK;
+}
+
+extern "C" int pft_filter_input_device(const pft_filter* f, const pft_point_xyzrgba** device_points, size_t* n) {
+  if (!f || !device_points || !n) return PFT_ERR_INVALID_ARG;
+  if (!f->applied || !f->in_owned) return PFT_ERR_STATE;
+  const int r = wait_pending(f);
+  if (r != PFT_OK) return r;
+  *device_points = f->d_in_own;
+  *n = f->n_in;
+  return PFT_OK;
+}
+
+extern "C" int pft_filter_get_input(pft_filter* f, pft_point_xyzrgba* host_out, size_t capacity, size_t* n) {
+  if (!f || !n) return PFT_ERR_INVALID_ARG;
+  if (!f->applied || !f->in_owned) return PFT_ERR_STATE;
+  const int r = wait_pending(f);
+  if (r != PFT_OK) return r;
+  *n = f->n_in;
+  if (f->n_in > capacity) return PFT_ERR_CAPACITY;
+  if (f->n_in) {
+    if (!host_out) return PFT_ERR_INVALID_ARG;
+    PFT_HIPCHK(f, hipMemcpyAsync(host_out, f->d_in_own, f->n_in * sizeof(pft_point_xyzrgba), hipMemcpyDeviceToHost, f->stream));
+    PFT_HIPCHK(f, hipStreamSynchronize(f->stream));
+  }
+  return PFT_OK;
 }
 
 int pftf_view(pft_filter* f, PftFilterView* v) {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/pft.h"
@@ -289,6 +290,23 @@ struct PftFilterView {
 // pft_filters.hip: PFT_ERR_STATE before the first apply
 int pftf_view(pft_filter* f, PftFilterView* v);
 void pftf_attach(pft_filter* f, PftBorrow* b);
+// ---- the depth entrance of an input filter (pft_depth.hip; include/pft_filters.h) ----
+// The device copies of the two images and the pinned slots hang on the filter handle, which frees them with pftd_destroy
+// (its stream drained).  pft_depth.hip reaches the handle through these calls of pft_filters.hip only:
+struct PftDepthState;
+void pftd_destroy(PftDepthState* s);
+struct PftFilterAccess {
+  hipStream_t stream;
+  int device_id;
+  PftDepthState** depth;  // the handle's slot for the state (null until the first depth call)
+  std::string& err;      // the handle's error text: PFT_HIPCHK(&access, call) works as on a handle
+};
+PftFilterAccess pftf_access(pft_filter* f);
+// the front half of an apply over n > 0 records the caller is about to write into the handle's own input buffer: the
+// capacity, the borrowed outputs settled.  *d_in: that buffer
+int pftf_begin_own_input(pft_filter* f, size_t n, pft_point_xyzrgba** d_in);
+// the back half: the pipeline over the own input buffer, then the wait for the counts if asked for
+int pftf_run_own_input(pft_filter* f, size_t n, bool wait);
 
 // ---- model preparation (pft_model.hip) and its hand-off to a tracker (pft_set_object_from_model) ----
 // pft_segment.hip: removeZeroPoints (RULE zero, no transform) as the ordered compaction of the segmenter.  keep_idx[0 ..

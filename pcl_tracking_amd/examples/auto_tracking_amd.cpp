@@ -4,7 +4,7 @@
 // drawResult / viz_cb do with each pose (:300-326, :432-466).  The shared steps live in tracking_app.hpp.
 //
 //   auto_tracking_amd <model0> [<model1> ...] --frames <frame0> [<frame1> ...] [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]]
-//                     [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
+//                     [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
 //                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]]
 //                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]
 //                     [--visibility[=min_visible_ratio[,occlusion_margin]]]
@@ -57,19 +57,60 @@
 // object of which less than min_visible_ratio is visible is `Object occluded`, never `Object not recognized`, and
 // --reset-on-loss and --reacquire leave it alone; otherwise it is lost after lost_after frames in a row in which fewer than
 // min_ratio of its VISIBLE points were matched.
+// --depth-frames fx,fy,cx,cy[,divisor] (implies --raw): every --frames entry is a `depth.pgm:colour.ppm` pair -- a registered
+// 16-bit depth image (binary PGM, maxval 65535; divided by divisor, default 1000: millimetres) and an RGB image (binary PPM)
+// -- or a bare `depth.pgm` without colour, and the organised cloud is formed on the device (InputFilter::setInputDepth):
+// 5 bytes per pixel cross the bus instead of the 32-byte record.  The lines are those of the --raw flow.  With --async the
+// images go through the front end's two pinned slots, frame f + 1 read from its files while frame f is in flight; with
+// --segment the scene is such a pair too and is segmented where the front end formed it (pft_filter_input_device).
 // --reacquire-residual (with --reacquire): the segmentation that serves the lost objects runs on the frame minus the objects
 // that are not lost, so a lost object is never scored at the cluster of an object that is still tracked.
 #include <cstdlib>
 
+#include "pft/pnm_io.hpp"
 #include "segment_options.hpp"
 #include "tracking_app.hpp"
 
 using namespace app;
 
+// --depth-frames: one frame = `depth.pgm:colour.ppm` (binary PGM, maxval 65535 / binary PPM, maxval 255; pft/pnm_io.hpp), or
+// a bare `depth.pgm` without colour
+struct DepthFrameFiles {
+  pft::DepthImage depth;
+  pft::ColorImage color;
+  pft_depth_frame desc;
+  const void* colorData() const { return desc.color_format == PFT_COLOR_NONE ? nullptr : color.data.data(); }
+};
+static bool loadDepthFrame(const char* spec, const pft::DepthCamera& cam, float divisor, DepthFrameFiles& out) {
+  const std::string s(spec);
+  const size_t colon = s.find(':');
+  std::string err;
+  if (!pft::loadPgm16(s.substr(0, colon), out.depth, err)) {
+    std::fprintf(stderr, "%s\n", err.c_str());
+    return false;
+  }
+  const bool has_color = colon != std::string::npos;
+  if (has_color) {
+    if (!pft::loadPpm8(s.substr(colon + 1), out.color, err)) {
+      std::fprintf(stderr, "%s\n", err.c_str());
+      return false;
+    }
+    if (out.color.width != out.depth.width || out.color.height != out.depth.height) {
+      std::fprintf(stderr, "%s: the two images differ in size\n", spec);
+      return false;
+    }
+  }
+  out.desc = pft::InputFilter::depthFrame(out.depth.width, out.depth.height, cam, PFT_DEPTH_U16, divisor,
+                                          has_color ? PFT_COLOR_RGB8 : PFT_COLOR_NONE);
+  return true;
+}
+
 int main(int argc, char** argv) {
   std::vector<const char*> models, frames;
   Options opt;
-  bool raw = false, in_frames = false, async = false, device_models = false;
+  bool raw = false, in_frames = false, async = false, device_models = false, depth_frames = false;
+  pft::DepthCamera depth_cam;
+  float depth_divisor = 1000.0f;
   const char* segment_scene = nullptr;
   SegmentOptions so;
   for (int i = 1; i < argc; i++) {
@@ -80,6 +121,14 @@ int main(int argc, char** argv) {
       if (got < 0) return 2;
     }
     else if (!std::strcmp(argv[i], "--async")) async = true;
+    else if (!std::strcmp(argv[i], "--depth-frames") && i + 1 < argc) {
+      depth_frames = raw = true;  // --depth-frames fx,fy,cx,cy[,divisor]: the frames are image pairs, and sensor frames
+      const int got = std::sscanf(argv[++i], "%f,%f,%f,%f,%f", &depth_cam.fx, &depth_cam.fy, &depth_cam.cx, &depth_cam.cy, &depth_divisor);
+      if (got < 4) {
+        std::fprintf(stderr, "--depth-frames fx,fy,cx,cy[,divisor]\n");
+        return 2;
+      }
+    }
     else if (!std::strcmp(argv[i], "--kld")) opt.use_fixed = false;
     else if (!std::strcmp(argv[i], "--pcl-sums")) opt.pcl_sums = true;
     else if (!std::strcmp(argv[i], "--device-report")) opt.device_report = true;
@@ -195,7 +244,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -222,15 +271,29 @@ int main(int argc, char** argv) {
 
   TrackingApp v(opt);
   if (segment_scene) {  // model creation and model preparation in this process, the clusters never leaving HBM
-    Cloud::Ptr scene = loadCloud(segment_scene);
-    if (scene->points.empty()) {
+    Cloud::Ptr scene(new Cloud());
+    DepthFrameFiles scene_images;
+    if (depth_frames ? !loadDepthFrame(segment_scene, depth_cam, depth_divisor, scene_images)
+                     : (scene = loadCloud(segment_scene))->points.empty()) {
       std::fprintf(stderr, "no points in %s\n", segment_scene);
       return 1;
     }
     pft::ModelSegmenter seg;
     pft::VoxelGrid grid;  // its output cloud stays on the device for as long as the segmentation reads it
+    InputFilter scene_cloud;  // --depth-frames: forms the scene's organised cloud, which is segmented where it lies
     try {
-      segmentScene(so, scene, grid, seg);
+      if (depth_frames) {
+        scene_cloud.setPassThrough("z", 0.0f, 10.0f, false, false);
+        scene_cloud.setVoxelMode(PFT_VOXEL_NONE);
+        scene_cloud.setInputDepth(scene_images.desc, scene_images.depth.data.data(), scene_images.colorData());
+        scene_cloud.filterAsync();
+        const pft_point_xyzrgba* d_scene = nullptr;
+        size_t n_scene = 0;
+        scene_cloud.inputDevice(&d_scene, &n_scene);
+        segmentDeviceCloud(so, d_scene, n_scene, grid, seg);
+      } else {
+        segmentScene(so, scene, grid, seg);
+      }
       const std::vector<uint32_t> sizes = seg.clusterSizes();
       std::fprintf(stderr, "clusters %zu\n", sizes.size());
       if (sizes.empty()) return 1;
@@ -253,15 +316,49 @@ int main(int argc, char** argv) {
   }
 
   InputFilter front_end;  // filterPassThrough (z in [0, 10]) + gridSampleApprox (0.01), fused on the device
+  // --depth-frames --async: frame f is read into pinned slot f % 2 of the front end, frame f + 1 while frame f is in flight
+  pft_depth_frame slot_desc[PFT_DEPTH_SLOTS];
+  void* slot_depth[PFT_DEPTH_SLOTS] = {nullptr, nullptr};
+  void* slot_color[PFT_DEPTH_SLOTS] = {nullptr, nullptr};
+  size_t staged = (size_t)-1;
+  auto stageDepthFrame = [&](size_t f) {
+    if (staged == f) return true;
+    const int slot = (int)(f % PFT_DEPTH_SLOTS);
+    DepthFrameFiles files;
+    if (!loadDepthFrame(frames[f], depth_cam, depth_divisor, files)) return false;
+    front_end.depthSlotDone(slot, true);  // the slot's last upload has finished before it is written again
+    front_end.depthHostBuffers(slot, files.desc, &slot_depth[slot], &slot_color[slot]);
+    std::memcpy(slot_depth[slot], files.depth.data.data(), files.depth.data.size() * sizeof(uint16_t));
+    if (slot_color[slot]) std::memcpy(slot_color[slot], files.color.data.data(), files.color.data.size());
+    slot_desc[slot] = files.desc;
+    staged = f;
+    return true;
+  };
   for (size_t f = 0; f < frames.size(); f++) {
-    Cloud::Ptr cloud = loadCloud(frames[f]);
+    Cloud::Ptr cloud = depth_frames ? Cloud::Ptr(new Cloud()) : loadCloud(frames[f]);
+    DepthFrameFiles files;  // --depth-frames without --async: the images live here until the frame's filter call returned
     const pft_point_xyzrgba* d_cloud = nullptr;
     size_t n_down = 0;
-    if (async) {
-      front_end.setInputCloud(cloud);
-      front_end.filterAsync();
+    if (depth_frames) {  // the images instead of the cloud: staged in a pinned slot (--async), else borrowed for the call
+      try {
+        if (async) {
+          if (!stageDepthFrame(f)) return 1;
+          const int slot = (int)(f % PFT_DEPTH_SLOTS);
+          front_end.setInputDepth(slot_desc[slot], slot_depth[slot], slot_color[slot]);
+        } else {
+          if (!loadDepthFrame(frames[f], depth_cam, depth_divisor, files)) return 1;
+          front_end.setInputDepth(files.desc, files.depth.data.data(), files.colorData());
+        }
+      } catch (const std::exception& e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+      }
     } else if (raw) {
       front_end.setInputCloud(cloud);
+    }
+    if (async) {
+      front_end.filterAsync();
+    } else if (raw) {
       front_end.filterDevice(&d_cloud, &n_down);
       std::fprintf(stderr, "PointCloud before downsampled: %zu data points.\nPointCloud after downsampled: %zu data points.\n",
                    front_end.passedPoints(), n_down);  // auto_tracking.cpp:682, 684
@@ -285,6 +382,7 @@ int main(int argc, char** argv) {
       if (opt.visibility) kv.second->computeVisibility();  // behind the match: its pairs count the visible matched points
       if (opt.spread) kv.second->computeSpread();
     }
+    if (depth_frames && async && f + 1 < frames.size() && !stageDepthFrame(f + 1)) return 1;  // while this frame is in flight
     std::vector<int> lost;  // --reacquire: the objects the match reported lost in this frame
     bool any_lost = false;
     for (auto& kv : v.tracker_dict) {
@@ -317,6 +415,7 @@ int main(int argc, char** argv) {
           if (n_res) segmentDeviceCloud(so, d_res, n_res, frame_grid, frame_seg);
           else throw std::runtime_error("the tracked objects explain the whole frame");
         } else {
+          if (depth_frames) front_end.inputCloud(*cloud);  // the sensor frame the front end formed
           segmentScene(so, cloud, frame_grid, frame_seg);
         }
         v.reacquireLost(lost, frame_seg);

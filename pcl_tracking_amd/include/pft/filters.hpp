@@ -19,6 +19,11 @@
 
 namespace pft {
 
+// the pinhole camera of a depth frame; the defaults are pft_depth_frame_default's (Kinect2 qhd, 960 x 540)
+struct DepthCamera {
+  float fx = 540.0f, fy = 540.0f, cx = 479.5f, cy = 269.5f;
+};
+
 class InputFilter {
  public:
   explicit InputFilter(int device_id = 0, void* hip_stream = nullptr) {
@@ -59,12 +64,75 @@ class InputFilter {
   void setInputCloud(const PointCloud<PointXYZRGBA>::ConstPtr& cloud) {
     input_ = cloud;
     dev_in_ = nullptr;
+    depth_ = nullptr;
   }
   // a cloud already in HBM (n 32-byte points)
   void setInputCloudDevice(const pft_point_xyzrgba* device_points, size_t n) {
     input_.reset();
     dev_in_ = device_points;
     dev_n_ = n;
+    depth_ = nullptr;
+  }
+  // The frame as the sensor delivers it: a registered depth image and an optional colour image in host memory, described
+  // by a pft_depth_frame (include/pft_filters.h has the specification).  The organised cloud of width x height records is
+  // formed on the device; filter / filterDevice / filterAsync then work as on a cloud.  The images are borrowed until the
+  // filter call returns; pointers of depthHostBuffers make filterAsync wait for nothing
+  void setInputDepth(const pft_depth_frame& frame, const void* depth, const void* color) {
+    input_.reset();
+    dev_in_ = nullptr;
+    frame_ = frame;
+    depth_ = depth;
+    color_ = color;
+  }
+  // 16-bit depth (divided by depth_divisor) + packed colour, both tightly packed
+  void setInputDepth(const uint16_t* depth, const uint8_t* color, int width, int height, const DepthCamera& cam = DepthCamera(),
+                     float depth_divisor = 1000.0f, int color_format = PFT_COLOR_BGR8) {
+    setInputDepth(depthFrame(width, height, cam, PFT_DEPTH_U16, depth_divisor, color ? color_format : PFT_COLOR_NONE), depth, color);
+  }
+  static pft_depth_frame depthFrame(int width, int height, const DepthCamera& cam = DepthCamera(), int depth_format = PFT_DEPTH_U16,
+                                    float depth_divisor = 1000.0f, int color_format = PFT_COLOR_BGR8) {
+    pft_depth_frame d;
+    pft_depth_frame_default(&d);
+    d.width = width;
+    d.height = height;
+    d.fx = cam.fx;
+    d.fy = cam.fy;
+    d.cx = cam.cx;
+    d.cy = cam.cy;
+    d.depth_format = depth_format;
+    d.depth_divisor = depth_divisor;
+    d.color_format = color_format;
+    return d;
+  }
+  // pinned slot `slot` (0 or 1) of the handle, sized for `frame`: fill it, pass its pointers to setInputDepth, and write
+  // to it again only when depthSlotDone(slot) says its upload has finished.  The slots die with the handle (any set* call
+  // that changes the configuration)
+  void depthHostBuffers(int slot, const pft_depth_frame& frame, void** depth, void** color) {
+    if (!h_) check(pft_filter_create(&cfg_, &h_), "pft_filter_create");
+    check(pft_filter_depth_host_buffers(h_, &frame, slot, depth, color), "pft_filter_depth_host_buffers");
+  }
+  bool depthSlotDone(int slot, bool wait = false) {
+    if (!h_) return true;
+    int done = 0;
+    check(pft_filter_depth_slot_done(h_, slot, wait ? 1 : 0, &done), "pft_filter_depth_slot_done");
+    return done != 0;
+  }
+  // the input cloud of the last filter call where the handle owns it (the cloud a depth apply formed, the upload of a
+  // host cloud), in HBM, valid until the next filter call: what ModelSegmenter / SceneSubtraction take
+  void inputDevice(const pft_point_xyzrgba** device_points, size_t* n) {
+    if (!h_) throw std::runtime_error("inputDevice() before filter()");
+    check(pft_filter_input_device(h_, device_points, n), "pft_filter_input_device");
+  }
+  void inputCloud(PointCloud<PointXYZRGBA>& cloud) {
+    const pft_point_xyzrgba* p = nullptr;
+    size_t n = 0, got = 0;
+    inputDevice(&p, &n);
+    cloud.points.resize(n);
+    check(pft_filter_get_input(h_, cloud.points.data(), n, &got), "pft_filter_get_input");
+    const bool organised = depth_ && (size_t)frame_.width * (size_t)frame_.height == n;
+    cloud.width = organised ? (uint32_t)frame_.width : (uint32_t)n;
+    cloud.height = organised ? (uint32_t)frame_.height : 1;
+    cloud.is_dense = false;
   }
 
   // pcl::Filter::filter(PointCloud& output)
@@ -118,6 +186,9 @@ class InputFilter {
   PointCloud<PointXYZRGBA>::ConstPtr input_;
   const pft_point_xyzrgba* dev_in_ = nullptr;
   size_t dev_n_ = 0;
+  pft_depth_frame frame_ = {};
+  const void* depth_ = nullptr;
+  const void* color_ = nullptr;
 
   void check(int st, const char* what) {
     if (st != PFT_OK)
@@ -131,6 +202,8 @@ class InputFilter {
     else if (input_)
       check((wait ? pft_filter_apply : pft_filter_apply_async)(h_, input_->points.data(), input_->points.size()),
             "pft_filter_apply");
+    else if (depth_)
+      check((wait ? pft_filter_apply_depth : pft_filter_apply_depth_async)(h_, &frame_, depth_, color_), "pft_filter_apply_depth");
     else
       throw std::runtime_error("filter() without an input cloud");
   }

@@ -266,6 +266,44 @@ def make_depth_frame(width=960, height=540, seed=SCENE_SEED, obj_pose=GT_POSE, d
     return pts
 
 
+def make_depth_images(width=960, height=540, seed=SCENE_SEED, obj_pose=GT_POSE, dropout=0.03, return_points=False):
+    """The frame of make_depth_frame as the sensor delivers it (InputFilter.setInputDepth): (depth_u16, bgr, camera) with
+    depth [height, width] uint16 in millimetres rounded to nearest -- 0 where a ray hits nothing or the pixel drops out,
+    the far strip beyond 10 m kept --, bgr [height, width, 3] uint8 and camera = (fx, fy, cx, cy) of the ray cast.
+    The same scene, rays, dropout and noise draws as make_depth_frame.  return_points: also the unquantised float64
+    points [height * width, 3] the depths were rounded from (rows of invalid pixels are NaN)."""
+    rng = np.random.default_rng(seed)
+    boxes = _scene_boxes(obj_pose, rng)
+    far_rgb = np.tile(np.array([[90, 100, 120]]), (6, 1))
+    boxes[2] = _Box((1.0, 0.0, 2.5), (4.0, 4.0, 0.02), (0, 0, 0), boxes[2].face_rgb)
+    boxes.append(_Box((-3.0, 0.0, 12.0), (30.0, 9.0, 0.02), (0, 0, 0), far_rgb))
+    u, v = np.meshgrid(np.arange(width), np.arange(height), indexing="xy")
+    fx = 0.82 * width
+    cx, cy = (width - 1) / 2, (height - 1) / 2
+    d = np.stack([(u.ravel() - cx) / fx, (v.ravel() - cy) / fx, np.ones(u.size)], 1)
+    best_t = np.full(len(d), np.inf)
+    best_rgb = np.zeros((len(d), 3), np.int32)
+    for b in boxes:
+        t, face = b.intersect(d)
+        closer = t < best_t
+        best_t = np.where(closer, t, best_t)
+        best_rgb[closer] = b.face_rgb[face[closer]]
+    ok = np.isfinite(best_t) & (rng.random(len(d)) >= dropout)
+    t = np.where(ok, best_t, 1.0)
+    xyz = d * t[:, None]
+    xyz = xyz * (1.0 + rng.normal(0, 0.0015, len(xyz)) / np.maximum(xyz[:, 2], 0.1))[:, None]
+    rgb = np.clip(best_rgb + rng.integers(-8, 9, best_rgb.shape), 0, 255)
+    mm = np.rint(xyz[:, 2] * 1000.0)
+    ok &= (mm >= 1) & (mm <= 65535)
+    depth = np.where(ok, mm, 0).astype(np.uint16).reshape(height, width)
+    bgr = np.ascontiguousarray(rgb[:, ::-1].astype(np.uint8).reshape(height, width, 3))
+    camera = (float(fx), float(fx), float(cx), float(cy))
+    if return_points:
+        xyz[~ok] = np.nan
+        return depth, bgr, camera, xyz
+    return depth, bgr, camera
+
+
 def advance_pose(pose, frame):
     """ground-truth motion for multi-frame runs: +1 mm in x and +0.5 deg yaw per frame"""
     p = list(pose)

@@ -136,6 +136,11 @@ class ModelSegmenter:
         else:
             raise PftError(2, "apply() without an input cloud")
 
+    def applyDevice(self, device_ptr, n, keepalive=None):
+        """setInputCloudDevice + apply: applyDevice(*f.inputDevice()) runs over the cloud a filter's depth apply formed"""
+        self.setInputCloudDevice(device_ptr, n, keepalive)
+        self.apply()
+
     # -- results of the last apply --
     def planeCount(self):
         """planes the last apply removed"""
