@@ -124,8 +124,11 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
   const double wd = prm.dist_w, whsv = prm.hsv_w;
   const float hw = prm.h_w, sw = prm.s_w, vw = prm.v_w;
   for (uint32_t item_v = it_begin + lw; item_v < it_end;) {
-    // the work item is wave-uniform: said explicitly, so the particle's matrix is fetched with scalar loads and
-    // lives in SGPRs
+    // the work item is wave-uniform, said explicitly: the index arithmetic below is scalar.  The particle's matrix is
+    // nevertheless fetched with three vector loads and held in 12 VGPRs (the kernel stores and the matrices are not
+    // provably invariant, so the compiler selects no scalar load).  Handing the twelve floats over as scalars
+    // (v_readfirstlane) frees 8 VGPRs but the kernel is at its 80 SGPRs already: SGPR spills 75 -> 148, one v_readlane
+    // inside the round loop, and the launch is 3 % slower (profiles/leaf_phase.txt): not done.
     const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item_v);
     uint32_t pi, ch, cstart, clen;
     if (item < big_items) {
@@ -198,7 +201,9 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
           // Ancestor table: the fast descent's result is the deepest existing ancestor of the query's leaf cell at a level
           // <= lim, an integer fact about the tree: one 4-byte gather of the entry of the query's level-L cell (a query
           // outside the window reads entry 0 and does not use it; a query outside the box has key 0 and lim < 0: neither).
-          // (Issued right after the key, its live range pushed the kernel past 64 VGPRs into scratch.)
+          // (Issued right after the key, its live range used to push the kernel past 64 VGPRs into scratch.  Since the leaf
+          // scan carries its winner instead of fetching it again the early gather fits in 63 VGPRs, scratch 0 -- and gains
+          // nothing: 0.4684 ... 0.4703 against 0.4673 ... 0.4690 ms per frame, profiles/leaf_phase.txt.  It stays here.)
           bool inw = false;
           uint32_t ae = 0u;
           if (cx.anc) {  // (wave-uniform)
@@ -336,47 +341,36 @@ __device__ __forceinline__ void likelihood_items(const PftParams& prm, const Pft
         le = W[node + 1];
       }
       if (abl & 2) le = ls;
-      float bd = (abl & 2) ? 1.0e-3f : INFINITY;
-      uint32_t bpos = ls;
-      if (!INDIRECT) {
-        for (uint32_t pos = ls; pos < le; pos += 2) {  // two candidates per round: their gathers overlap
-          const bool two = pos + 1 < le;
-          const float4 c = d.leaf_pts[pos];
-          const float4 c2 = d.leaf_pts[two ? pos + 1 : pos];
-          float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
-          float dd = dx * dx + (dy * dy + dz * dz);
-          bool better = dd < bd;
-          bd = better ? dd : bd;
-          bpos = better ? pos : bpos;
-          dx = c2.x - qx; dy = c2.y - qy; dz = c2.z - qz;
-          dd = dx * dx + (dy * dy + dz * dz);
-          better = two & (dd < bd);
-          bd = better ? dd : bd;
-          bpos = better ? pos + 1 : bpos;
-        }
-      } else {
-        for (uint32_t pos = ls; pos < le; pos += 2) {
-          const bool two = pos + 1 < le;
-          const uint32_t i1 = d.leaf_order[pos], i2 = d.leaf_order[two ? pos + 1 : pos];
-          const float4 c = d.crop_pts[i1];
-          const float4 c2 = d.crop_pts[i2];
-          float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
-          float dd = dx * dx + (dy * dy + dz * dz);
-          bool better = dd < bd;
-          bd = better ? dd : bd;
-          bpos = better ? i1 : bpos;
-          dx = c2.x - qx; dy = c2.y - qy; dz = c2.z - qz;
-          dd = dx * dx + (dy * dy + dz * dz);
-          better = two & (dd < bd);
-          bd = better ? dd : bd;
-          bpos = better ? i2 : bpos;
-        }
-        // (no candidate beat +inf -- a NaN query --: bpos still holds the leaf position it started from; the direct path
-        // reports the leaf's first record then, and so does this one)
-        if (!(bd < INFINITY)) bpos = d.leaf_order[min(bpos, n_crop - 1u)];
+      // The leaf's first record (every leaf holds one: ls < le <= n_crop) is loaded once, whole, and is the provisional
+      // winner; the winner's record (position + packed colour) is carried through the loop in registers, bt, and the loop
+      // runs only in the lanes whose leaf holds more, one record per trip.  A leaf holds 1.27 records on the bench
+      // workload: most lanes issue this one gather.  (The scan used to take two records per trip, the second a duplicate
+      // load in a one-record leaf, and fetched the winner again behind the loop -- three gathers for one record: 161.4
+      // against 157.9 us per launch, profiles/leaf_phase.txt; the peel with two records per trip measured no gain.)
+      // bpos: the winner's position in leaf_pts, or (INDIRECT) its index in crop_pts; only DEBUG_NN reads it.
+      // A query for which no candidate beats +inf (a NaN query) keeps the first record and bd = +inf, in both forms.
+      // PFT_DIAG's abl & 2 (no candidates, bd = 1e-3): the coherence is still fed the leaf's first record.  One difference
+      // from the earlier code, in the INDIRECT form of that diagnostic only: it used the leaf POSITION ls as an index into
+      // crop_pts (some other record); now it is crop_pts[leaf_order[ls]], the leaf's own.  Timing ablation, results are
+      // wrong by design either way; the direct form is unchanged.
+      uint32_t bpos = INDIRECT ? d.leaf_order[ls] : ls;
+      float4 bt = INDIRECT ? d.crop_pts[bpos] : d.leaf_pts[ls];
+      float bd;
+      {
+        const float dx = bt.x - qx, dy = bt.y - qy, dz = bt.z - qz;
+        const float dd = dx * dx + (dy * dy + dz * dz);
+        bd = (abl & 2) ? 1.0e-3f : (dd < INFINITY ? dd : INFINITY);
       }
-      // the winner's record (position + packed colour) is fetched again instead of being carried through the loop
-      const float4 bt = INDIRECT ? d.crop_pts[bpos] : d.leaf_pts[bpos];
+      for (uint32_t pos = ls + 1u; pos < le; pos++) {
+        const uint32_t ci = INDIRECT ? d.leaf_order[pos] : pos;
+        const float4 c = INDIRECT ? d.crop_pts[ci] : d.leaf_pts[pos];
+        const float dx = c.x - qx, dy = c.y - qy, dz = c.z - qz;
+        const float dd = dx * dx + (dy * dy + dz * dz);
+        const bool better = dd < bd;
+        bd = better ? dd : bd;
+        bpos = better ? ci : bpos;
+        bt.x = better ? c.x : bt.x; bt.y = better ? c.y : bt.y; bt.z = better ? c.z : bt.z; bt.w = better ? c.w : bt.w;
+      }
       if (DEBUG_NN) {
         const size_t o = (size_t)pi * M + d.ref_perm[j];
         d.nn_idx[o] = INDIRECT ? (int32_t)bpos : (int32_t)d.leaf_order[bpos];
