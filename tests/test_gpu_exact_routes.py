@@ -7,7 +7,11 @@ of the DEBUG_NN instantiations) that its route was taken, so that a changed capa
 Bars, as everywhere for this mode (tests/test_gpu_parity.py): the crop bit-equal; inside the oracle's gate the neighbour's
 index and float squared distance bit-equal; outside the gate no neighbour; the raw weight within 1 ulp (a double sum in
 another order, rounded to float once); the cell-sorted and the per-query path the same bits; a tracked frame's pose within
-1e-4 of the oracle's."""
+1e-4 of the oracle's.
+
+The second part runs the same bars at grid cells other than 2 cm (exact_cases.RES_NAMES: octree resolutions from 1.1 mm to
+0.5 m, gates of 0.1 to 33 cells), among them the one route DESIGN.md section 7 names that the default resolution cannot
+reach: a query that attains the crop box's maximum and computes a cell one past the grid."""
 
 import numpy as np
 import pytest
@@ -36,13 +40,13 @@ def gpu():
     return tracker
 
 
-def coherence(gpu, gate):
+def coherence(gpu, gate, res=ec.RES):
     coh = gpu.NearestPairPointCloudCoherence()
     coh.addPointCoherence(gpu.DistanceCoherence())
     hc = gpu.HSVColorCoherence()
     hc.setWeight(0.1)
     coh.addPointCoherence(hc)
-    coh.setSearchMethod(gpu.OctreeSearch(ec.RES))
+    coh.setSearchMethod(gpu.OctreeSearch(res))
     coh.setMaximumDistance(gate)
     return coh
 
@@ -62,7 +66,7 @@ def make_gpu(gpu, monkeypatch, case, path, P=None, seed=1, kld=False, iterations
         g.setParticleNum(P)
     if iterations:
         g.setIterationNum(iterations)
-    g.setCloudCoherence(coherence(gpu, case["gate"]))
+    g.setCloudCoherence(coherence(gpu, case["gate"], case["res"]))
     g.setReferenceCloud(case["model"])
     g.setTrans(scene.initial_trans())
     g.setInputCloud(case["cloud"])  # (creates the handle)
@@ -408,6 +412,132 @@ def test_tracked_frames_on_a_kld_handle(gpu, orc, monkeypatch):
     assert S2["ec_pool_used"] <= S2["ec_pool_cap"] and not (S2["ec_count"] == NOLIST).any()
     for St in (S1, S2):
         assert_list_ranges(St)
+
+
+# ---- grid cells other than 2 cm ----
+def host_cells(case, mats, bbox):
+    """the cell of every query as exact_cases restates eg_query_cell, on the device's own matrices and box: (P, M), -1
+    outside the grid"""
+    p = case["particles"]
+    ref = ec.xyz_of(case["model"])
+    T = np.asarray(mats, np.float32).reshape(len(p), -1, 4)[:, :3, :]
+    q = ref[None, :, :]
+    # the device's xform in float32 (exact for the identity matrices of the top_query cases, which is where the count of
+    # queries outside the grid is asserted)
+    q = (T[:, None, :, 0] * q[..., 0:1] + T[:, None, :, 1] * q[..., 1:2] + T[:, None, :, 2] * q[..., 2:3]) + T[:, None, :, 3]
+    geo = ec.grid_geometry(bbox, case["res"])
+    return geo, ec.query_cell(geo, q.reshape(-1, 3).astype(np.float32)).reshape(len(p), -1)
+
+
+_res = {}
+
+
+def res_evaluate(gpu, orc, monkeypatch, name, path):
+    """a case of RES_NAMES on one path, once for all tests: -> (the device's matrices, [(G, S)] per evaluation), every
+    evaluation checked against the oracle.  The list paths evaluate twice on the handle (below: pool_may_be_short)"""
+    if (name, path) not in _res:
+        g, evs = evaluate(gpu, orc, monkeypatch, name, path, evaluations=1 if path == "shells" else 2)
+        np.testing.assert_array_equal(evs[0][0]["raw"], evs[-1][0]["raw"])
+        _res[name, path] = (g.debugPoseToMatrix(ec.build(name)["particles"]), evs)
+    return _res[name, path]
+
+
+def pool_may_be_short(S):
+    """A wave of k_ec_build takes a whole chunk of EC_CHUNK entries for the short lists it serves, and slot s goes to wave
+    s modulo the 8 x 4 waves per CU, so up to min(slots, waves) chunks are taken whatever the lists hold; lists above half
+    a chunk take their own length besides.  A pool at least that large holds every list: only where this upper limit
+    exceeds the pool may cells be left without a list (on a fresh handle: more than 2 048 cells hit), and the next
+    evaluation on the handle finds the pool grown to the demand."""
+    cnt = S["ec_count"][S["ec_count"] != NOLIST].astype(np.int64)
+    own = int(cnt[cnt > ec.EC_CHUNK // 2].sum()) if (S["ec_count"] != NOLIST).all() else ec.EC_POOL
+    return min(S["ec_nslots"], 8 * 4 * S["num_cus"]) * ec.EC_CHUNK + own > S["ec_pool_cap"]
+
+
+@pytest.mark.parametrize("path", ["sorted", "per_query", "shells"])
+@pytest.mark.parametrize("name", ec.RES_NAMES)
+def test_other_resolutions(gpu, orc, monkeypatch, name, path):
+    """every case of exact_cases.RES_NAMES on every search path against the oracle's exhaustive search (check()), the grid
+    the device built against the restated k_eg_setup, and the route each case exists for from the device's counters"""
+    case = ec.build(name)
+    mats, evs = res_evaluate(gpu, orc, monkeypatch, name, path)
+    for number, (G, S) in enumerate(evs):
+        assert_capacities_restated(S)
+        n = G["nn_idx"].size
+        geo, qcell = host_cells(case, mats, G["bbox"])
+        b = ec.search_bounds(geo, case["gate"])
+        outside = int((qcell < 0).sum())
+        short = path != "shells" and pool_may_be_short(S)
+        print("%s[%s] evaluation %d: eg_g %.9g, dim %s, %d cells, crop %d, slots %d, Kmax %d, R %d, outside %d / %d (host %d), "
+              "shell queries %d, pool %d of %d%s" % (
+                  name, path, number, S["eg_g"], S["eg_dim"].tolist(), S["eg_ncells"], S["n_crop"], S["ec_nslots"], b["Kmax"], b["R"],
+                  S["outside"], S["lik_outside"], outside, S["inline_shell"] + S["lik_shell"], S["ec_pool_used"], S["ec_pool_cap"],
+                  " (may be short: %d cells without a list)" % (S["ec_count"] == NOLIST).sum() if short else ""))
+        # the grid is the restated one, at the case's resolution
+        assert geo["g"] == np.float32(S["eg_g"]) and geo["dim"].tolist() == S["eg_dim"].tolist() and geo["ncells"] == S["eg_ncells"]
+        np.testing.assert_array_equal(geo["mn"], S["eg_min"])
+        assert S["n_crop"] == len(G["crop_idx"])
+        if name == "fine_cell_doubles":
+            assert geo["cells_at_resolution"] > ec.EG_CAP and np.float32(S["eg_g"]) == np.float32(0.0022) * np.float32(2.0)
+        else:
+            assert np.float32(S["eg_g"]) == np.float32(2.0 * case["res"])
+        if name.startswith("coarse_cell"):
+            assert S["eg_ncells"] == 1 and S["eg_dim"].tolist() == [1, 1, 1]
+        if name.startswith("fine_cell") and name != "fine_cell_doubles":
+            assert b["slabs"] > 64
+        # the queries outside the grid: as many as the host model counts, none in the cases that are not built for them
+        if name.startswith("top_query"):
+            ref = ec.xyz_of(case["model"])
+            np.testing.assert_array_equal(G["bbox"], np.stack([ref.min(0), ref.max(0)], 1).ravel())
+            assert outside >= len(case["particles"])
+        else:
+            assert outside == 0
+        if path == "sorted":
+            assert S["outside"] == outside and S["lik_outside"] == 0 and S["inline_shell"] >= outside
+        else:
+            assert S["lik_outside"] == outside and S["outside"] == 0 and S["lik_shell"] >= outside
+        assert_route_totals(S, "per_query" if path == "shells" else path, n)
+        if path == "shells":
+            assert S["ec_nslots"] == 0 and S["lik_shell"] == S["lik_queries"] == n
+            continue
+        # (a query within rounding of a cell face may be counted on the other side, except under the identity)
+        hit = len(np.unique(qcell[qcell >= 0]))
+        assert abs(S["ec_nslots"] - hit) <= (0 if name.startswith("top_query") else 8)
+        assert S["ec_nslots"] <= S["ec_slots_cap"]
+        assert_list_ranges(S)
+        # every cell has its list and only the queries outside the grid take the shell search: on the first evaluation
+        # wherever the fresh pool cannot be short, and on the second in every case
+        if not short or number == len(evs) - 1:
+            assert S["ec_pool_used"] <= S["ec_pool_cap"] and not (S["ec_count"] == NOLIST).any()
+            assert (S["inline_shell"] if path == "sorted" else S["lik_shell"]) == outside
+    if name == "fine_cell_far_slabs" and path != "shells":
+        # the lists that only the second round of segments can fill: one per site cell, none empty
+        G, S = evs[-1]
+        assert placed_lists(S).sum() >= 9
+    # the three paths: the same bytes (each of the other two against the cell-sorted one)
+    if path != "sorted":
+        G, G0 = evs[-1][0], res_evaluate(gpu, orc, monkeypatch, name, "sorted")[1][-1][0]
+        for k in ("raw", "nn_idx", "nn_d2", "crop_idx"):
+            assert G[k].tobytes() == G0[k].tobytes(), k
+
+
+@pytest.mark.parametrize("name", ["top_query_leaves_grid_g030", "odd_ratio_r037_gate030"])
+def test_tracked_frames_at_other_resolutions(gpu, orc, monkeypatch, name):
+    """compute() on the product (non-debug) kernels, two frames from the case's particles (setParticles: the first frame
+    weighs the identity particles of the top_query case as they are), the pose within 1e-4 of the oracle's"""
+    case = ec.build(name)
+    S1, S2 = compute_pair(gpu, orc, monkeypatch, name, 2)
+    for S in (S1, S2):
+        assert np.float32(S["eg_g"]) == np.float32(2.0 * case["res"])
+        assert not pool_may_be_short(S)  # (a few hundred cells hit: the fresh pool holds a chunk for each)
+        assert not (S["ec_count"] == NOLIST).any() and S["ec_nslots"] > 0
+        assert_list_ranges(S)
+    if name.startswith("top_query"):
+        # the first frame's box is the reference's own: the grid of the case, whose top queries leave it
+        ref = ec.xyz_of(case["model"])
+        geo = ec.grid_geometry(np.stack([ref.min(0), ref.max(0)], 1).ravel(), case["res"])
+        assert geo["dim"].tolist() == S1["eg_dim"].tolist() and (ec.query_cell(geo, ref) < 0).any()
+        # the cells hit are those of the queries inside the grid alone
+        assert S1["ec_nslots"] == len(np.unique(ec.query_cell(geo, ref)[ec.query_cell(geo, ref) >= 0]))
 
 
 def test_state_readback_refuses_other_handles(gpu):
