@@ -224,6 +224,26 @@ SUBTRACT_MAX_OBJECTS = 64
 SUBTRACT_MAX_MODEL_POINTS, SUBTRACT_MAX_FRAME_POINTS = 1 << 22, 1 << 26
 SUBTRACT_REFERENCE_CLOUD, SUBTRACT_REPORT_CLOUD = 0, 1
 
+class GrowConfig(C.Structure):
+    """pft_grow_config (include/pft_grow.h)"""
+    _fields_ = [("abi_version", C.c_uint32), ("device_id", C.c_int32), ("leaf", C.c_float), ("reach", C.c_int32),
+                ("confirm", C.c_int32), ("forget", C.c_int32), ("max_radius", C.c_float), ("max_voxels", C.c_uint32),
+                ("plane_margin", C.c_float)]
+
+
+class GrowStatsStruct(C.Structure):
+    """pft_grow_stats (include/pft_grow.h): the counts of one apply and the handle's state behind it, 80 bytes"""
+    _fields_ = [("applies", C.c_uint32), ("n_in", C.c_uint32), ("n_state", C.c_uint32 * 7),
+                ("n_candidate_voxels", C.c_uint32), ("n_added", C.c_uint32), ("n_model_points", C.c_uint32),
+                ("n_model_voxels", C.c_uint32), ("n_pending_live", C.c_uint32), ("occupied", C.c_uint32),
+                ("n_rebuilds", C.c_uint32), ("overflow", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+GROW_STATES = ("NONFINITE", "PLANE", "FAR", "KNOWN", "UNREACHED", "CANDIDATE", "ADDED")
+GROW_NONFINITE, GROW_PLANE, GROW_FAR, GROW_KNOWN, GROW_UNREACHED, GROW_CANDIDATE, GROW_ADDED = range(7)
+GROW_KIND_MODEL, GROW_KIND_PENDING = 1, 2
+GROW_MAX_PLANES = 4
+
 # every symbol include/*.h declare: (name, restype, argtypes)
 _vp, _sz, _i32, _u32, _u64, _f64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint64, C.c_double
 _P = C.POINTER
@@ -405,6 +425,23 @@ SYMBOLS = [
     ("pft_visibility", C.c_int, [_vp, _vp]),
     ("pft_get_visibility", C.c_int, [_vp, _P(VisibilityStatsStruct)]),
     ("pft_get_visibility_points", C.c_int, [_vp, _vp, _vp, _vp, _sz, _P(_sz)]),
+    # include/pft_grow.h
+    ("pft_grow_default_config", None, [_P(GrowConfig)]),
+    ("pft_grow_create", C.c_int, [_P(GrowConfig), _P(_vp)]),
+    ("pft_grow_destroy", None, [_vp]),
+    ("pft_grow_last_error_string", C.c_char_p, [_vp]),
+    ("pft_grow_set_model", C.c_int, [_vp, _vp, _sz]),
+    ("pft_grow_set_model_device", C.c_int, [_vp, _vp, _sz]),
+    ("pft_grow_set_planes", C.c_int, [_vp, _vp, _sz]),
+    ("pft_grow_apply", C.c_int, [_vp, _vp, _sz, _vp]),
+    ("pft_grow_apply_device", C.c_int, [_vp, _vp, _sz, _vp]),
+    ("pft_grow_get_stats", C.c_int, [_vp, _P(GrowStatsStruct)]),
+    ("pft_grow_get_states", C.c_int, [_vp, _vp, _sz]),
+    ("pft_grow_get_model", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_grow_model_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
+    ("pft_grow_get_transform", C.c_int, [_vp, _vp]),
+    ("pft_grow_last_ms", C.c_int, [_vp, _P(_f64)]),
+    ("pft_debug_grow_get_table", C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _P(_sz)]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

@@ -7,7 +7,7 @@
 //                     [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss]
 //                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]]
 //                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]
-//                     [--visibility[=min_visible_ratio[,occlusion_margin]]]
+//                     [--visibility[=min_visible_ratio[,occlusion_margin]]] [--grow-models[=confirm[,reach[,max_radius]]]]
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -51,6 +51,13 @@
 // prepares its objects, and is tracked from the next frame on: one `discover frame <f>: cluster <c> -> obj <j> (<n> points)`
 // line per new object, and with --match one `support obj <j> <n>` line per subtracted object (the frame points it holds).
 // A frame in which an object is lost discovers nothing: the lost object's own points are unexplained there.
+// --grow-models[=confirm[,reach[,max_radius]]] (with --discover; the defaults 3,2,0.5) folds surface that is seen next to a
+// tracked object's model into the model (pft::ModelGrowth): after the frame's subtraction, every subtracted object grows on
+// the RESIDUAL at its result pose, with the plane that --segment removed from the scene as the exclusion plane, and prints
+// one `grow obj <j>: candidates <n> added <n> model <n>` line.  A model that grew becomes its tracker's report cloud and is
+// what the subtraction takes from the next frame on, so a face that turns into view is not discovered as an object of its
+// own.  The tracker's REFERENCE cloud stays the one view it was given: a model with faces the camera cannot see has no
+// likelihood maximum at the true pose.
 // --visibility[=min_visible_ratio[,occlusion_margin]] enqueues the visibility of every model at its result pose behind the
 // match (pft_visibility: two depth images from the camera at the origin) and prints one `visibility obj <j> visible <n>/<M>
 // occluded <n> self <n> out <n>` line per object and frame.  With --match the occlusion-aware rule decides about a loss: an
@@ -219,6 +226,21 @@ int main(int argc, char** argv) {
         opt.discover_radius = radius;
       }
     }
+    else if (!std::strncmp(argv[i], "--grow-models", 13) && (argv[i][13] == 0 || argv[i][13] == '=')) {
+      opt.grow_models = true;  // --grow-models[=confirm[,reach[,max_radius]]]; the defaults 3,2,0.5
+      if (argv[i][13] == '=') {
+        int confirm = opt.grow_confirm, reach = opt.grow_reach;
+        double max_radius = opt.grow_max_radius;
+        const int got = std::sscanf(argv[i] + 14, "%d,%d,%lf", &confirm, &reach, &max_radius);
+        if (got < 1 || confirm < 1 || confirm > 255 || reach < 1 || reach > 4 || !(max_radius > 0.0) || !std::isfinite(max_radius)) {
+          std::fprintf(stderr, "--grow-models=confirm[,reach[,max_radius]] with 1 <= confirm <= 255, 1 <= reach <= 4 and max_radius > 0\n");
+          return 2;
+        }
+        opt.grow_confirm = confirm;
+        opt.grow_reach = reach;
+        opt.grow_max_radius = max_radius;
+      }
+    }
     else if (!std::strcmp(argv[i], "--reacquire-residual")) opt.reacquire_residual = true;
     else if (!std::strncmp(argv[i], "--visibility", 12) && (argv[i][12] == 0 || argv[i][12] == '=')) {
       opt.visibility = true;  // --visibility[=min_visible_ratio[,occlusion_margin]]; the defaults 0.25,0.03
@@ -244,7 +266,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--grow-models[=confirm[,reach[,max_radius]]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]]\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -264,12 +286,18 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "--reacquire-residual needs --reacquire: it is the re-acquisition's segmentation that runs on the residual\n");
     return 2;
   }
+  if (opt.grow_models && !opt.discover) {
+    std::fprintf(stderr, "--grow-models needs --discover: it is the residual of its subtraction that the models grow on\n");
+    return 2;
+  }
   if (async && !raw) {
     std::fprintf(stderr, "--async needs --raw: it is the front end that is not waited for\n");
     return 2;
   }
 
   TrackingApp v(opt);
+  float scene_plane[4] = {};  // --segment: the plane the model creation removed, --grow-models' exclusion plane
+  bool have_scene_plane = false;
   if (segment_scene) {  // model creation and model preparation in this process, the clusters never leaving HBM
     Cloud::Ptr scene(new Cloud());
     DepthFrameFiles scene_images;
@@ -293,6 +321,11 @@ int main(int argc, char** argv) {
         segmentDeviceCloud(so, d_scene, n_scene, grid, seg);
       } else {
         segmentScene(so, scene, grid, seg);
+      }
+      if (opt.grow_models && so.plane && !so.have_transform) {  // (a transformed scene's plane is not in the camera frame)
+        const pft_segment_plane pl = seg.plane();
+        have_scene_plane = pl.status == PFT_PLANE_FOUND;
+        std::memcpy(scene_plane, pl.coefficients, sizeof(scene_plane));
       }
       const std::vector<uint32_t> sizes = seg.clusterSizes();
       std::fprintf(stderr, "clusters %zu\n", sizes.size());
@@ -436,6 +469,7 @@ int main(int argc, char** argv) {
           const std::vector<uint32_t> support = sub.support();
           for (size_t k = 0; k < v.boundIds().size(); k++) std::printf("support obj %d %u\n", v.boundIds()[k], support[k]);
         }
+        if (opt.grow_models) v.growModels(sub, have_scene_plane ? scene_plane : nullptr);
         if (n_res) {
           pft::ModelSegmenter res_seg;
           pft::VoxelGrid res_grid;

@@ -32,6 +32,7 @@
 
 #include "pft/common.hpp"
 #include "pft/filters.hpp"
+#include "pft/model_growth.hpp"
 #include "pft/model_preparation.hpp"
 #include "pft/pcd_io.hpp"
 #include "pft/particle_filter_tracker.hpp"
@@ -79,6 +80,9 @@ struct Options {
   bool discover = false;                // --discover: clusters of the frame that no tracked object explains become objects
   int discover_every = 1;               // every n-th frame
   double discover_radius = 0.02;        // the subtraction's radius (also --reacquire-residual's)
+  bool grow_models = false;             // --grow-models: every bound object grows on the residual at its result pose
+  int grow_confirm = 3, grow_reach = 2;  // pft_grow_config::confirm / reach
+  double grow_max_radius = 0.5;         // pft_grow_config::max_radius
   bool reacquire_residual = false;      // --reacquire-residual: lost objects are looked for in the residual only
 };
 
@@ -392,7 +396,13 @@ class TrackingApp {
                      (int)PFT_SUBTRACT_MAX_OBJECTS, kv.first);
         break;
       }
-      subtraction_->bindTracker((int)bound_ids_.size(), *kv.second);
+      auto grown = grown_dict_.find(kv.first);
+      if (grown != grown_dict_.end()) {  // --grow-models: the grown model at the result pose, an explicit slot
+        const Affine3f pose = kv.second->toEigenMatrix(kv.second->getResult());
+        subtraction_->setObject((int)bound_ids_.size(), *grown->second, pose.m);
+      } else {
+        subtraction_->bindTracker((int)bound_ids_.size(), *kv.second);
+      }
       bound_ids_.push_back(kv.first);
     }
     if (d_frame) subtraction_->applyDevice(d_frame, d_n);
@@ -400,6 +410,35 @@ class TrackingApp {
     return *subtraction_;
   }
   const std::vector<int>& boundIds() const { return bound_ids_; }
+
+  // --grow-models: every object of the last subtractTracked() grows on its residual at its result pose (pft::ModelGrowth;
+  // `plane`: the scene's plane {a, b, c, d} in the camera frame, or null).  One line per object.  A model that grew becomes
+  // the tracker's report cloud and what subtractTracked() subtracts from then on; the REFERENCE cloud stays as it was
+  void growModels(pft::SceneSubtraction& sub, const float* plane) {
+    for (const int obj_id : bound_ids_) {
+      ParticleFilter& tr = *tracker_dict[obj_id];
+      std::shared_ptr<pft::ModelGrowth>& g = growth_dict_[obj_id];
+      if (!g) {
+        pft_grow_config cfg = pft::ModelGrowth::defaults();
+        cfg.confirm = opt_.grow_confirm;
+        cfg.reach = opt_.grow_reach;
+        cfg.max_radius = (float)opt_.grow_max_radius;
+        g.reset(new pft::ModelGrowth(cfg));
+        g->setModel(*referenceCloud(obj_id));
+        if (plane) g->setPlanes(plane, 1);
+      }
+      g->applyTracker(tr, sub);
+      const pft_grow_stats s = g->stats();
+      std::printf("grow obj %d: candidates %u added %u model %u\n", obj_id, s.n_state[PFT_GROW_CANDIDATE] + s.n_added, s.n_added,
+                  s.n_model_points);
+      if (!s.n_added) continue;
+      Cloud::Ptr grown(new Cloud());
+      g->model(*grown);
+      grown_dict_[obj_id] = grown;
+      reference_dict[obj_id] = grown;
+      tr.setReportCloud(grown);
+    }
+  }
 
   // --discover: the clusters of `seg` (a segmentation of the residual) become objects with the next free ids, prepared on
   // the device from where the clusters lie (the --segment path).  One line per new object
@@ -424,6 +463,8 @@ class TrackingApp {
   std::map<int, std::shared_ptr<pft::ModelPreparation>> model_dict_;  // the device-side models, one handle per object
   std::unique_ptr<pft::SceneSubtraction> subtraction_;                // created by the first subtractTracked()
   std::vector<int> bound_ids_;                                        // object of every slot of the last subtractTracked()
+  std::map<int, std::shared_ptr<pft::ModelGrowth>> growth_dict_;      // --grow-models: one handle per object
+  std::map<int, Cloud::Ptr> grown_dict_;                              // the objects whose model grew, and that model
 
   bool prepareOnDevice(pft::ModelSegmenter* seg) {
     for (auto& kv : tracker_dict)
