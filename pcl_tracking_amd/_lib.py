@@ -97,6 +97,19 @@ class VisibilityStatsStruct(C.Structure):
 VIS_VISIBLE, VIS_OCCLUDED, VIS_SELF_OCCLUDED, VIS_OUT_OF_VIEW = range(4)
 
 
+class ViewStatsStruct(C.Structure):
+    """pft_view_stats (include/pft_view.h): the counts of one view selection, 88 bytes"""
+    _fields_ = [
+        ("transform", C.c_float * 12),
+        ("n_model", C.c_uint32), ("n_state", C.c_uint32 * 5), ("n_visible", C.c_uint32), ("n_kept", C.c_uint32),
+        ("evaluated", C.c_uint32), ("calls", C.c_uint32),
+    ]
+
+
+VIEW_KEPT, VIEW_DECIMATED, VIEW_SELF_OCCLUDED, VIEW_OUT_OF_VIEW, VIEW_NONFINITE = range(5)
+VIEW_MAX_MODEL_POINTS = 1 << 22
+
+
 class ReacquireConfig(C.Structure):
     """pft_reacquire_config (include/pft.h): the orientation lattice, the inlier gate and the acceptance rule, 64 bytes"""
     _fields_ = [
@@ -442,6 +455,16 @@ SYMBOLS = [
     ("pft_grow_get_transform", C.c_int, [_vp, _vp]),
     ("pft_grow_last_ms", C.c_int, [_vp, _P(_f64)]),
     ("pft_debug_grow_get_table", C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _P(_sz)]),
+    # include/pft_view.h
+    ("pft_view_select", C.c_int, [_vp, _vp, _sz, _vp, _u32]),
+    ("pft_view_select_device", C.c_int, [_vp, _vp, _sz, _vp, _u32]),
+    ("pft_get_view", C.c_int, [_vp, _P(ViewStatsStruct)]),
+    ("pft_get_view_points", C.c_int, [_vp, _vp, _vp, _sz, _P(_sz)]),
+    ("pft_get_view_indices", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_get_view_cloud", C.c_int, [_vp, _vp, _sz, _P(_sz)]),
+    ("pft_view_cloud_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
+    ("pft_set_reference_from_view", C.c_int, [_vp, _u32]),
+    ("pft_debug_set_view_grid", C.c_int, [_vp, _u32]),
 ]
 
 # exported by the diagnostic variant library only (tools/build_variant.py diag -DPFT_DIAG): bound when present

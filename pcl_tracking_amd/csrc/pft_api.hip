@@ -585,6 +585,10 @@ int pftt_match_clear_streak(pft_tracker* t) {
 }
 
 extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n) {
+  return pftt_set_reference(t, pts, n, false);
+}
+
+int pftt_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, bool same_object) {
   if (!t || (!pts && n)) return PFT_ERR_INVALID_ARG;
   if (n > 0x7fffffffu) return PFT_ERR_CAPACITY;
   hipSetDevice(t->cfg.device_id);
@@ -693,7 +697,7 @@ extern "C" int pft_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, s
   t->tree_of_compute = false;  // the tree on the device was searched for another model
   t->match_n = 0;
   t->vis_n = 0;
-  {
+  if (!same_object) {
     const int r = pftt_match_clear_streak(t);  // a new object: the lost rule starts over
     if (r != PFT_OK) return r;
   }

@@ -22,6 +22,7 @@
 
 #include "../../include/pft.h"
 #include "../../include/pft_visibility.h"
+#include "../../include/pft_view.h"
 
 #define PFT_MAX_DEVICES 64      // per-device caches of one-time kernel attributes
 #define PFT_MAX_DEPTH 30
@@ -400,6 +401,32 @@ void pftk_visibility_clear(hipStream_t s, const PftVisBufs& b, uint32_t M);
 void pftk_visibility(hipStream_t s, const PftDev& d, uint32_t M, const float4* pts, uint32_t stride4, uint32_t N,
                      const uint32_t* n_dev, const PftVisCam& cam, const PftVisArgs& a, const PftVisBufs& b,
                      const pft_match_stats* match, const int32_t* match_idx, int num_cus);
+// the view-dependent reference (pft_view.hip)
+struct PftViewArgs {
+  float m[12];               // the explicit matrix (use_rep == 0)
+  uint32_t use_rep;          // T = pose_to_matrix(PftHeader::rep); a failed last iteration is then not evaluated
+  uint32_t K;                // max_points (0: no limit)
+};
+struct PftViewCtl {  // written by k_view_fill, read by the launches behind it
+  float T[12];
+  uint32_t run;              // 0: nothing is evaluated
+};
+struct PftViewBufs {
+  PftViewCtl* ctl;
+  uint32_t* zbuf;            // [W H] depth bits of the moved model
+  uint2* q;                  // [N] {bits of the moved z, pixel | 0xffffffff out of view | 0xfffffffe non-finite record}
+  uint8_t* state;            // [N]
+  float* gap;                // [N]
+  uint4* tile_cnt;           // [tiles of 256 records] {visible, self-occluded, out of view, non-finite}
+  uint32_t* tile_base;       // [tiles] visible records before the tile
+  uint32_t* kept_idx;        // [n_kept]
+  float4* cloud;             // [2 n_kept] the kept records
+  pft_view_stats* out;
+};
+// fill, project, classify, scan, compact over the N records at `model` (pairs of 16 bytes); grid: the workgroups of every
+// pass but the one-workgroup scan, 0 = sized from N and num_cus
+void pftk_view(hipStream_t s, const PftHeader* hdr, const float4* model, uint32_t N, const PftVisCam& cam,
+               const PftViewArgs& a, const PftViewBufs& b, uint32_t grid, int num_cus);
 // re-acquisition (pft_reacquire.hip): the orientation lattice, the per-candidate score arrays (K each, owned by the feature)
 struct PftRqLattice {
   uint32_t n[3];             // roll, pitch, yaw steps (>= 1)

@@ -3,6 +3,7 @@
 //   pft_frame.hip         the stages of a frame, pft_compute with its graph capture, the pft_dist_* phases
 //   pft_api_debug.hip     pft_eval_weights, the pft_debug_* hooks, the state checkpoint
 //   pft_api_features.hip  change-detector settings, report, match, spread, visibility, re-acquisition, refinement
+//   pft_view.hip          the view-dependent reference: its kernels and its part of the C ABI (include/pft_view.h)
 // Internal: nothing outside csrc/ includes this.
 //
 // Device memory: every buffer the handle owns is a DevBuf (pft_devbuf.h), so deleting the handle frees it and no list of
@@ -191,6 +192,22 @@ struct pft_tracker {
   bool vis_issued = false;           // a pft_visibility has been enqueued: d_vis holds (or will hold) its result
   bool match_of_compute = false;     // a pft_match has been enqueued since the last pft_compute
 
+  // the view-dependent reference (pft_view_select): the result block, the depth image (sized for the largest camera used),
+  // the copy of a host model, and the per-record group that grows with the model
+  DevBuf<pft_view_stats> d_view;
+  DevBuf<PftViewCtl> d_view_ctl;
+  DevBuf<uint32_t> d_view_z;
+  DevBuf<pft_point_xyzrgba> d_view_model;
+  DevBuf<uint2> d_view_q;
+  DevBuf<uint8_t> d_view_state;
+  DevBuf<float> d_view_gap;
+  DevBuf<uint4> d_view_tile;
+  DevBuf<uint32_t> d_view_base, d_view_idx;
+  DevBuf<pft_point_xyzrgba> d_view_cloud;  // (allocated last of the group: its cap() is the records all have room for)
+  uint32_t view_grid = 0;            // test hook (pft_debug_set_view_grid): workgroups of every pass, 0 = sized from the model
+  bool view_issued = false;          // a select has been enqueued: d_view holds (or will hold) its result
+  bool view_fresh = false;           // ... and pft_set_reference_from_view has not consumed it
+
   // re-acquisition (pft_reacquire): buffers of the feature's own, sized for the largest K seen (never the handle's
   // particle_num-sized ones): candidates, their matrices, the scores, the partial boxes of k_aabb, the result block
   DevBuf<pft_particle> d_rq_part;
@@ -275,6 +292,8 @@ struct ProfScope {
 void pftt_sync_dev(pft_tracker* t);            // the one place that forms PftDev from the handle
 int pftt_check_device_error(pft_tracker* t);   // after the stream has drained: PftHeader::error as a status
 int pftt_match_clear_streak(pft_tracker* t);
+// pft_set_reference; same_object (pft_set_reference_from_view): the streaks and flags of the three rules are kept
+int pftt_set_reference(pft_tracker* t, const pft_point_xyzrgba* pts, size_t n, bool same_object);
 void pftt_cd_free(CdInst& c);
 int pftt_cd_reserve(pft_tracker* t, CdInst& c, uint32_t cap, bool debug);
 // pft_frame.hip

@@ -16,36 +16,14 @@
 // Depths are the uint32 bit patterns of positive floats (z > z_near >= 0): order-preserving, +inf = 0x7f800000, updated
 // with atomicMin.  Only these integer atomics and the kernel boundaries cross workgroups; no loop waits on anything.
 #include "pft_device_utils.h"
+#include "pft_vis_project.h"  // the projection and the splat, shared with pft_view.hip
 #include "../../include/pft_visibility.h"
 
 #define VS_THREADS 1024
 #define VS_WAVES (VS_THREADS / 64)
-#define VS_INF_BITS 0x7f800000u
-#define VS_NO_PIXEL 0xffffffffu
-
-// the projection of include/pft_visibility.h, shared by the kernels and pft_visibility_project
-__host__ __device__ __forceinline__ bool vis_project(const PftVisCam& c, float x, float y, float z, int& u, int& v) {
-  const bool front = z > c.z_near;
-  const float xn = x / z, yn = y / z;
-  const float uf = c.fx * xn + c.cx, vf = c.fy * yn + c.cy;
-  const bool in_view = front && uf >= 0.0f && uf < (float)c.W && vf >= 0.0f && vf < (float)c.H;
-  if (!in_view) return false;
-  u = (int)floorf(uf);
-  v = (int)floorf(vf);
-  return true;
-}
 
 __global__ void __launch_bounds__(256) k_vis_fill(uint32_t* __restrict__ z, uint32_t n) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) z[i] = VS_INF_BITS;
-}
-
-// min over the pixels [ua, ub] x [va, vb] (inside the image) of the image with zb
-__device__ __forceinline__ void vis_splat(uint32_t* __restrict__ img, int W, int ua, int ub, int va, int vb, uint32_t zb) {
-  for (int y = va; y <= vb; y++) {
-    uint32_t* row = img + (size_t)y * (size_t)W;
-    for (int x = ua; x <= ub; x++)
-      if (row[x] > zb) atomicMin(row + x, zb);  // (values only fall during a call: a stale read costs one atomic, no more)
-  }
 }
 
 struct VsModelSh {

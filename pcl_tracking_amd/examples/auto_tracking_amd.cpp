@@ -8,6 +8,7 @@
 //                     [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]]
 //                     [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--reacquire-residual]
 //                     [--visibility[=min_visible_ratio[,occlusion_margin]]] [--grow-models[=confirm[,reach[,max_radius]]]]
+//                     [--view-reference[=angle[,min_points[,max_points]]]] [--view-model FILE]...
 //   auto_tracking_amd --segment <scene> [model-creation flags] --frames <frame0> [<frame1> ...] [the flags above]
 //   (one model only: `auto_tracking_amd <model> <frame0> [frame1 ...]` also works)
 //
@@ -64,6 +65,14 @@
 // object of which less than min_visible_ratio is visible is `Object occluded`, never `Object not recognized`, and
 // --reset-on-loss and --reacquire leave it alone; otherwise it is lost after lost_after frames in a row in which fewer than
 // min_ratio of its VISIBLE points were matched.
+// --view-reference[=angle[,min_points[,max_points]]] (default angle 0.2 rad) lets the reference cloud follow the side of a
+// full-surface model that the camera sees (pft_view_select / pft_set_reference_from_view): after a frame's result, once the
+// result has turned more than `angle` away from the pose of the object's last selection -- the first result always selects
+// --, the visible points of the model at the result pose, at most max_points of them, become the reference cloud.  The full
+// model is the grown one under --grow-models, else --view-model FILE, one per object in object order, in the coordinates of
+// that object's model file (it is moved by the same re-centring transform).  One `view obj <j> frame <f>: model <n> visible
+// <n> kept <n>` line per selection; a selection that keeps fewer than min_points is refused with its text on stderr and the
+// tracking goes on with the old reference.
 // --depth-frames fx,fy,cx,cy[,divisor] (implies --raw): every --frames entry is a `depth.pgm:colour.ppm` pair -- a registered
 // 16-bit depth image (binary PGM, maxval 65535; divided by divisor, default 1000: millimetres) and an RGB image (binary PPM)
 // -- or a bare `depth.pgm` without colour, and the organised cloud is formed on the device (InputFilter::setInputDepth):
@@ -113,7 +122,7 @@ static bool loadDepthFrame(const char* spec, const pft::DepthCamera& cam, float 
 }
 
 int main(int argc, char** argv) {
-  std::vector<const char*> models, frames;
+  std::vector<const char*> models, frames, view_models;
   Options opt;
   bool raw = false, in_frames = false, async = false, device_models = false, depth_frames = false;
   pft::DepthCamera depth_cam;
@@ -255,6 +264,22 @@ int main(int argc, char** argv) {
         opt.vis_occlusion_margin = margin;
       }
     }
+    else if (!std::strncmp(argv[i], "--view-reference", 16) && (argv[i][16] == 0 || argv[i][16] == '=')) {
+      opt.view_reference = true;  // --view-reference[=angle[,min_points[,max_points]]]; the defaults 0.2,1,0
+      if (argv[i][16] == '=') {
+        double angle = opt.view_angle;
+        unsigned min_points = opt.view_min_points, max_points = opt.view_max_points;
+        const int got = std::sscanf(argv[i] + 17, "%lf,%u,%u", &angle, &min_points, &max_points);
+        if (got < 1 || !(angle >= 0.0) || !std::isfinite(angle)) {
+          std::fprintf(stderr, "--view-reference=angle[,min_points[,max_points]] with angle >= 0\n");
+          return 2;
+        }
+        opt.view_angle = angle;
+        opt.view_min_points = min_points;
+        opt.view_max_points = max_points;
+      }
+    }
+    else if (!std::strcmp(argv[i], "--view-model") && i + 1 < argc) view_models.push_back(argv[++i]);
     else if (!std::strcmp(argv[i], "--frames")) in_frames = true;
     else if (!std::strcmp(argv[i], "--model-leaf") && i + 1 < argc) opt.downsampling_grid_size = std::atof(argv[++i]);
     else if (!std::strcmp(argv[i], "--particles") && i + 1 < argc) opt.particles = std::atoi(argv[++i]);
@@ -266,7 +291,7 @@ int main(int argc, char** argv) {
     models.resize(1);
   }
   if (segment_scene ? !models.empty() || frames.empty() : models.empty() || frames.empty()) {
-    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--grow-models[=confirm[,reach[,max_radius]]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]]\n"
+    std::fprintf(stderr, "usage: %s <model>... --frames <frame>... [--particles N] [--seed S] [--raw] [--kld] [--pcl-sums] [--change-detector[=interval,min_points,resolution]] [--model-leaf L] [--device-report] [--async] [--depth-frames fx,fy,cx,cy[,divisor]] [--device-models] [--match[=min_ratio[,lost_after]]] [--reset-on-loss] [--reacquire[=n_yaw[,accept_ratio[,inlier_distance]]]] [--refine[=max_iterations[,pair_distance]]] [--spread[=max_pos_sigma[,min_n_eff[,after]]]] [--discover[=every[,radius]]] [--grow-models[=confirm[,reach[,max_radius]]]] [--reacquire-residual] [--visibility[=min_visible_ratio[,occlusion_margin]]] [--view-reference[=angle[,min_points[,max_points]]]] [--view-model FILE]...\n"
                          "       %s --segment <scene> " APP_SEGMENT_USAGE_1 " " APP_SEGMENT_USAGE_2 " --frames <frame>... [the flags above]\n", argv[0], argv[0]);
     return 2;
   }
@@ -292,6 +317,10 @@ int main(int argc, char** argv) {
   }
   if (async && !raw) {
     std::fprintf(stderr, "--async needs --raw: it is the front end that is not waited for\n");
+    return 2;
+  }
+  if (opt.view_reference ? !opt.grow_models && view_models.empty() : !view_models.empty()) {
+    std::fprintf(stderr, "--view-reference takes the full models from --grow-models or from one --view-model FILE per object, and --view-model needs --view-reference\n");
     return 2;
   }
 
@@ -344,6 +373,14 @@ int main(int argc, char** argv) {
       if (!(device_models ? v.setObjectsToTrackOnDevice() : v.setObjectsToTrack())) return 1;
     } catch (const std::exception& e) {
       std::fprintf(stderr, "%s\n", e.what());
+      return 1;
+    }
+  }
+
+  for (size_t k = 0; k < view_models.size() && !opt.grow_models; k++) {  // --view-model: object k's full-surface model
+    const Cloud::Ptr full = loadCloud(view_models[k]);
+    if (!v.setViewModel((int)k, *full)) {
+      std::fprintf(stderr, "--view-model %s: no points, or no object %zu\n", view_models[k], k);
       return 1;
     }
   }
@@ -418,8 +455,10 @@ int main(int argc, char** argv) {
     if (depth_frames && async && f + 1 < frames.size() && !stageDepthFrame(f + 1)) return 1;  // while this frame is in flight
     std::vector<int> lost;  // --reacquire: the objects the match reported lost in this frame
     bool any_lost = false;
+    std::map<int, ParticleT> results;  // --view-reference: the poses the reference clouds follow, once the frame is done
     for (auto& kv : v.tracker_dict) {
       const ParticleT result = kv.second->getResult();
+      if (opt.view_reference) results[kv.first] = result;
       if (opt.spread) v.reportSpread(kv.first);
       if (opt.visibility) v.reportVisibility(kv.first);
       if (opt.match && v.reportMatch(f + 1, kv.first, !opt.reacquire)) {
@@ -480,6 +519,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "discover: %s\n", e.what());
       }
     }
+    for (const auto& kv : results) v.updateViewReference(f + 1, kv.first, kv.second);  // (behind the frame's growth)
     if (async)  // the counts, now that the frame's results are on the host
       std::fprintf(stderr, "PointCloud before downsampled: %zu data points.\nPointCloud after downsampled: %zu data points.\n",
                    front_end.passedPoints(), front_end.outputPoints());

@@ -84,6 +84,9 @@ struct Options {
   int grow_confirm = 3, grow_reach = 2;  // pft_grow_config::confirm / reach
   double grow_max_radius = 0.5;         // pft_grow_config::max_radius
   bool reacquire_residual = false;      // --reacquire-residual: lost objects are looked for in the residual only
+  bool view_reference = false;          // --view-reference: the reference cloud follows the visible side of a full model
+  double view_angle = 0.2;              // re-selected once the result has turned this far (rad) from the last selection
+  unsigned view_min_points = 1, view_max_points = 0;  // setReferenceFromView's floor, selectView's limit (0: none)
 };
 
 // *.pcd = PCD v0.7 with fields x y z rgba (create_model.cpp:219-222 writes them, :741 once loaded them);
@@ -231,6 +234,7 @@ class TrackingApp {
                    ref_cloud->points.size(), nonzero_ref->points.size(), transed_ref_downsampled->points.size());
       kv.second->setReferenceCloud(transed_ref_downsampled);
       kv.second->setTrans(trans);
+      recentre_dict_[obj_id] = trans;
       reference_dict[obj_id] = transed_ref;
       if (opt_.device_report) kv.second->setReportCloud(transed_ref);
       kv.second->setMinIndices((int)ref_cloud->points.size() / 2);
@@ -440,6 +444,46 @@ class TrackingApp {
     }
   }
 
+  // --view-model: an object's full-surface model, in the coordinates of its model file; it is moved by the re-centring
+  // transform the object's model got.  False for an empty cloud or an unknown object
+  bool setViewModel(int obj_id, const Cloud& full) {
+    auto rc = recentre_dict_.find(obj_id);
+    Cloud::Ptr nonzero(new Cloud()), moved(new Cloud());
+    removeZeroPoints(full, *nonzero);
+    if (rc == recentre_dict_.end() || nonzero->empty()) return false;
+    transformPointCloud(*nonzero, *moved, inverseOfTranslation(rc->second));
+    view_model_dict_[obj_id] = moved;
+    return true;
+  }
+
+  // --view-reference, after a frame's result: once the result has turned more than view_angle away from the pose of the
+  // object's last selection (the first result always selects), the visible side of the object's full model at the result
+  // pose -- the grown model under --grow-models, else its --view-model -- becomes the reference cloud.  One line per
+  // selection; a refusal prints its text and the tracking goes on with the old reference
+  void updateViewReference(size_t frame, int obj_id, const ParticleT& result) {
+    ParticleFilter& tr = *tracker_dict[obj_id];
+    const Affine3f now = tr.toEigenMatrix(result);
+    auto last = view_pose_dict_.find(obj_id);
+    if (last != view_pose_dict_.end()) {
+      double trace = 0.0;  // of R_last^T R_now
+      for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) trace += (double)last->second(r, c) * (double)now(r, c);
+      const double cosine = std::min(1.0, std::max(-1.0, (trace - 1.0) / 2.0));
+      if (!(std::acos(cosine) > opt_.view_angle)) return;
+    }
+    int st = PFT_ERR_STATE;
+    auto g = growth_dict_.find(obj_id);
+    auto m = view_model_dict_.find(obj_id);
+    if (opt_.grow_models && g != growth_dict_.end() && g->second) st = tr.selectView(*g->second, nullptr, opt_.view_max_points);
+    else if (!opt_.grow_models && m != view_model_dict_.end()) st = tr.selectView(*m->second, nullptr, opt_.view_max_points);
+    else return;  // no full model (yet)
+    if (st != PFT_OK) return;
+    const pft_view_stats v = tr.getView();
+    if (!v.evaluated) return;
+    std::printf("view obj %d frame %zu: model %u visible %u kept %u\n", obj_id, frame, v.n_model, v.n_visible, v.n_kept);
+    if (tr.setReferenceFromView(opt_.view_min_points) == PFT_OK) view_pose_dict_[obj_id] = now;
+  }
+
   // --discover: the clusters of `seg` (a segmentation of the residual) become objects with the next free ids, prepared on
   // the device from where the clusters lie (the --segment path).  One line per new object
   template <class F>
@@ -465,6 +509,9 @@ class TrackingApp {
   std::vector<int> bound_ids_;                                        // object of every slot of the last subtractTracked()
   std::map<int, std::shared_ptr<pft::ModelGrowth>> growth_dict_;      // --grow-models: one handle per object
   std::map<int, Cloud::Ptr> grown_dict_;                              // the objects whose model grew, and that model
+  std::map<int, Affine3f> recentre_dict_;                             // the re-centring translation of every object's model
+  std::map<int, Cloud::Ptr> view_model_dict_;                         // --view-model: the full model, re-centred
+  std::map<int, Affine3f> view_pose_dict_;                            // --view-reference: the pose of the last selection
 
   bool prepareOnDevice(pft::ModelSegmenter* seg) {
     for (auto& kv : tracker_dict)
@@ -486,6 +533,7 @@ class TrackingApp {
                    mp->inputPoints(), mp->nonzeroPoints(), mp->referencePoints());
       if (tracker.setObjectFromModel(*mp, opt_.device_report) != PFT_OK) return false;
       model_dict_[obj_id] = mp;
+      recentre_dict_[obj_id] = mp->getTrans();
       reference_dict.erase(obj_id);
       tracker.setMinIndices((int)mp->inputPoints() / 2);
     }

@@ -24,6 +24,7 @@
 
 #include "pft.h"
 #include "pft_visibility.h"
+#include "pft_view.h"
 
 namespace pft {
 
@@ -513,6 +514,77 @@ class ParticleFilterTracker {
   }
   bool isOccluded() const { return handle_ && getVisibility().hidden != 0; }
   bool isLostVisible() const { return handle_ && getVisibility().lost != 0; }
+
+  // ---- the view-dependent reference (pft_view.h): a full model's visible side as the reference cloud ----
+  // enqueues the selection of the records of `model` that the visibility camera sees at m12 (row-major 3x4; nullptr: the
+  // last result pose) on the tracker's stream; nothing waits.  max_points: 0 = no limit
+  int selectView(const PointCloudIn& model, const float* m12 = nullptr, uint32_t max_points = 0) {
+    if (m12 ? !ensure() : !handle_) return check(m12 ? PFT_ERR_NO_DEVICE : PFT_ERR_STATE, "selectView");
+    return check(pft_view_select(handle_, model.points.data(), model.points.size(), m12, max_points), "selectView");
+  }
+  // ... of n records in this device's HBM (16-byte aligned), written in the order of the tracker's stream or before
+  int selectView(const pft_point_xyzrgba* device_points, size_t n, const float* m12 = nullptr, uint32_t max_points = 0) {
+    if (m12 ? !ensure() : !handle_) return check(m12 ? PFT_ERR_NO_DEVICE : PFT_ERR_STATE, "selectView");
+    return check(pft_view_select_device(handle_, device_points, n, m12, max_points), "selectView");
+  }
+  // ... of the grown model of a pft::ModelGrowth, device to device (modelDevice() waits for that handle's stream)
+  template <class Growth, class = decltype(&Growth::modelDevice)>
+  int selectView(Growth& grow, const float* m12 = nullptr, uint32_t max_points = 0) {
+    const pft_point_xyzrgba* p = nullptr;
+    size_t n = 0;
+    grow.modelDevice(&p, &n);
+    return selectView(p, n, m12, max_points);
+  }
+  // waits for the last selectView()
+  pft_view_stats getView() const {
+    pft_view_stats v;
+    std::memset(&v, 0, sizeof(v));
+    if (handle_) check(pft_get_view(handle_, &v), "getView");
+    return v;
+  }
+  // per model record: PFT_VIEW_* and the self gap
+  void getViewPoints(std::vector<uint8_t>& state, std::vector<float>& self_gap) const {
+    state.clear();
+    self_gap.clear();
+    size_t n = 0;
+    if (handle_ && check(pft_get_view_points(handle_, nullptr, nullptr, 0, &n), "getViewPoints") == PFT_OK && n) {
+      state.resize(n);
+      self_gap.resize(n);
+      check(pft_get_view_points(handle_, state.data(), self_gap.data(), n, &n), "getViewPoints");
+    }
+  }
+  // the kept records' indices into the model, ascending
+  void getViewIndices(std::vector<uint32_t>& idx) const {
+    idx.clear();
+    size_t n = 0;
+    if (handle_ && check(pft_get_view_indices(handle_, nullptr, 0, &n), "getViewIndices") == PFT_OK && n) {
+      idx.resize(n);
+      check(pft_get_view_indices(handle_, idx.data(), n, &n), "getViewIndices");
+    }
+  }
+  // the kept records, whole, in index order
+  void getViewCloud(PointCloudIn& out) const {
+    out.points.clear();
+    size_t n = 0;
+    if (handle_ && check(pft_get_view_cloud(handle_, nullptr, 0, &n), "getViewCloud") == PFT_OK && n) {
+      out.points.resize(n);
+      check(pft_get_view_cloud(handle_, out.points.data(), n, &n), "getViewCloud");
+    }
+    out.width = (uint32_t)out.points.size();
+    out.height = 1;
+  }
+  // the view cloud of the last selectView() becomes the reference cloud (waits).  The object is the same: the lost, the
+  // visibility and the spread rule keep their streaks.  A refusal (PFT_ERR_STATE: fewer than max(min_points, 1) points
+  // kept, a select that was not evaluated or is consumed already) prints its text and leaves the old reference in force
+  int setReferenceFromView(uint32_t min_points = 1) {
+    if (!handle_) return check(PFT_ERR_STATE, "setReferenceFromView");
+    const int st = check(pft_set_reference_from_view(handle_, min_points), "setReferenceFromView");
+    if (st != PFT_OK) return st;
+    std::shared_ptr<PointCloudIn> ref(new PointCloudIn());
+    getViewCloud(*ref);
+    ref_ = ref;
+    return PFT_OK;
+  }
 
   // ---- re-acquisition of a lost object (pft.h, pft_reacquire) ----
   // every centre (n_centres x 3 floats) with every orientation of cfg's lattice is scored against the input cloud the handle

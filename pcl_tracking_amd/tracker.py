@@ -124,6 +124,24 @@ class VisibilityStats:
 
 
 @dataclass
+class ViewStats:
+    """pft_view_stats: the counts of one selectView()"""
+    transform: np.ndarray  # 3x4 float32, the T used
+    n_model: int
+    n_state: tuple         # records per state: kept, decimated, self-occluded, out of view, non-finite
+    n_visible: int
+    n_kept: int
+    evaluated: bool
+    calls: int
+
+    @classmethod
+    def from_struct(cls, r):
+        return cls(transform=np.array(r.transform, dtype=np.float32).reshape(3, 4), n_model=int(r.n_model),
+                   n_state=tuple(int(v) for v in r.n_state), n_visible=int(r.n_visible), n_kept=int(r.n_kept),
+                   evaluated=bool(r.evaluated), calls=int(r.calls))
+
+
+@dataclass
 class PopulationStats:
     """pft_population_stats: how sure the filter is about its pose"""
     sum_w: float           # the 29 tree sums in double: weights, squared weights,
@@ -770,6 +788,95 @@ class ParticleFilterTracker:
     def isLostVisible(self):
         """the lost flag of the occlusion-aware rule after the last computeVisibility() (waits for it)"""
         return self.getVisibility().lost
+
+    # ---- the view-dependent reference: a full model's visible side as the reference cloud ----
+    def selectView(self, model, matrix=None, max_points=0):
+        """enqueues the selection of the points of `model` that the visibility camera sees at `matrix` (3x4 or 4x4; None:
+        the result pose of the last compute()); nothing waits.  model: a host cloud, a (device pointer, count) pair, or a
+        ModelGrowth (its grown model, device to device).  max_points: 0 = no limit"""
+        if matrix is None:
+            if self._h is None:
+                raise PftError(7, "selectView without a matrix before the first compute()")
+            m = None
+        else:
+            self._ensure()
+            m = np.ascontiguousarray(np.asarray(matrix, np.float32).reshape(-1)[:12])
+            if m.size != 12:
+                raise PftError(1, "selectView: the matrix must have 3x4 or 4x4 entries")
+        if hasattr(model, "modelDevice"):
+            p, n = model.modelDevice()  # (waits for the growth handle's stream)
+            self._view_keep = model
+            self._check(self._L.pft_view_select_device(self._h, C.c_void_p(p), n, _ptr(m), int(max_points)))
+        elif isinstance(model, tuple):
+            p, n = model
+            self._view_keep = None
+            self._check(self._L.pft_view_select_device(self._h, C.c_void_p(int(p)), int(n), _ptr(m), int(max_points)))
+        else:
+            cloud = np.ascontiguousarray(model, POINT_DTYPE)
+            self._view_keep = cloud
+            self._check(self._L.pft_view_select(self._h, _ptr(cloud), len(cloud), _ptr(m), int(max_points)))
+
+    def getView(self):
+        """waits for the last selectView(); returns ViewStats"""
+        if self._h is None:
+            raise PftError(7, "getView before the first selectView()")
+        r = _lib.ViewStatsStruct()
+        self._check(self._L.pft_get_view(self._h, C.byref(r)))
+        return ViewStats.from_struct(r)
+
+    def getViewPoints(self):
+        """per model record: (state uint8 -- 0 kept, 1 decimated, 2 occluded by the model itself, 3 out of view, 4 not
+        finite --, self_gap float32)"""
+        if self._h is None:
+            raise PftError(7, "getViewPoints before the first selectView()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_view_points(self._h, None, None, 0, C.byref(n)))
+        st = np.zeros(n.value, np.uint8)
+        gap = np.zeros(n.value, np.float32)
+        self._check(self._L.pft_get_view_points(self._h, _ptr(st), _ptr(gap), n.value, C.byref(n)))
+        return st, gap
+
+    def getViewIndices(self):
+        """the kept records' indices into the model, ascending (uint32)"""
+        if self._h is None:
+            raise PftError(7, "getViewIndices before the first selectView()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_view_indices(self._h, None, 0, C.byref(n)))
+        idx = np.zeros(n.value, np.uint32)
+        self._check(self._L.pft_get_view_indices(self._h, _ptr(idx), n.value, C.byref(n)))
+        return idx
+
+    def getViewCloud(self):
+        """the kept records, whole, in index order"""
+        if self._h is None:
+            raise PftError(7, "getViewCloud before the first selectView()")
+        n = C.c_size_t()
+        self._check(self._L.pft_get_view_cloud(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, POINT_DTYPE)
+        self._check(self._L.pft_get_view_cloud(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def viewCloudDevice(self):
+        """(device pointer, n): the view cloud in HBM, valid until the next selectView()"""
+        if self._h is None:
+            raise PftError(7, "viewCloudDevice before the first selectView()")
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(self._L.pft_view_cloud_device(self._h, C.byref(p), C.byref(n)))
+        return p.value or 0, n.value
+
+    def setReferenceFromView(self, min_points=1):
+        """the view cloud of the last selectView() becomes the reference cloud (waits).  The object is the same: the lost,
+        visibility and spread rules keep their streaks.  PftError(7), the old reference still in force, when the view keeps
+        fewer than max(min_points, 1) points, was not evaluated, or has been consumed already"""
+        if self._h is None:
+            raise PftError(7, "setReferenceFromView before the first selectView()")
+        self._check(self._L.pft_set_reference_from_view(self._h, int(min_points)))
+        self._ref = self.getViewCloud()  # what a later close() and re-creation hands to the new handle
+
+    def debugSetViewGrid(self, blocks):
+        """test hook: the workgroups of every pass of the selectView() calls that follow (0: the default)"""
+        self._ensure()
+        self._check(self._L.pft_debug_set_view_grid(self._h, int(blocks)))
 
     # ---- re-acquisition of a lost object ----
     def reacquire(self, centres=None, segmenter=None, n=(1, 1, 8), span=(0.0, 0.0, 2.0 * np.pi), base_rpy=None,
