@@ -139,6 +139,42 @@ int pft_debug_segment_hypotheses(pft_segment* s, int32_t* samples, uint32_t* cou
 int pft_debug_segment_round_hypotheses(pft_segment* s, size_t round, int32_t* samples, uint32_t* counts,
                                        size_t capacity, size_t* n);
 
+/* ---- what the one-lane tail of a round's refit did (csrc/pft_segment_solve.h fills one per solve) ----
+ * Everything between the nine sums and the coefficients is + - * / sqrt in float except three library calls; the
+ * record holds their arguments and results, so a restatement given the same three values reproduces every other
+ * field bit for bit. */
+enum {
+  PFT_REFIT_SCALE_TINY = 1u << 0,     /* largest |covariance entry| <= FLT_MIN: scale = 1 */
+  PFT_REFIT_C0_SMALL = 1u << 1,       /* |c0| < FLT_EPSILON: computeRoots2 */
+  PFT_REFIT_A_CLAMPED = 1u << 2,      /* a_over_3 > 0 set to 0 */
+  PFT_REFIT_Q_CLAMPED = 1u << 3,      /* q > 0 set to 0 */
+  PFT_REFIT_SWAP_01 = 1u << 4,        /* the three swaps of the root sort, in source order */
+  PFT_REFIT_SWAP_12 = 1u << 5,
+  PFT_REFIT_SWAP_01_AGAIN = 1u << 6,
+  PFT_REFIT_R0_FALLBACK = 1u << 7,    /* smallest root <= 0: computeRoots2 */
+  PFT_REFIT_D_NEGATIVE = 1u << 8,     /* computeRoots2's discriminant < 0 set to 0 */
+  PFT_REFIT_PICK_0 = 1u << 9,         /* the longest cross product: rows (0,1), (0,2), (1,2) */
+  PFT_REFIT_PICK_1 = 1u << 10,
+  PFT_REFIT_PICK_2 = 1u << 11,
+  PFT_REFIT_ZERO_LENGTH = 1u << 12    /* its squared length is 0: the normal is 0 / 0 */
+};
+typedef struct pft_segment_refit_debug {
+  uint32_t m;                  /* inliers of the best hypothesis: the terms of each sum */
+  uint32_t branches;           /* PFT_REFIT_* */
+  float accu[9];               /* the sums of xx xy xz yy yz zz x y z, divided by m */
+  float cov[6];                /* xx xy xz yy yz zz */
+  float scale;
+  float trig_arg[3];           /* atan2f's y and x, then theta = atan2f(y, x) / 3, the argument of cosf and sinf */
+  float trig[3];               /* atan2f(y, x), cosf(theta), sinf(theta); all six are 0 when computeRoots2 came first */
+  float roots[3];              /* of the scaled matrix, ascending, as the eigenvector step uses them */
+  float len[3];                /* squared lengths of the three cross products */
+  float coef[4];               /* the result: pft_segment_plane::coefficients */
+} pft_segment_refit_debug;
+/* the record of one round's refit (the single plane is round 0).  PFT_ERR_INVALID_ARG: no such round;
+ * PFT_ERR_STATE with a text: no apply yet, the round found no plane, or no refit ran (optimize_coefficients off, or
+ * fewer than 4 inliers: the coefficients stay) */
+int pft_debug_segment_refit(pft_segment* s, size_t round, pft_segment_refit_debug* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,15 @@ class SegmentPlane(C.Structure):
     ]
 
 
+class SegmentRefitDebug(C.Structure):
+    """pft_segment_refit_debug (include/pft_segment.h)"""
+    _fields_ = [
+        ("m", C.c_uint32), ("branches", C.c_uint32), ("accu", C.c_float * 9), ("cov", C.c_float * 6),
+        ("scale", C.c_float), ("trig_arg", C.c_float * 3), ("trig", C.c_float * 3), ("roots", C.c_float * 3),
+        ("len", C.c_float * 3), ("coef", C.c_float * 4),
+    ]
+
+
 PLANE_FOUND, PLANE_NONE, PLANE_DISABLED = 0, 1, 2
 SEGMENT_MAX_PLANES = 16
 ROUNDS_STOP_FRACTION, ROUNDS_STOP_NO_PLANE, ROUNDS_STOP_MAX_PLANES = 0, 1, 2
@@ -393,6 +402,7 @@ SYMBOLS = [
     ("pft_segment_set_refit_order", C.c_int, [_vp, C.c_int]),
     ("pft_debug_segment_round_hypotheses", C.c_int, [_vp, _sz, _vp, _vp, _sz, _P(_sz)]),
     ("pft_segment_clusters_device", C.c_int, [_vp, _P(_vp), _P(_sz)]),
+    ("pft_debug_segment_refit", C.c_int, [_vp, _sz, _P(SegmentRefitDebug)]),
     # include/pft_model.h
     ("pft_model_create", C.c_int, [C.c_int, _P(_vp)]),
     ("pft_model_destroy", None, [_vp]),

@@ -12,7 +12,7 @@ OUT_DIR = os.path.join(_HERE, "_build")
 LIB = os.path.join(OUT_DIR, "libpft_hip.so")
 SOURCES = ["pft_kernels.hip", "pft_octree.hip", "pft_octree_gated.hip", "pft_octree_sorted.hip", "pft_likelihood.hip", "pft_population.hip", "pft_kld.hip", "pft_change.hip", "pft_exact_nn.hip", "pft_hull.hip", "pft_api.hip", "pft_frame.hip", "pft_api_debug.hip", "pft_api_features.hip",
            "pft_filters.hip", "pft_segment.hip", "pft_report.hip", "pft_model.hip", "pft_match.hip", "pft_reacquire.hip", "pft_spread.hip", "pft_refine.hip", "pft_subtract.hip", "pft_visibility.hip", "pft_depth.hip", "pft_grow.hip", "pft_view.hip"]
-HEADERS = ["pft_internal.h", "pft_tracker.h", "pft_devbuf.h", "pft_device_utils.h", "pft_vis_project.h", "pft_alias.h", "pft_octree_box.h", "pft_report_solve.h", "pft_match_search.h", "pft_pair_tree.h", "pft_spread_final.h", "pft_refine_solve.h", os.path.join("..", "..", "include", "pft.h"),
+HEADERS = ["pft_internal.h", "pft_tracker.h", "pft_devbuf.h", "pft_device_utils.h", "pft_vis_project.h", "pft_alias.h", "pft_octree_box.h", "pft_report_solve.h", "pft_match_search.h", "pft_pair_tree.h", "pft_spread_final.h", "pft_refine_solve.h", "pft_segment_solve.h", os.path.join("..", "..", "include", "pft.h"),
            os.path.join("..", "..", "include", "pft_filters.h"), os.path.join("..", "..", "include", "pft_segment.h"),
            os.path.join("..", "..", "include", "pft_model.h"), os.path.join("..", "..", "include", "pft_subtract.h"),
            os.path.join("..", "..", "include", "pft_visibility.h"), os.path.join("..", "..", "include", "pft_grow.h"),

@@ -25,6 +25,7 @@
 
 #include "pft_devbuf.h"
 #include "pft_device_utils.h"
+#include "pft_segment_solve.h"
 #include "../../include/pft_segment.h"
 
 #define SG_TILE 1024u
@@ -57,6 +58,8 @@ struct SgHdr {
   float bmin[3], bmax[3];
   // sampler state (mt19937 and the sparse map live in HBM between batches)
   uint32_t mt_pos, map_count, emitted;
+  // what the one-lane tail of this round's refit did (m = 0: no refit ran)
+  pft_segment_refit_debug refit;
 };
 
 struct SgHyp {
@@ -512,96 +515,17 @@ __global__ __launch_bounds__(SG_THREADS) void k_sg_select(SgParams p, const SgHd
   if (sflag) sg_tile_count(sflag, n, stile);
 }
 
-// RULE eigen: pcl::computeRoots / computeRoots2 / eigen33 (smallest eigenvalue's vector) in float
-__device__ void sg_roots2(float b, float c, float* r) {
-  r[0] = 0.0f;
-  float d = (float)((double)(b * b) - 4.0 * (double)c);
-  if (d < 0.0f) d = 0.0f;
-  const float sd = sqrtf(d);
-  r[2] = 0.5f * (b + sd);
-  r[1] = 0.5f * (b - sd);
-}
-__device__ void sg_roots(const float* m, float* r) {  // m row-major 3x3
-  const float m00 = m[0], m01 = m[1], m02 = m[2], m11 = m[4], m12 = m[5], m22 = m[8];
-  const float c0 = m00 * m11 * m22 + 2.0f * m01 * m02 * m12 - m00 * m12 * m12 - m11 * m02 * m02 - m22 * m01 * m01;
-  const float c1 = m00 * m11 - m01 * m01 + m00 * m22 - m02 * m02 + m11 * m22 - m12 * m12;
-  const float c2 = m00 + m11 + m22;
-  if (fabsf(c0) < FLT_EPSILON) {
-    sg_roots2(c2, c1, r);
-    return;
-  }
-  const float s_inv3 = (float)(1.0 / 3.0);
-  const float s_sqrt3 = sqrtf(3.0f);
-  const float c2_over_3 = c2 * s_inv3;
-  float a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
-  if (a_over_3 > 0.0f) a_over_3 = 0.0f;
-  const float half_b = 0.5f * (c0 + c2_over_3 * (2.0f * c2_over_3 * c2_over_3 - c1));
-  float q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
-  if (q > 0.0f) q = 0.0f;
-  const float rho = sqrtf(-a_over_3);
-  const float theta = atan2f(sqrtf(-q), half_b) * s_inv3;
-  const float ct = cosf(theta), st = sinf(theta);
-  r[0] = c2_over_3 + 2.0f * rho * ct;
-  r[1] = c2_over_3 - rho * (ct + s_sqrt3 * st);
-  r[2] = c2_over_3 - rho * (ct - s_sqrt3 * st);
-  float t;
-  if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
-  if (r[1] >= r[2]) {
-    t = r[1]; r[1] = r[2]; r[2] = t;
-    if (r[0] >= r[1]) { t = r[0]; r[0] = r[1]; r[1] = t; }
-  }
-  if (r[0] <= 0.0f) sg_roots2(c2, c1, r);
-}
-__device__ void sg_eigen33(const float* mat, float* vec) {
-  float scale = 0.0f;
-  for (int k = 0; k < 9; k++) scale = fmaxf(scale, fabsf(mat[k]));
-  if (scale <= FLT_MIN) scale = 1.0f;
-  float m[9];
-  for (int k = 0; k < 9; k++) m[k] = mat[k] / scale;
-  float r[3];
-  sg_roots(m, r);
-  m[0] -= r[0];
-  m[4] -= r[0];
-  m[8] -= r[0];
-  float v[3][3];
-  const int ra[3] = {0, 0, 1}, rb[3] = {1, 2, 2};
-  float len[3];
-  for (int k = 0; k < 3; k++) {
-    const float* a = m + 3 * ra[k];
-    const float* b = m + 3 * rb[k];
-    v[k][0] = a[1] * b[2] - a[2] * b[1];
-    v[k][1] = a[2] * b[0] - a[0] * b[2];
-    v[k][2] = a[0] * b[1] - a[1] * b[0];
-    len[k] = v[k][0] * v[k][0] + (v[k][1] * v[k][1] + v[k][2] * v[k][2]);  // Vector3f::squaredNorm
-  }
-  int pick = 2;
-  if (len[0] >= len[1] && len[0] >= len[2]) pick = 0;
-  else if (len[1] >= len[0] && len[1] >= len[2]) pick = 1;
-  const float s = sqrtf(len[pick]);
-  vec[0] = v[pick][0] / s;
-  vec[1] = v[pick][1] / s;
-  vec[2] = v[pick][2] / s;
-}
-
-// the refit after the sums, one lane: accu = the nine sums divided by the count
+// RULE eigen: pcl::computeRoots / computeRoots2 / eigen33 (smallest eigenvalue's vector) in float: pft_segment_solve.h,
+// host and device.  The refit after the sums, one lane: accu = the nine sums divided by the count; the record of the
+// solve stays in the header for pft_debug_segment_refit
 __device__ void sg_refit_tail(SgHdr* __restrict__ h, const float* accu) {
-  float cov[9];
-  cov[0] = accu[0] - accu[6] * accu[6];
-  cov[1] = accu[1] - accu[6] * accu[7];
-  cov[2] = accu[2] - accu[6] * accu[8];
-  cov[4] = accu[3] - accu[7] * accu[7];
-  cov[5] = accu[4] - accu[7] * accu[8];
-  cov[8] = accu[5] - accu[8] * accu[8];
-  cov[3] = cov[1];
-  cov[6] = cov[2];
-  cov[7] = cov[5];
-  float e[3];
-  sg_eigen33(cov, e);
-  const float dot = (e[0] * accu[6] + e[1] * accu[7]) + (e[2] * accu[8] + 0.0f * 1.0f);
-  h->coef_final[0] = e[0];
-  h->coef_final[1] = e[1];
-  h->coef_final[2] = e[2];
-  h->coef_final[3] = -1.0f * dot;
+  pft_segment_refit_debug rec;
+  sg_refit_solve(accu, h->n_ransac_inl, &rec);
+  h->coef_final[0] = rec.coef[0];
+  h->coef_final[1] = rec.coef[1];
+  h->coef_final[2] = rec.coef[2];
+  h->coef_final[3] = rec.coef[3];
+  h->refit = rec;
 }
 
 // RULE refit: optimizeModelCoefficients -- nine float accumulators summed in inlier index order, divided by the
@@ -1893,5 +1817,25 @@ extern "C" int pft_debug_segment_round_hypotheses(pft_segment* s, size_t round, 
   if (!samples || !counts) return PFT_ERR_INVALID_ARG;
   PFT_HIPCHK(s, hipMemcpy(samples, s->hyp.sample + 3 * off, 3 * cnt * sizeof(int32_t), hipMemcpyDeviceToHost));
   PFT_HIPCHK(s, hipMemcpy(counts, s->hyp.count + off, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return PFT_OK;
+}
+
+extern "C" int pft_debug_segment_refit(pft_segment* s, size_t round, pft_segment_refit_debug* out) {
+  if (!s || !out) return PFT_ERR_INVALID_ARG;
+  if (!s->have_result) {
+    s->err = "pft_debug_segment_refit: no apply yet";
+    return PFT_ERR_STATE;
+  }
+  if (round >= s->rounds.size()) return bad_round(s, "pft_debug_segment_refit");
+  const SgHdr& h = s->rounds[round];
+  if (!s->cfg.plane_enable || h.best_h < 0) {
+    s->err = "pft_debug_segment_refit: the round found no plane";
+    return PFT_ERR_STATE;
+  }
+  if (!s->cfg.optimize_coefficients || h.n_ransac_inl < 4 || h.refit.m == 0) {
+    s->err = "pft_debug_segment_refit: no refit ran (optimize_coefficients off, or fewer than 4 inliers)";
+    return PFT_ERR_STATE;
+  }
+  *out = h.refit;
   return PFT_OK;
 }

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import PftError, SegmentConfig, SegmentPlane
+from ._lib import PftError, SegmentConfig, SegmentPlane, SegmentRefitDebug
 from .scene import POINT_DTYPE
 
 
@@ -216,6 +216,16 @@ class ModelSegmenter:
         self._check(self._L.pft_debug_segment_round_hypotheses(self._h, round, _ptr(smp), _ptr(cnt), n.value,
                                                                C.byref(n)))
         return smp, cnt
+
+    def refitDebug(self, round=0):
+        """what the one-lane tail of a round's refit did (pft_segment_refit_debug) as a dict of NumPy values; raises
+        PftError when the round found no plane or no refit ran"""
+        d = SegmentRefitDebug()
+        self._check(self._L.pft_debug_segment_refit(self._h, round, C.byref(d)))
+        out = {"m": d.m, "branches": d.branches, "scale": np.float32(d.scale)}
+        for k in ("accu", "cov", "trig_arg", "trig", "roots", "len", "coef"):
+            out[k] = np.array(getattr(d, k), np.float32)
+        return out
 
     def lastMilliseconds(self):
         """(total, {stage: ms})"""

@@ -139,96 +139,168 @@ def ransac_stop(counts, n, max_iterations=1000, probability=0.99):
     return it, best_h
 
 
-# ---- RULE eigen + refit ----
-def _roots2(b, c):
+# ---- RULE eigen + refit: csrc/pft_segment_solve.h line for line ----
+# branch bits of the record (include/pft_segment.h PFT_REFIT_*)
+SCALE_TINY, C0_SMALL, A_CLAMPED, Q_CLAMPED, SWAP_01, SWAP_12, SWAP_01_AGAIN, R0_FALLBACK, D_NEGATIVE, PICK_0, PICK_1, \
+    PICK_2, ZERO_LENGTH = (1 << k for k in range(13))
+BRANCH_NAMES = ("scale_tiny", "c0_small", "a_clamped", "q_clamped", "swap_01", "swap_12", "swap_01_again", "r0_fallback",
+                "d_negative", "pick_0", "pick_1", "pick_2", "zero_length")
+
+
+def branch_names(bits):
+    return [n for k, n in enumerate(BRANCH_NAMES) if bits >> k & 1]
+
+
+def _roots2(b, c, t):
     d = F(float(F(b * b)) - 4.0 * float(c))
     if d < 0:
         d = F(0)
+        t["branches"] |= D_NEGATIVE
     sd = F(np.sqrt(d))
     return [F(0), F(F(0.5) * F(b - sd)), F(F(0.5) * F(b + sd))]
 
 
-def _roots(m):
+def _roots(m, t, trig=None):
     m00, m01, m02, m11, m12, m22 = m[0, 0], m[0, 1], m[0, 2], m[1, 1], m[1, 2], m[2, 2]
     c0 = F(F(F(F(F(F(m00 * m11) * m22) + F(F(F(F(2) * m01) * m02) * m12)) - F(F(m00 * m12) * m12)) - F(F(m11 * m02) * m02))
            - F(F(m22 * m01) * m01))
     c1 = F(F(F(F(F(F(m00 * m11) - F(m01 * m01)) + F(m00 * m22)) - F(m02 * m02)) + F(m11 * m22)) - F(m12 * m12))
     c2 = F(F(m00 + m11) + m22)
     if abs(c0) < np.finfo(F).eps:
-        return _roots2(c2, c1)
+        t["branches"] |= C0_SMALL
+        return _roots2(c2, c1, t)
     s_inv3 = F(1.0 / 3.0)
     s_sqrt3 = F(np.sqrt(F(3)))
     c2o3 = F(c2 * s_inv3)
     a_o3 = F(F(c1 - F(c2 * c2o3)) * s_inv3)
     if a_o3 > 0:
         a_o3 = F(0)
+        t["branches"] |= A_CLAMPED
     half_b = F(F(0.5) * F(c0 + F(c2o3 * F(F(F(F(2) * c2o3) * c2o3) - c1))))
     q = F(F(half_b * half_b) + F(F(a_o3 * a_o3) * a_o3))
     if q > 0:
         q = F(0)
+        t["branches"] |= Q_CLAMPED
     rho = F(np.sqrt(F(-a_o3)))
-    theta = F(F(np.arctan2(F(np.sqrt(F(-q))), half_b)) * s_inv3)
-    ct, st = F(np.cos(theta)), F(np.sin(theta))
+    ay = F(np.sqrt(F(-q)))
+    at = F(np.arctan2(ay, half_b)) if trig is None else F(trig[0])
+    theta = F(at * s_inv3)
+    ct, st = (F(np.cos(theta)), F(np.sin(theta))) if trig is None else (F(trig[1]), F(trig[2]))
+    t["trig_arg"] = np.array([ay, half_b, theta], F)
+    t["trig"] = np.array([at, ct, st], F)
     r = [F(c2o3 + F(F(F(2) * rho) * ct)), F(c2o3 - F(rho * F(ct + F(s_sqrt3 * st)))),
          F(c2o3 - F(rho * F(ct - F(s_sqrt3 * st))))]
     if r[0] >= r[1]:
         r[0], r[1] = r[1], r[0]
+        t["branches"] |= SWAP_01
     if r[1] >= r[2]:
         r[1], r[2] = r[2], r[1]
+        t["branches"] |= SWAP_12
         if r[0] >= r[1]:
             r[0], r[1] = r[1], r[0]
+            t["branches"] |= SWAP_01_AGAIN
     if r[0] <= 0:
-        return _roots2(c2, c1)
+        t["branches"] |= R0_FALLBACK
+        return _roots2(c2, c1, t)
     return r
 
 
-def eigen33(mat):
+def eigen33_trace(mat, trig=None):
+    """pcl::eigen33 (the smallest eigenvalue's vector) with the record of pft_segment_refit_debug: scale, trig_arg[3],
+    trig[3], roots[3], len[3], branches, and `vec`.  trig = (atan2 value, cos, sin): used in place of NumPy's own, so that
+    everything else can be compared bit for bit with a solve that ran on another libm"""
     mat = np.asarray(mat, F)
+    t = {"branches": 0, "trig_arg": np.zeros(3, F), "trig": np.zeros(3, F)}
     scale = F(np.max(np.abs(mat)))
     if scale <= np.finfo(F).tiny:
         scale = F(1)
-    m = (mat / scale).astype(F)
-    r = _roots(m)
-    for k in range(3):
-        m[k, k] = F(m[k, k] - r[0])
-    vs, ls = [], []
-    for a, b in ((0, 1), (0, 2), (1, 2)):
-        A, B = m[a], m[b]
-        v = [F(F(A[1] * B[2]) - F(A[2] * B[1])), F(F(A[2] * B[0]) - F(A[0] * B[2])), F(F(A[0] * B[1]) - F(A[1] * B[0]))]
-        vs.append(v)
-        ls.append(F(v[0] * v[0] + F(F(v[1] * v[1]) + F(v[2] * v[2]))))
-    if ls[0] >= ls[1] and ls[0] >= ls[2]:
-        k = 0
-    elif ls[1] >= ls[0] and ls[1] >= ls[2]:
-        k = 1
-    else:
-        k = 2
-    s = F(np.sqrt(ls[k]))
-    return np.array([F(v / s) for v in vs[k]], F)
+        t["branches"] |= SCALE_TINY
+    t["scale"] = scale
+    with np.errstate(all="ignore"):
+        m = (mat / scale).astype(F)
+        r = _roots(m, t, trig)
+        t["roots"] = np.array(r, F)
+        for k in range(3):
+            m[k, k] = F(m[k, k] - r[0])
+        vs, ls = [], []
+        for a, b in ((0, 1), (0, 2), (1, 2)):
+            A, B = m[a], m[b]
+            v = [F(F(A[1] * B[2]) - F(A[2] * B[1])), F(F(A[2] * B[0]) - F(A[0] * B[2])),
+                 F(F(A[0] * B[1]) - F(A[1] * B[0]))]
+            vs.append(v)
+            ls.append(F(F(v[0] * v[0]) + F(F(v[1] * v[1]) + F(v[2] * v[2]))))
+        t["len"] = np.array(ls, F)
+        if ls[0] >= ls[1] and ls[0] >= ls[2]:
+            k = 0
+        elif ls[1] >= ls[0] and ls[1] >= ls[2]:
+            k = 1
+        else:
+            k = 2
+        t["branches"] |= (PICK_0, PICK_1, PICK_2)[k]
+        if ls[k] == 0:
+            t["branches"] |= ZERO_LENGTH
+        s = F(np.sqrt(ls[k]))
+        t["vec"] = np.array([F(v / s) for v in vs[k]], F)
+    return t
 
 
-def refit(xyz, coef):
-    """optimizeModelCoefficients over the inlier points (in index order)"""
-    n = len(xyz)
-    if n < 4:
-        return np.asarray(coef, F)
+def eigen33(mat):
+    return eigen33_trace(mat)["vec"]
+
+
+def moment_terms(xyz):
     x, y, z = (xyz[:, k].astype(F) for k in range(3))
-    terms = [x * x, x * y, x * z, y * y, y * z, z * z, x, y, z]
-    accu = []
-    for t in terms:  # sequential float sums in index order
-        accu.append(F(np.cumsum(t.astype(F), dtype=F)[-1]))
-    accu = [F(a / F(n)) for a in accu]
+    return [(x * x).astype(F), (x * y).astype(F), (x * z).astype(F), (y * y).astype(F), (y * z).astype(F),
+            (z * z).astype(F), x, y, z]
+
+
+def moment_sums(xyz, order):
+    """the nine sums: "pcl" sequential float sums in index order, "tree" adjacent-pair trees"""
+    if order == "pcl":
+        return np.array([F(np.cumsum(t, dtype=F)[-1]) for t in moment_terms(xyz)], F)
+    from report_model import tree_sum
+    return np.array([F(tree_sum(t)) for t in moment_terms(xyz)], F)
+
+
+def moment_means(xyz, order):
+    """the nine sums divided by the count"""
+    return np.array([F(a / F(len(xyz))) for a in moment_sums(xyz, order)], F)
+
+
+def solve_trace(accu, m, trig=None):
+    """sg_refit_solve: from the nine means to the record (coef included)"""
+    accu = np.asarray(accu, F)
     cov = np.zeros((3, 3), F)
-    cov[0, 0] = F(accu[0] - F(accu[6] * accu[6]))
-    cov[0, 1] = F(accu[1] - F(accu[6] * accu[7]))
-    cov[0, 2] = F(accu[2] - F(accu[6] * accu[8]))
-    cov[1, 1] = F(accu[3] - F(accu[7] * accu[7]))
-    cov[1, 2] = F(accu[4] - F(accu[7] * accu[8]))
-    cov[2, 2] = F(accu[5] - F(accu[8] * accu[8]))
-    cov[1, 0], cov[2, 0], cov[2, 1] = cov[0, 1], cov[0, 2], cov[1, 2]
-    e = eigen33(cov)
-    dot = F(F(F(e[0] * accu[6]) + F(e[1] * accu[7])) + F(F(e[2] * accu[8]) + F(F(0) * F(1))))
-    return np.array([e[0], e[1], e[2], F(F(-1) * dot)], F)
+    with np.errstate(all="ignore"):
+        cov[0, 0] = F(accu[0] - F(accu[6] * accu[6]))
+        cov[0, 1] = F(accu[1] - F(accu[6] * accu[7]))
+        cov[0, 2] = F(accu[2] - F(accu[6] * accu[8]))
+        cov[1, 1] = F(accu[3] - F(accu[7] * accu[7]))
+        cov[1, 2] = F(accu[4] - F(accu[7] * accu[8]))
+        cov[2, 2] = F(accu[5] - F(accu[8] * accu[8]))
+        cov[1, 0], cov[2, 0], cov[2, 1] = cov[0, 1], cov[0, 2], cov[1, 2]
+        t = eigen33_trace(cov, trig)
+        e = t["vec"]
+        dot = F(F(F(e[0] * accu[6]) + F(e[1] * accu[7])) + F(F(e[2] * accu[8]) + F(F(0) * F(1))))
+        t["coef"] = np.array([e[0], e[1], e[2], F(F(-1) * dot)], F)
+    t["m"] = int(m)
+    t["accu"] = accu
+    t["cov"] = np.array([cov[0, 0], cov[0, 1], cov[0, 2], cov[1, 1], cov[1, 2], cov[2, 2]], F)
+    return t
+
+
+def refit_trace(xyz, coef, order="pcl", trig=None):
+    """optimizeModelCoefficients over the inlier points (in index order) in either summation order, with the record;
+    fewer than 4 points: None (the coefficients stay).  `coef` is not read: the refit starts from the points alone, the
+    parameter keeps the signature of `refit`, which hands it back below 4 points"""
+    if len(xyz) < 4:
+        return None
+    return solve_trace(moment_means(xyz, order), len(xyz), trig)
+
+
+def refit(xyz, coef, order="pcl"):
+    t = refit_trace(xyz, coef, order)
+    return np.asarray(coef, F) if t is None else t["coef"]
 
 
 # ---- stages 1, 2, 5 ----

@@ -5,7 +5,6 @@ PCL itself is not available, so parity stays unpinned."""
 import numpy as np
 
 import segment_model as M
-from report_model import tree_sum
 
 F = np.float32
 STOP_FRACTION, STOP_NO_PLANE, STOP_MAX_PLANES = 0, 1, 2
@@ -13,26 +12,8 @@ STOP_FRACTION, STOP_NO_PLANE, STOP_MAX_PLANES = 0, 1, 2
 
 def refit(xyz, coef, order="pcl"):
     """optimizeModelCoefficients; order "tree": the nine sums as adjacent-pair trees in float over the inlier list
-    padded with -0.0 to a power of two, the products rounded to float first; everything after the sums as M.refit"""
-    if order == "pcl":
-        return M.refit(xyz, coef)
-    n = len(xyz)
-    if n < 4:
-        return np.asarray(coef, F)
-    x, y, z = (xyz[:, k].astype(F) for k in range(3))
-    terms = [x * x, x * y, x * z, y * y, y * z, z * z, x, y, z]
-    accu = [F(tree_sum(t.astype(F)) / F(n)) for t in terms]
-    cov = np.zeros((3, 3), F)
-    cov[0, 0] = F(accu[0] - F(accu[6] * accu[6]))
-    cov[0, 1] = F(accu[1] - F(accu[6] * accu[7]))
-    cov[0, 2] = F(accu[2] - F(accu[6] * accu[8]))
-    cov[1, 1] = F(accu[3] - F(accu[7] * accu[7]))
-    cov[1, 2] = F(accu[4] - F(accu[7] * accu[8]))
-    cov[2, 2] = F(accu[5] - F(accu[8] * accu[8]))
-    cov[1, 0], cov[2, 0], cov[2, 1] = cov[0, 1], cov[0, 2], cov[1, 2]
-    e = M.eigen33(cov)
-    dot = F(F(F(e[0] * accu[6]) + F(e[1] * accu[7])) + F(F(e[2] * accu[8]) + F(F(0) * F(1))))
-    return np.array([e[0], e[1], e[2], F(F(-1) * dot)], F)
+    padded with -0.0 to a power of two, the products rounded to float first; everything after the sums is the same"""
+    return M.refit(xyz, coef, order)
 
 
 def segment_once(cx, max_iterations=1000, threshold=0.015, probability=0.99, seed=12345, optimize=True, order="pcl"):
